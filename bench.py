@@ -10,6 +10,11 @@ all-reduce of the flat 18.2 MB gradient bucket per step.
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel
 (HIP-event timed inside the timed region through the library's profiling hook) and `cpu_baseline`
 (the CPU oracle restating the reference's op sequence, timed on this box's host cores, N=1 only).
+
+--steps K is the number of timed steps of the headline: K steps in all, one block by default (--repeats R: R blocks, the median
+block's time per step is `ms_per_step`), after --warmup steps and two untimed settle blocks of SETTLE_STEPS steps.  --dump-outputs DIR
+writes what the last timed step computed (loss, head outputs, updated parameters, gradients) as DIR/<name>.npy; the inputs
+and the number of steps before it depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -23,6 +28,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 B_PER_GPU, NPTS, K_NN = 32, 1024, 20
+SETTLE_STEPS, SETTLE_BLOCKS = 20, 2     # untimed blocks after --warmup (a fresh process' clocks / allocator are still ramping)
 FLOP_PER_POINT = 28.19e6        # algorithmic fwd+bwd FLOP per point (reference op sequence)
 PEAK_FP32_TFLOPS = 157.3        # MI355X_MICROARCH.md: f32 MFMA == f32 vector peak
 PEAK_HBM_GBS = 8000.0
@@ -178,11 +184,13 @@ def make_adam(params):
     return FlatAdam(params, lr=1e-3, weight_decay=5e-5)
 
 
-def gpu_step(model, mlsp, args, batch, opt):
+def gpu_step(model, mlsp, args, batch, opt, keep=None):
     """zero_grad -> forward (all three heads) -> position + normal + cardinality losses -> backward -> step
-    (PointDA/trainer.py:542-571, target branch)."""
+    (PointDA/trainer.py:542-571, target branch).  `keep` (a dict): receives the head outputs of this step."""
     opt.zero_grad()
     logits = model(batch["x"], activate_density_normal_ondef=True)
+    if keep is not None:
+        keep["logits"] = logits
     loss = mlsp.calc_loss(args, logits, batch["gold"], batch["mask"])
     loss = loss + mlsp.calc_masked_normal_loss(args, logits["Normal"], batch["normal_gt"], batch["mask_cord"])
     kl, mae = mlsp.densityloss(args, logits, batch["dens_val"], batch["dens_vec"], mask=batch["mask_cord"].reshape(-1))
@@ -190,6 +198,31 @@ def gpu_step(model, mlsp, args, batch, opt):
     loss.backward()
     opt.step()
     return loss
+
+
+def block_sizes(steps, repeats):
+    """The timed steps as (at most) `repeats` blocks of near-equal size: exactly `steps` steps in all."""
+    n = max(1, min(repeats, steps))
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+def dump_outputs(out_dir, model, loss, logits):
+    """What one training step hands its caller, as float32 .npy files in `out_dir`: the loss, every head output, and the parameters
+    the optimizer step left together with the gradients it applied (~40 MB at B = 32, N = 1024: under the 64 MB cap, no sampling)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss}
+    arrays.update(("logits.%s" % k, v) for k, v in logits.items())
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "dump of %d bytes exceeds 64 MB" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": total}
 
 
 def _cpu_info():
@@ -670,9 +703,11 @@ def stub_ranks(a, world, rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline, in all")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="blocks the --steps timed steps are split into; the median block is reported.  Every block starts from an idle "
+                         "queue: 4-step blocks measured 8 %% above 20-step ones, so keep blocks long")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="STRONG scaling: this many clouds in total, split over the ranks (SURVEY 8d config (2) secondary: 32). "
                          "Default 0 = weak scaling, 32 clouds per GPU")
@@ -680,10 +715,14 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] runs after the headline")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the comparison blocks with every GEMM on the f32 MFMA")
     ap.add_argument("--stub", action="store_true", help="launcher self-test: gloo ranks, no GPU, no kernels (never a measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # no launcher around us: become one.  Nothing in this process has initialised the GPU (and nothing will).
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -741,16 +780,19 @@ def main():
     opt = sync.wrap(make_adam(model.parameters()))                                            # trainer.py:258-259
     batch = synth_batch(b_local, NPTS, dev, seed=1000 + rank)
 
-    def one_step():
-        return gpu_step(model, mlsp, args, batch, opt)
+    def one_step(keep=None):
+        return gpu_step(model, mlsp, args, batch, opt, keep)
 
     for _ in range(a.warmup):
         one_step()
 
     import gc
 
-    def timed_block():
-        """EXACTLY a.steps steps between two (barrier + synchronize) brackets; max over ranks.  Python's cyclic garbage collector runs
+    sizes = block_sizes(a.steps, a.repeats)
+    keep = {} if a.dump_outputs and rank == 0 else None
+
+    def timed_block(nsteps):
+        """EXACTLY `nsteps` steps between two (barrier + synchronize) brackets; max over ranks.  Python's cyclic garbage collector runs
         BEFORE the bracket and is paused inside it (as `timeit` does): a generation-2 pass inside a block is host time of the interpreter,
         not of the step (it showed as a 10.8 ms block among 5.1 ms ones)."""
         torch.cuda.synchronize()
@@ -761,8 +803,8 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(a.steps):
-                last = one_step()
+            for i in range(nsteps):
+                last = one_step(keep if i == nsteps - 1 else None)
             torch.cuda.synchronize()
             if distributed:
                 dist.barrier()
@@ -777,24 +819,22 @@ def main():
         return dt_, last
 
     # After --warmup steps the clocks / allocator / caches of a fresh process are still ramping (round 2: first block 10.5 ms against 5.75):
-    # untimed SETTLE blocks run until two consecutive ones agree to 1 % (at most 4); only then do the timed blocks start.  Every rank
-    # takes the same decision (block times are max-reduced over the ranks).
-    settle, prev = [], None
-    for _ in range(4):
-        dt_s, _ = timed_block()
-        settle.append(dt_s)
-        if prev is not None and abs(dt_s - prev) <= 0.01 * prev:
-            break
-        prev = dt_s
+    # SETTLE_BLOCKS untimed blocks of SETTLE_STEPS steps run before the timed blocks (two were always enough to agree to 1 %).  A fixed
+    # count, so that the number of steps before the last timed one, and with it what that step computes, depends on the arguments only.
+    settle = [timed_block(SETTLE_STEPS)[0] / SETTLE_STEPS for _ in range(SETTLE_BLOCKS)]
 
-    # One block of a.steps steps lasts ~0.1 s: the block is repeated and the MEDIAN block is the headline (a single short
-    # sample is at the mercy of clock ramps and of whatever else the host does); min/max go into `blocks_ms_per_step`.
-    blocks = []
-    for _ in range(max(1, a.repeats)):
-        dt_b, loss = timed_block()
-        blocks.append(dt_b)
-    dt = sorted(blocks)[len(blocks) // 2]
+    # The timed steps: one block, or --repeats blocks whose MEDIAN is the headline (min/max go into `blocks_ms_per_step`).  dt: seconds
+    # for a.steps steps at the (median) block's rate.
+    def median_leg():
+        per, loss_ = [], None
+        for n in sizes:
+            dt_b, loss_ = timed_block(n)
+            per.append(dt_b / n)
+        return sorted(per)[len(per) // 2] * a.steps, per, loss_
+
+    dt, blocks, loss = median_leg()
     assert torch.isfinite(loss).item()
+    dumped = dump_outputs(a.dump_outputs, model, loss, keep["logits"]) if keep is not None else None
 
     # HIP events around every launch of the priced kernel families: a separate, untimed block AFTER the timing
     prof_steps = 3
@@ -838,27 +878,24 @@ def main():
                      "note": "all-reduce of the %d-byte gradient bucket alone: median of 10 (after 2 warm-up), HIP events around the call on "
                              "the enqueueing stream, max over ranks; bus bandwidth = 2 (n - 1) / n x bytes / time" % nbytes}
 
-    # the same step with every GEMM on the f32 MFMA, for the record (not the headline): one settle block + the same number of blocks
+    # the same step with every GEMM on the f32 MFMA, for the record (not the headline): one settle block + the same blocks as the headline
     f32_leg, f32_blocks, x6_leg, x6_blocks = None, [], None, []
     if Fh.gemm_precision.current in ("bf16x6", "f16x3") and not a.no_fp32_leg:
         with Fh.gemm_precision("fp32"):
-            timed_block()
-            f32_blocks = [timed_block()[0] for _ in range(max(1, a.repeats))]
-        f32_leg = sorted(f32_blocks)[len(f32_blocks) // 2]
+            timed_block(SETTLE_STEPS)
+            f32_leg, f32_blocks, _ = median_leg()
         if Fh.gemm_precision.current == "f16x3":                     # ... and on the six-product bf16 split (the round 3-5 default)
             with Fh.gemm_precision("bf16x6"):
-                timed_block()
-                x6_blocks = [timed_block()[0] for _ in range(max(1, a.repeats))]
-            x6_leg = sorted(x6_blocks)[len(x6_blocks) // 2]
+                timed_block(SETTLE_STEPS)
+                x6_leg, x6_blocks, _ = median_leg()
 
     if rank == 0:
         pts = b_local * NPTS * n_gpus * a.steps
         value = pts / dt
         out = {"metric": "points/sec fwd+bwd, DGCNN+MLSP B=32 N=1024 k=20", "value": value, "unit": "points/s",
                "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-               "blocks_ms_per_step": {"n": len(blocks), "median": 1e3 * dt / a.steps, "min": 1e3 * min(blocks) / a.steps,
-                                      "max": 1e3 * max(blocks) / a.steps,
-                                      "untimed_settle_blocks": [round(1e3 * t / a.steps, 3) for t in settle]},
+               "blocks_ms_per_step": {"n": len(blocks), "steps": sizes, "median": 1e3 * dt / a.steps, "min": 1e3 * min(blocks),
+                                      "max": 1e3 * max(blocks), "untimed_settle_blocks": [round(1e3 * t, 3) for t in settle]},
                "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "timing_note": "cyclic GC collected before and paused inside every timed block (timeit's convention)",
                "config": {"workload": "DGCNN encoder + 3 MLSP heads + losses, fwd+bwd+Adam, B=%d/GPU N=1024 k=20 fp32 "
@@ -873,11 +910,11 @@ def main():
         if x6_leg is not None:
             out["bf16x6_split"] = {"ms_per_step": 1e3 * x6_leg / a.steps, "value": pts / x6_leg,
                                    "note": "the same step with the GEMM family on the six-product bf16 split (gemm_precision('bf16x6'), the "
-                                           "round 3-5 default): median of %d blocks of %d steps, same process" % (len(x6_blocks), a.steps)}
+                                           "round 3-5 default): median of %d blocks, %d steps in all, same process" % (len(x6_blocks), a.steps)}
         if f32_leg is not None:
             out["fp32_mfma"] = {"ms_per_step": 1e3 * f32_leg / a.steps, "value": pts / f32_leg,
-                                "note": "the same step with every GEMM on the f32 MFMA (gemm_precision('fp32')): median of %d blocks "
-                                        "of %d steps, timed after the headline blocks in the same process" % (len(f32_blocks), a.steps)}
+                                "note": "the same step with every GEMM on the f32 MFMA (gemm_precision('fp32')): median of %d blocks, "
+                                        "%d steps in all, timed after the headline blocks in the same process" % (len(f32_blocks), a.steps)}
         P_ROWS = b_local * NPTS
         if prof and prof[1] > 0:
             # prof = [total ms of the GEMM family, launches, algorithmic FLOP summed over launches, algorithmic bytes];
@@ -1007,6 +1044,8 @@ def main():
             out["secondary"].append(trainer_shaped_workload(dev))
         if n_gpus == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out))
     if distributed:
         dist.destroy_process_group()

@@ -88,3 +88,36 @@ def test_profile_without_the_priced_kernel_is_an_error(tmp_path):
     t, src, n = b.pmc_gemm_traffic("gemm_split_kernel", "configs1", root=str(tmp_path))
     assert src.endswith("summary_v2.csv") and n == 4
     assert b.pmc_gemm_traffic("gemm_split_kernel", "configs1", root=str(tmp_path / "nowhere")) == (None, None, 0)
+
+
+# ---- --steps is the number of timed steps; --dump-outputs writes what the last step computed ----
+def test_timed_blocks_hold_exactly_steps():
+    b = _bench_module()
+    for steps in (1, 2, 5, 7, 20, 101):
+        for repeats in (1, 3, 5, 50):
+            sizes = b.block_sizes(steps, repeats)
+            assert sum(sizes) == steps and len(sizes) == min(steps, repeats) and min(sizes) >= 1
+            assert max(sizes) - min(sizes) <= 1
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench_module()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.ReLU(), torch.nn.Linear(4, 2, bias=False))
+    x = torch.randn(5, 3, dtype=torch.float64)
+    logits = {"cls": model.double()(x)}
+    loss = logits["cls"].square().mean()
+    loss.backward()
+    rec = b.dump_outputs(str(tmp_path / "d"), model, loss, logits)
+    files = sorted(p.name for p in (tmp_path / "d").iterdir())
+    assert files == sorted(["loss.npy", "logits.cls.npy", "param.0.weight.npy", "param.0.bias.npy", "param.2.weight.npy",
+                            "grad.0.weight.npy", "grad.0.bias.npy", "grad.2.weight.npy"])
+    assert rec["arrays"] == len(files)
+    for name in files:
+        a = np.load(str(tmp_path / "d" / name))
+        assert a.dtype == np.float32
+    np.testing.assert_array_equal(np.load(str(tmp_path / "d" / "logits.cls.npy")), logits["cls"].detach().float().numpy())
+    np.testing.assert_array_equal(np.load(str(tmp_path / "d" / "grad.2.weight.npy")), model[2].weight.grad.float().numpy())
+    assert rec["bytes"] == sum(np.load(str(tmp_path / "d" / n)).nbytes for n in files)
