@@ -305,6 +305,44 @@ int mlsp_density_loss_bwd_f32(const float* pvec, const float* dens, const float*
                               const float* mask, int P, int nc, float density_weight, const float* fwd_out,
                               const float* grad_kl, const float* grad_mae, float* dpvec, float* ddens, mlsp_stream_t stream);
 
+/* Index-matched losses on the deformed region (def_loss.hip).  N <= 4096 (MLSP_ERR_UNSUPPORTED otherwise); indices are int64 [B][N]
+ * as torch.min returns them; an index outside [0, N) is never dereferenced (its row contributes zero).
+ * mask [B][3][N] (row 0 is used); defpart = args.Density_normal_defpart: row weight w = m if set, 26 m + 1 otherwise.
+ *
+ * findindexs / findneareat_index (MLSP/mlsp.py:184-220): pred [B][N][3], gold [B][3][N];
+ * index1[b][i] = argmin_j |pred_bi - gold_bj|^2 + pen_bj, index2[b][j] = argmin_i |gold_bj - pred_bi|^2 + pen_bi, pen = 100 where
+ * mask == 0 and 0 where it is 1; distance as torch.norm(...)**2 in fp32; ties go to the lowest index. */
+int mlsp_def_nearest_index_f32(const float* pred, const float* gold, const float* mask, int B, int N, int64_t* index1, int64_t* index2,
+                               mlsp_stream_t stream);
+
+/* calc_def_normal_loss (MLSP/mlsp.py:289-329): pred, labels [B][N][3];
+ * out[0] = -weight/B sum_b (sum_i w_bi |n(pred_bi).n(lab_b,idx1)| + sum_j w_bj |n(pred_b,idx2).n(lab_bj)|) / sum_i w_bi,
+ * out[1 + b] = sum_i w_bi (out has 1 + B floats, kept for the backward).  ws: 16 B bytes.  The backward writes dpred [B][N][3]
+ * (no gradient to the labels); its scatter through index2 runs in a fixed order (deterministic). */
+int mlsp_def_normal_loss_fwd_f32(const float* pred, const float* labels, const float* mask, const int64_t* index1, const int64_t* index2,
+                                 int B, int N, int defpart, float weight, float* out, void* ws, size_t ws_bytes, mlsp_stream_t stream);
+int mlsp_def_normal_loss_bwd_f32(const float* pred, const float* labels, const float* mask, const int64_t* index1, const int64_t* index2,
+                                 int B, int N, int defpart, float weight, const float* fwd_out, const float* grad_loss, float* dpred,
+                                 mlsp_stream_t stream);
+
+/* deform_densityloss (MLSP/mlsp.py:370-427): pvec [B*N][nc] and dens [B*N] (logits['density'], logits['density_mse']), label_vec
+ * [B*N][nc], label_val [B*N].  out = {kl + kl1, mae + mae1, sum w}: the two densityloss (:430-454) evaluations, labels gathered
+ * through index1 against the predictions, then predictions gathered through index2 as the target of the labels.  ws: 6 KiB.
+ * The backward writes dpvec [B*N][nc] and ddens [B*N] (grad_kl / grad_mae nullable = 0), scattered deterministically. */
+int mlsp_def_density_loss_fwd_f32(const float* pvec, const float* dens, const float* label_vec, const float* label_val, const float* mask,
+                                  const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart, float density_weight,
+                                  float* out, void* ws, size_t ws_bytes, mlsp_stream_t stream);
+int mlsp_def_density_loss_bwd_f32(const float* pvec, const float* dens, const float* label_vec, const float* label_val, const float* mask,
+                                  const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart, float density_weight,
+                                  const float* fwd_out, const float* grad_kl, const float* grad_mae, float* dpvec, float* ddens,
+                                  mlsp_stream_t stream);
+
+/* the row gathers of calc_def_density_loss (MLSP/mlsp.py:346-348, :359-361): out[b][j][:] = x[b][index[b][j]][:], rows of W 32-bit
+ * words (bits copied, so int64 class labels gather as W = 2); the backward dx[b][i][:] = sum over j with index[b][j] == i of
+ * dout[b][j][:] (C floats per row) in ascending j -- deterministic. */
+int mlsp_gather_rows_u32(const void* x, const int64_t* index, int B, int N, int W, void* out, mlsp_stream_t stream);
+int mlsp_gather_rows_bwd_f32(const float* dout, const int64_t* index, int B, int N, int C, float* dx, mlsp_stream_t stream);
+
 /* plain fp32 GEMM on the matrix cores (exposed for tests and the 3x3 input transform):
  * C[M][N] = opA(A) opB(B) + bias;  ta/tb as in gemm.hip */
 int mlsp_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,

@@ -67,6 +67,13 @@ SIGNATURES = {
     "mlsp_density_tail_bwd_f32": [_P, _P, _P, _P, _I, _I, _P, _P],
     "mlsp_density_loss_fwd_f32": [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _SZ, _P],
     "mlsp_density_loss_bwd_f32": [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P],
+    "mlsp_def_nearest_index_f32": [_P, _P, _P, _I, _I, _P, _P, _P],
+    "mlsp_def_normal_loss_fwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _SZ, _P],
+    "mlsp_def_normal_loss_bwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P],
+    "mlsp_def_density_loss_fwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _SZ, _P],
+    "mlsp_def_density_loss_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
+    "mlsp_gather_rows_u32": [_P, _P, _I, _I, _I, _P, _P],
+    "mlsp_gather_rows_bwd_f32": [_P, _P, _I, _I, _I, _P, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],

@@ -174,6 +174,21 @@ int launch_density_loss_fwd(hipStream_t st, const float* pvec, const float* dens
 int launch_density_loss_bwd(hipStream_t st, const float* pvec, const float* dens, const float* tvec, const float* target,
                             const float* m, int P, int nc, float dweight, const float* fwd_out, const float* gkl,
                             const float* gmae, float* dp, float* dd);
+int launch_def_nearest(hipStream_t st, const float* pred, const float* gold, const float* mask, int B, int N, int64_t* index1,
+                       int64_t* index2);
+int launch_def_normal_fwd(hipStream_t st, const float* pred, const float* lab, const float* mask, const int64_t* index1,
+                          const int64_t* index2, int B, int N, int defpart, float weight, double* part, float* out);
+int launch_def_normal_bwd(hipStream_t st, const float* pred, const float* lab, const float* mask, const int64_t* index1,
+                          const int64_t* index2, int B, int N, int defpart, float weight, const float* fwd_out, const float* gout,
+                          float* dpred);
+int launch_def_density_fwd(hipStream_t st, const float* pvec, const float* dens, const float* lvec, const float* lval,
+                           const float* mask, const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart,
+                           float dweight, double* part, float* out);
+int launch_def_density_bwd(hipStream_t st, const float* pvec, const float* dens, const float* lvec, const float* lval,
+                           const float* mask, const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart,
+                           float dweight, const float* fwd_out, const float* gkl, const float* gmae, float* dp, float* dd);
+int launch_def_gather(hipStream_t st, const uint32_t* x, const int64_t* index, int B, int N, int W, uint32_t* out);
+int launch_def_gather_bwd(hipStream_t st, const float* dout, const int64_t* index, int B, int N, int C, float* dx);
 int launch_bn_bwd_finalize(hipStream_t st, const double* part, int nparts, double count, int C, float* dgamma, float* dbeta,
                            float* mean_dz, float* mean_dzy);
 
@@ -1177,6 +1192,56 @@ int mlsp_density_loss_bwd_f32(const float* pvec, const float* dens, const float*
     if (!pvec || !dens || !target_vec || !target || !fwd_out || !dpvec || !ddens || P <= 0 || nc <= 0) return MLSP_ERR_ARG;
     return launch_density_loss_bwd(st, pvec, dens, target_vec, target, mask, P, nc, density_weight, fwd_out, grad_kl, grad_mae,
                                    dpvec, ddens);
+}
+
+int mlsp_def_nearest_index_f32(const float* pred, const float* gold, const float* mask, int B, int N, int64_t* index1, int64_t* index2,
+                               mlsp_stream_t st) {
+    if (!pred || !gold || !mask || !index1 || !index2 || B <= 0 || N <= 0) return MLSP_ERR_ARG;
+    return launch_def_nearest(st, pred, gold, mask, B, N, index1, index2);
+}
+int mlsp_def_normal_loss_fwd_f32(const float* pred, const float* labels, const float* mask, const int64_t* index1, const int64_t* index2,
+                                 int B, int N, int defpart, float weight, float* out, void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    if (!pred || !labels || !mask || !index1 || !index2 || !out || B <= 0 || N <= 0) return MLSP_ERR_ARG;
+    Workspace w(ws, ws_bytes);
+    double* part = w.take<double>((size_t)B * 2);
+    if (!w.ok()) return MLSP_ERR_WORKSPACE;
+    return launch_def_normal_fwd(st, pred, labels, mask, index1, index2, B, N, defpart, weight, part, out);
+}
+int mlsp_def_normal_loss_bwd_f32(const float* pred, const float* labels, const float* mask, const int64_t* index1, const int64_t* index2,
+                                 int B, int N, int defpart, float weight, const float* fwd_out, const float* grad_loss, float* dpred,
+                                 mlsp_stream_t st) {
+    if (!pred || !labels || !mask || !index1 || !index2 || !fwd_out || !grad_loss || !dpred || B <= 0 || N <= 0) return MLSP_ERR_ARG;
+    return launch_def_normal_bwd(st, pred, labels, mask, index1, index2, B, N, defpart, weight, fwd_out, grad_loss, dpred);
+}
+int mlsp_def_density_loss_fwd_f32(const float* pvec, const float* dens, const float* label_vec, const float* label_val, const float* mask,
+                                  const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart, float density_weight,
+                                  float* out, void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    if (!pvec || !dens || !label_vec || !label_val || !mask || !index1 || !index2 || !out || B <= 0 || N <= 0 || nc <= 0 ||
+        (long long)B * N > INT32_MAX)
+        return MLSP_ERR_ARG;
+    Workspace w(ws, ws_bytes);
+    double* part = w.take<double>(256 * 3);
+    if (!w.ok()) return MLSP_ERR_WORKSPACE;
+    return launch_def_density_fwd(st, pvec, dens, label_vec, label_val, mask, index1, index2, B, N, nc, defpart, density_weight, part,
+                                  out);
+}
+int mlsp_def_density_loss_bwd_f32(const float* pvec, const float* dens, const float* label_vec, const float* label_val, const float* mask,
+                                  const int64_t* index1, const int64_t* index2, int B, int N, int nc, int defpart, float density_weight,
+                                  const float* fwd_out, const float* grad_kl, const float* grad_mae, float* dpvec, float* ddens,
+                                  mlsp_stream_t st) {
+    if (!pvec || !dens || !label_vec || !label_val || !mask || !index1 || !index2 || !fwd_out || !dpvec || !ddens || B <= 0 || N <= 0 ||
+        nc <= 0)
+        return MLSP_ERR_ARG;
+    return launch_def_density_bwd(st, pvec, dens, label_vec, label_val, mask, index1, index2, B, N, nc, defpart, density_weight, fwd_out,
+                                  grad_kl, grad_mae, dpvec, ddens);
+}
+int mlsp_gather_rows_u32(const void* x, const int64_t* index, int B, int N, int W, void* out, mlsp_stream_t st) {
+    if (!x || !index || !out || B <= 0 || N <= 0 || W <= 0) return MLSP_ERR_ARG;
+    return launch_def_gather(st, (const uint32_t*)x, index, B, N, W, (uint32_t*)out);
+}
+int mlsp_gather_rows_bwd_f32(const float* dout, const int64_t* index, int B, int N, int C, float* dx, mlsp_stream_t st) {
+    if (!dout || !index || !dx || B <= 0 || N <= 0 || C <= 0 || (long long)N * C > INT32_MAX) return MLSP_ERR_ARG;
+    return launch_def_gather_bwd(st, dout, index, B, N, C, dx);
 }
 
 }  // extern "C"

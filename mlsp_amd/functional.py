@@ -1732,6 +1732,158 @@ def density_loss(pvec, dens, tvec, target, mask=None, dweight=1.0):
     return _DensityLoss.apply(pvec, dens, tvec, target, mask, float(dweight))
 
 
+def _index_pair(index1, index2, B, N):
+    i1, i2 = index1.contiguous().long(), index2.contiguous().long()
+    assert i1.shape == (B, N) and i2.shape == (B, N), (i1.shape, i2.shape, B, N)
+    return i1, i2
+
+
+def def_nearest_index(pred, gold, mask):
+    """findindexs (MLSP/mlsp.py:184-220): pred [B,N,3], gold / mask [B,3,N] -> (index1, index2) int64 [B,N]: the nearest gold point
+    of every predicted point and the reverse, +100 on columns whose mask[b,0] is 0; ties go to the lowest index (torch.min)."""
+    lib = _lib.load()
+    pred = pred.detach().contiguous().float()
+    gold, mask = gold.detach().contiguous().float(), mask.detach().contiguous().float()
+    _lib.require_gpu(pred, gold, mask)
+    B, N, C = pred.shape
+    assert C == 3 and gold.shape == (B, 3, N) and mask.shape == (B, 3, N), (pred.shape, gold.shape, mask.shape)
+    index1 = torch.empty((B, N), dtype=torch.int64, device=pred.device)
+    index2 = torch.empty_like(index1)
+    _lib.check(lib.mlsp_def_nearest_index_f32(pred.data_ptr(), gold.data_ptr(), mask.data_ptr(), B, N, index1.data_ptr(),
+                                              index2.data_ptr(), _lib.stream()), "mlsp_def_nearest_index_f32")
+    return index1, index2
+
+
+class _DefNormalLoss(Function):
+    @staticmethod
+    def forward(ctx, pred, labels, mask, index1, index2, defpart, weight):
+        lib = _lib.load()
+        pred = pred.contiguous().float()
+        labels, mask = labels.contiguous().float(), mask.contiguous().float()
+        _lib.require_gpu(pred, labels, mask, index1, index2)
+        B, N, C = pred.shape
+        assert C == 3 and labels.shape == (B, N, 3) and mask.shape == (B, 3, N), (pred.shape, labels.shape, mask.shape)
+        index1, index2 = _index_pair(index1, index2, B, N)
+        out = torch.empty((1 + B,), dtype=torch.float32, device=pred.device)
+        ws, wsn = _lib.workspace(pred.device, 1, 1, 1)
+        _lib.check(lib.mlsp_def_normal_loss_fwd_f32(pred.data_ptr(), labels.data_ptr(), mask.data_ptr(), index1.data_ptr(),
+                                                    index2.data_ptr(), B, N, int(defpart), weight, out.data_ptr(), ws, wsn,
+                                                    _lib.stream()), "mlsp_def_normal_loss_fwd_f32")
+        ctx.save_for_backward(pred, labels, mask, index1, index2, out)
+        ctx.defpart, ctx.weight = int(defpart), weight
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        pred, labels, mask, index1, index2, out = ctx.saved_tensors
+        B, N, _ = pred.shape
+        g = g.contiguous().float()
+        dpred = torch.empty_like(pred)
+        _lib.check(lib.mlsp_def_normal_loss_bwd_f32(pred.data_ptr(), labels.data_ptr(), mask.data_ptr(), index1.data_ptr(),
+                                                    index2.data_ptr(), B, N, ctx.defpart, ctx.weight, out.data_ptr(), g.data_ptr(),
+                                                    dpred.data_ptr(), _lib.stream()), "mlsp_def_normal_loss_bwd_f32")
+        return dpred, None, None, None, None, None, None
+
+
+def def_normal_loss(pred, labels, mask, index1, index2, defpart, weight):
+    """calc_def_normal_loss (MLSP/mlsp.py:289-329): pred, labels [B,N,3], mask [B,3,N], indices [B,N] -> 0-dim loss; gradient to pred
+    only, scattered through index2 in a fixed order."""
+    return _DefNormalLoss.apply(pred, labels, mask, index1, index2, bool(defpart), float(weight))
+
+
+class _DefDensityLoss(Function):
+    @staticmethod
+    def forward(ctx, pvec, dens, label_vec, label_val, mask, index1, index2, defpart, dweight):
+        lib = _lib.load()
+        pvec, dens = pvec.contiguous().float(), dens.contiguous().float()
+        label_vec, label_val = label_vec.contiguous().float(), label_val.contiguous().float()
+        mask = mask.contiguous().float()
+        _lib.require_gpu(pvec, dens, label_vec, label_val, mask, index1, index2)
+        B, _, N = mask.shape
+        P, nc = pvec.shape
+        assert P == B * N and dens.numel() == P and label_vec.shape == (P, nc) and label_val.numel() == P, \
+            (pvec.shape, dens.shape, label_vec.shape, label_val.shape, mask.shape)
+        index1, index2 = _index_pair(index1, index2, B, N)
+        out = torch.empty((3,), dtype=torch.float32, device=pvec.device)
+        ws, wsn = _lib.workspace(pvec.device, 1, 1, 1)
+        _lib.check(lib.mlsp_def_density_loss_fwd_f32(pvec.data_ptr(), dens.data_ptr(), label_vec.data_ptr(), label_val.data_ptr(),
+                                                     mask.data_ptr(), index1.data_ptr(), index2.data_ptr(), B, N, nc, int(defpart),
+                                                     dweight, out.data_ptr(), ws, wsn, _lib.stream()), "mlsp_def_density_loss_fwd_f32")
+        ctx.save_for_backward(pvec, dens, label_vec, label_val, mask, index1, index2, out)
+        ctx.defpart, ctx.dweight, ctx.dens_shape = int(defpart), dweight, dens.shape
+        return out[0], out[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gkl, gmae):
+        lib = _lib.load()
+        pvec, dens, label_vec, label_val, mask, index1, index2, out = ctx.saved_tensors
+        B, N = index1.shape
+        nc = pvec.shape[1]
+        gkl = gkl.contiguous().float() if gkl is not None else None
+        gmae = gmae.contiguous().float() if gmae is not None else None
+        dp, dd = torch.empty_like(pvec), torch.empty_like(dens)
+        _lib.check(lib.mlsp_def_density_loss_bwd_f32(pvec.data_ptr(), dens.data_ptr(), label_vec.data_ptr(), label_val.data_ptr(),
+                                                     mask.data_ptr(), index1.data_ptr(), index2.data_ptr(), B, N, nc, ctx.defpart,
+                                                     ctx.dweight, out.data_ptr(), _lib.ptr(gkl), _lib.ptr(gmae), dp.data_ptr(),
+                                                     dd.data_ptr(), _lib.stream()), "mlsp_def_density_loss_bwd_f32")
+        return dp, dd.view(ctx.dens_shape), None, None, None, None, None, None, None
+
+
+def def_density_loss(pvec, dens, label_vec, label_val, mask, index1, index2, defpart, dweight):
+    """deform_densityloss (MLSP/mlsp.py:370-427): pvec [B*N,nc], dens [B*N], label_vec [B*N,nc], label_val [B,N] or [B*N],
+    mask [B,3,N], indices [B,N] -> (kl + kl1, mae + mae1); gradients to pvec and dens."""
+    return _DefDensityLoss.apply(pvec, dens, label_vec, label_val, mask, index1, index2, bool(defpart), float(dweight))
+
+
+def gather_rows_bits(x, index):
+    """out[b, j] = x[b, index[b, j]] for x [B,N,...] of any dtype whose rows are whole 32-bit words (bits copied); no autograd."""
+    lib = _lib.load()
+    x = x.contiguous()
+    _lib.require_gpu(x, index)
+    B, N = x.shape[0], x.shape[1]
+    index = index.contiguous().long()
+    assert index.shape == (B, N), (index.shape, x.shape)
+    row_bytes = x[0, 0].numel() * x.element_size()
+    assert row_bytes % 4 == 0 and row_bytes > 0, "rows must be whole 32-bit words"
+    out = torch.empty_like(x)
+    _lib.check(lib.mlsp_gather_rows_u32(x.data_ptr(), index.data_ptr(), B, N, row_bytes // 4, out.data_ptr(), _lib.stream()),
+               "mlsp_gather_rows_u32")
+    return out
+
+
+class _GatherRows(Function):
+    @staticmethod
+    def forward(ctx, x, index):
+        out = gather_rows_bits(x, index)
+        ctx.save_for_backward(index.contiguous().long())
+        ctx.shape = x.shape
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        index, = ctx.saved_tensors
+        B, N = index.shape
+        g = g.contiguous().float()
+        C = g[0, 0].numel()
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        _lib.check(lib.mlsp_gather_rows_bwd_f32(g.data_ptr(), index.data_ptr(), B, N, C, dx.data_ptr(), _lib.stream()),
+                   "mlsp_gather_rows_bwd_f32")
+        return dx, None
+
+
+def gather_rows(x, index):
+    """Differentiable row gather out[b, j] = x[b, index[b, j]] (x float32 [B,N,...], index [B,N]); the backward sums each row's
+    gradients over the j that picked it, in ascending j (deterministic, no atomics)."""
+    if x.dtype != torch.float32:
+        raise TypeError("gather_rows differentiates float32 rows; use gather_rows_bits for other dtypes")
+    return _GatherRows.apply(x, index)
+
+
 def gemm(A, B, ta=False, tb=False, bias=None):
     """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests."""
     lib = _lib.load()

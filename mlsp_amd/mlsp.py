@@ -147,3 +147,63 @@ def calc_masked_normal_loss(args, prediction, labels, mask_cord):
 def densityloss(args, logits, target, target_vec, mask=None):
     """MLSP/mlsp.py:430-454 -> (kl, mae)."""
     return Fh.density_loss(logits['density'], logits['density_mse'], target_vec, target, mask, args.Density_weight)
+
+
+# ---- index-matched losses on the deformed region (MLSP/mlsp.py:184-220, 289-427) ----
+# The indices come from one kernel that searches every row of both clouds (def_loss.hip); the losses gather through them on
+# device and scatter back in a fixed order.  `device` is accepted for the reference's signature and unused: inputs already
+# live on the GPU.
+
+def findindexs(pred, gold, mask):
+    """MLSP/mlsp.py:184-193.  pred [B,N,3]; gold, mask [B,3,N] -> [index1, index2], int64 [B,N]: index1[b,i] the nearest gold
+    point of pred_i, index2[b,j] the nearest predicted point of gold_j; columns whose mask[b,0] is 0 carry +100.  Ties go to
+    the lowest index, as torch.min."""
+    index1, index2 = Fh.def_nearest_index(pred, gold, mask)
+    return [index1, index2]
+
+
+def findneareat_index(p1, p2, mask):
+    """MLSP/mlsp.py:196-220 (the reference's spelling).  p1, p2, mask [B,N,3] -> int64 [B,N]: for every point of p1 the arg-min
+    over the points j of p2 of |p1_i - p2_j|^2 + 100 [mask[b,j,0] == 0]."""
+    assert p1.size(0) == p2.size(0) and p1.size(2) == p2.size(2)
+    index1, _ = Fh.def_nearest_index(p1, p2.permute(0, 2, 1), mask.permute(0, 2, 1))
+    return index1
+
+
+def calc_def_normal_loss(args, logits, normal_labels, mask, indexes, device, all=False):
+    """MLSP/mlsp.py:289-329.  logits['Normal'], normal_labels [B,N,3]; mask [B,3,N]; indexes = findindexs(...).  Weights
+    mask[:,0] if args.Density_normal_defpart else 26 mask[:,0] + 1; `all` is unused, as in the reference."""
+    index1, index2 = indexes
+    return Fh.def_normal_loss(logits['Normal'], normal_labels, mask, index1, index2, args.Density_normal_defpart,
+                              args.normal_pred_weight)
+
+
+def calc_def_density_loss(args, logits, density_labels, mask, indexes, device, criterion, all=False):
+    """MLSP/mlsp.py:331-368.  `criterion` is any reduction='none' torch loss (e.g. nn.NLLLoss(reduction='none')) applied to
+    logits['density'] [B*N,C] against density_labels [B*N] gathered through index1, then to logits['density'] gathered through
+    index2 against density_labels.  The gathers are kernels (the backward scatter is deterministic); the criterion is torch's."""
+    mask_cord = mask.permute(0, 2, 1)[:, :, 0].reshape(-1)
+    index1, index2 = indexes
+    batch_size, num_points = index1.size(0), index1.size(1)
+    density_pred = logits["density"]
+    density_gt = Fh.gather_rows_bits(density_labels.reshape(batch_size, num_points, 1), index1).reshape(-1)
+    tmp = criterion(density_pred, density_gt)
+    if all:
+        loss = args.Density_weight * torch.sum(tmp) / (batch_size * num_points)
+    else:
+        loss = args.Density_weight * torch.sum(tmp * mask_cord) / (batch_size * torch.sum(mask_cord))
+    pred_gt = Fh.gather_rows(density_pred.reshape(batch_size, num_points, args.density_num_class), index2)
+    tmp = criterion(pred_gt.reshape(-1, args.density_num_class), density_labels)
+    if all:
+        loss = loss + args.Density_weight * torch.sum(tmp) / (batch_size * num_points)
+    else:
+        loss = loss + args.Density_weight * torch.sum(tmp * mask_cord) / (batch_size * torch.sum(mask_cord))
+    return loss
+
+
+def deform_densityloss(args, logits, density_labels, density_mse_label, mask, indexes, device):
+    """MLSP/mlsp.py:370-427 -> (kl + kl1, mae + mae1).  density_labels [B*N,C], density_mse_label [B,N]; logits['density']
+    [B*N,C] and logits['density_mse'] [B*N] receive the gradients."""
+    index1, index2 = indexes
+    return Fh.def_density_loss(logits['density'], logits['density_mse'], density_labels, density_mse_label, mask, index1, index2,
+                               args.Density_normal_defpart, args.Density_weight)
