@@ -16,8 +16,8 @@
  *     (ABI v8: the products of the GEMM family are the per-call `precision` argument below, not a library switch; ABI v13:
  *     mlsp_operand_bounds_next hands ONE following call an optional table through a thread-local slot that the call empties -- an
  *     out-of-band argument of that call, not state).  The only process-wide object is the measurement hook mlsp_profile_begin/_end (HIP events around launches while armed; bench.py only,
- *     never armed in a production step).  Environment variables read once per process, all A/B measurement switches:
- *     MLSP_TNET_BWD_OLD=1 (round-1 T-Net backward kernel), MLSP_GEMM_SPLIT_ALWAYS, MLSP_GEMM_OLD_EPILOGUE.
+ *     never armed in a production step).  The library reads one environment variable, MLSP_PROF_DUMP (a listing of
+ *     the profiled launches while the hook is armed); it changes no kernel choice.
  *   - `precision` (every entry point that reaches a matrix-core contraction takes it, just before its workspace):
  *       MLSP_PREC_F32    0  f32 MFMA, exact fp32 products (v_mfma_f32_32x32x2_f32);
  *       MLSP_PREC_BF16   1  operands ROUNDED to bf16, fp32 accumulation (BASELINE.json configs[4]; reduced precision);

@@ -759,9 +759,8 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
     // masked gradient + its sums in hand (pre_stats): when the dgrad and the weight gradient can form dY = (d' + y * nk2 + c0) * sc in their
     // A operand loads (gemm.hip gemm_split_kernel<.., DY>) the apply pass and the dY tensor are skipped; the per-cloud bias gradient comes
     // from the row-panel sums of d' and the clouds' column sums of y (bn.hip launch_bn_dy_gbias)
-    static const bool dy_off = getenv("MLSP_BWD_DY_OFF") != nullptr;        // read-once A/B switch (tools/ab)
     GemmDy dy_s = {Y, coef, Cout, 1}; const GemmDy* dy = nullptr;          // (the finalizers below fill the fourth coefficient row)
-    if (has_bn && M > 32 && pre_stats && training && !dy_off && (!in || xf) && M % pre_parts == 0 &&
+    if (has_bn && M > 32 && pre_stats && training && (!in || xf) && M % pre_parts == 0 &&
         (!dX || gemm_dy_supported(false, false, M, Cin, Cout, dZ, Cout, W, ldw)) && gemm_dy_supported(true, false, Cout, Cin, M, dZ, Cout, X, ldx) &&
         (!dgbias || (rows_per_group >= 256 && rows_per_group % (M / pre_parts) == 0 && Cout % 4 == 0 && 256 % (Cout / 4) == 0 && Cout <= 1024)))
         dy = &dy_s;
@@ -796,8 +795,7 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
         bs_s.amax = (float*)(in_stats + (size_t)(M / 128) * 2 * in->ld) + in->col;      // the maxima plane behind the [M / 128][2][ld] sums
         bs = &bs_s;
     }
-    static const bool no_pair = getenv("MLSP_SKINNY_NO_PAIR") != nullptr;          // read-once A/B switch
-    if (M <= 32 && dX && !bs && !dy && !xf && !no_pair) {
+    if (M <= 32 && dX && !bs && !dy && !xf) {
         // per-cloud layer (rows = batch): input gradient (added into dX under dx_accumulate: the x5 halves of the PointSegDA heads share one
         // gradient buffer) and weight gradient in one launch (skinny.hip)
         CHECK(launch_skinny_bwd_pair(st, g, Cout, W, ldw, X, ldx, dX, lddx, dW, M, Cin, Cout, dx_accumulate));

@@ -210,9 +210,7 @@ __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __res
 // (u16) are staged in LDS once; the k row gathers of every point then run at LDS rate instead of one L2 round trip per
 // neighbour row.  A thread owns (point, channel quad) and walks its k neighbours in slot order, so the first-occurrence
 // rule needs no cross-lane merge.  Partial BN statistics: one fp64 row per (cloud, chunk), each slice writes its columns.
-#ifndef ELDS_CS
 #define ELDS_CS 8           // channels of a slice: 32 KB of LDS at N = 1024 (four workgroups per CU; 16 measured 2 % slower)
-#endif
 template <int KMAX, bool EXACT>     // EXACT: k == KMAX, the neighbour loop is straight-line (all index / row reads of a point in flight)
 __global__ __launch_bounds__(256) void edge_reduce_lds_kernel(const float* __restrict__ uv, const int* __restrict__ idx,
                                                               const float* __restrict__ gamma, int B, int N, int k, int Cout, int psplit,
@@ -756,23 +754,21 @@ int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const fl
                        float* msel, uint8_t* argsel, float* s1, double* part, int* nparts_used) {
     const bool al = (((uintptr_t)uv | (uintptr_t)msel | (uintptr_t)s1 | (uintptr_t)gamma) & 15) == 0 && (((uintptr_t)argsel) & 3) == 0;
     if (nparts_used) *nparts_used = edge_reduce_parts(P);
-#ifndef EDGE_NO_LDS
-    static const bool no_wide = getenv("MLSP_EDGE_NO_WIDE") != nullptr;       // read-once A/B switch (tools/ab)
-    if (!no_wide && al && P % N == 0 && N % 4 == 0 && (k == 20 || k == 40 || k <= 32) && Cout % 32 == 0 && N <= 2048) {
-        // wide slices: CS = 32 channels, one 1024-thread workgroup per CU while the cloud's slice fits (N <= 1024: 128 KB), else 16
-        static const int force_cs = getenv("MLSP_EDGE_WIDE_CS") ? atoi(getenv("MLSP_EDGE_WIDE_CS")) : 0;     // read-once A/B switch: 16 -> 16-channel slices, 512 threads, two workgroups per CU
-        // measured (B = 32, N = 1024, k = 20, five launches of a step): 32 channels x 1024 threads 143 us, 16 x 512 (two workgroups per CU: one
-        // stages while the other gathers) 129 us, 8 x 256 141 us; the round-4 kernel 182 us
-        const int B = P / N, CS = force_cs == 8 ? 8 : (force_cs == 32 && N <= 1024) ? 32 : 16, nsl = Cout / CS;
-        const int NT = CS == 8 ? 256 : (CS == 16 && N <= 1024) ? 512 : 1024;
-        const int want = NT == 256 ? 1024 : NT == 512 ? 512 : 256;
+    if (al && P % N == 0 && N % 4 == 0 && (k == 20 || k == 40 || k <= 32) && Cout % 32 == 0 && N <= 2048) {
+        // wide slices: CS = 16 channels, 512 threads (two workgroups per CU: one stages while the other gathers) while N <= 1024, else 1024
+        // threads.  Measured (B = 32, N = 1024, k = 20, five launches of a step): 32 channels x 1024 threads 143 us, 16 x 512 129 us,
+        // 8 x 256 141 us; the round-4 kernel 182 us
+        constexpr int CS = 16;
+        const int B = P / N, nsl = Cout / CS;
+        const int NT = N <= 1024 ? 512 : 1024;
+        const int want = NT == 512 ? 512 : 256;
         int psplit = 1;                                        // cut the point range only to give every CU its workgroup(s)
         while (psplit < 8 && B * nsl * psplit < want && N % (psplit * 2) == 0) psplit *= 2;
         const size_t lds = (size_t)N * CS * sizeof(float);
         const size_t red = (size_t)2 * (NT / (CS / 4)) * CS * sizeof(double);
         if ((lds > red ? lds : red) <= 150 * 1024 && B * psplit <= edge_reduce_parts(P)) {
             const size_t ldsz = lds > red ? lds : red;
-#define EW_GO(KM, EX) do { auto kern = CS == 32 ? edge_reduce_wide_kernel<KM, EX, 32, 1024> : CS == 8 ? edge_reduce_wide_kernel<KM, EX, 8, 256> : NT == 512 ? edge_reduce_wide_kernel<KM, EX, 16, 512> : edge_reduce_wide_kernel<KM, EX, 16, 1024>; \
+#define EW_GO(KM, EX) do { auto kern = NT == 512 ? edge_reduce_wide_kernel<KM, EX, CS, 512> : edge_reduce_wide_kernel<KM, EX, CS, 1024>; \
                 if (ldsz > 64 * 1024) { hipError_t e_ = mlsp_lds_limit((const void*)kern, ldsz); if (e_ != hipSuccess) return (int)e_; } \
                 hipLaunchKernelGGL(kern, dim3(B * nsl * psplit), dim3(NT), ldsz, st, uv, idx, gamma, B, N, k, Cout, psplit, msel, argsel, s1, part); } while (0)
             if (k == 20) EW_GO(20, true); else if (k <= 20) EW_GO(20, false); else if (k <= 32) EW_GO(32, false); else EW_GO(40, true);
@@ -798,7 +794,6 @@ int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const fl
             return mlsp_launch_status();
         }
     }
-#endif
     if (al && (Cout == 64 || Cout == 128 || Cout == 256)) {
         dim3 g(edge_reduce_parts(P)), b(256);
         if (Cout == 64) hipLaunchKernelGGL((edge_reduce_vec_kernel<16>), g, b, 0, st, uv, idx, gamma, P, N, k, msel, argsel, s1, part);

@@ -304,12 +304,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[2
                     float v = acc[i][j][r] + bv;
                     if (epi && p.gbias) v += p.gbias[(size_t)(row / p.rows_per_group) * p.N + col];
                     if (epi && p.accumulate) v += CBF ? (float)Cb[(size_t)row * p.ldc + col] : Cout[(size_t)row * p.ldc + col];
-#ifdef GP_NOSTORE
-                    if (p.C && v == 12345.678f) Cout[(size_t)row * p.ldc + col] = v;
-#else
                     if (CBF) { if (p.C) Cb[(size_t)row * p.ldc + col] = (__bf16)v; }
                     else if (p.C) Cout[(size_t)row * p.ldc + col] = v;
-#endif
                     cs[j] += v; cq[j] = fmaf(v, v, cq[j]);
                     acc[i][j][r] = v;
                 }
@@ -401,11 +397,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs p) {
     constexpr int BMT = 64 * WM, NPA = 2 * WM;
     // A tile is k-major in LDS either way; its GLOBAL source is k-major iff TA.  B's source is
     // k-major iff !TB.
-#ifdef GP_LDSPAD
-    __shared__ __attribute__((aligned(16))) float smem[BM * SROW * 2 + GP_LDSPAD];
-#else
     __shared__ __attribute__((aligned(16))) float smem[BM * SROW * 2];
-#endif
     float* As = smem;
     float* Bs = smem + BM * SROW;
 
@@ -446,25 +438,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs p) {
         Bp += (size_t)(tm / p.gtiles) * p.b_gs;
     }
 
-#ifdef GP_TIMELINE
-    const long long tl0 = wall_clock64();
-    long long tl1 = 0;
-#endif
-#ifdef GP_DEPHASE
-    {   // co-resident workgroups get distinct issue priorities: they drift out of phase, one's C stores run under another's MFMAs
-#if GP_DEPHASE == 1
-        const unsigned slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) & 3u;        // HW_ID.wave_id[3:0] & 3
-#elif GP_DEPHASE == 2
-        const unsigned slot = ((unsigned)bid >> 3) & 3u;
-#else
-        const unsigned slot = ((unsigned)bid >> 8) & 3u;
-#endif
-        if (slot == 0) __builtin_amdgcn_s_setprio(0);
-        else if (slot == 1) __builtin_amdgcn_s_setprio(1);
-        else if (slot == 2) __builtin_amdgcn_s_setprio(2);
-        else __builtin_amdgcn_s_setprio(3);
-    }
-#endif
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -515,22 +488,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs p) {
     };
     if (XF) xf_tile(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
-#ifdef GP_NOR2S
-        if (k0 == kbeg)
-#endif
-        {
         r2s<TA, NPA>(ra, As, tid);
         r2s<!TB, 4>(rb, Bs, tid);
-        }
         __syncthreads();
-#ifdef GP_TIMELINE
-        if (k0 == kbeg) tl1 = wall_clock64();
-#endif
-#ifdef GP_NOGLOBAL
-        if (false) {
-#else
         if (k0 + BK < kend) {
-#endif
             if (FAST) {
                 soa += TA ? BK * lda4 : BK * 4;
                 sob += !TB ? BK * ldb4 : BK * 4;
@@ -548,14 +509,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs p) {
         // (h = lane >> 5), so a row-major image gives each lane its two values with ONE 8-byte read; a k-major image is
         // read per value.  Both operands use the same k assignment, so every (TA, TB) combination is consistent.
         const int arow = wm * (32 * WM) + l31, bcol = wn * 64 + l31;
-#ifdef GP_PRIO
-        __builtin_amdgcn_s_setprio(GP_PRIO);
-#endif
 #pragma unroll
         for (int m = 0; m < BK / 4; ++m) {
-#ifdef GP_IGLP
-            __builtin_amdgcn_iglp_opt(GP_IGLP);
-#endif
             if (XF && m == BK / 8 && k0 + BK < kend) xf_tile(k0 + BK);
             const int kq = 4 * m + 2 * h;
             float a0s0, a0s1, a1s0, a1s1, b0s0, b0s1, b1s0, b1s1;
@@ -588,28 +543,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs p) {
                 acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1s1, b1s1, acc[1][1], 0, 0, 0);
             }
         }
-#ifdef GP_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#ifndef GP_NOBAR
         __syncthreads();
-#endif
     }
 
-#ifdef GP_TIMELINE
-    const long long tl2 = wall_clock64();
-#endif
     gemm_epilogue<WM, FAST>(p, acc, smem, tm, m0, n0, split, tid, l31, h, wm, wn);
-#ifdef GP_TIMELINE
-    __syncthreads();
-    if (tid == 0) {                                    // 100 MHz ticks: start, first tile staged, loop end, epilogue end
-        const long long tl3 = wall_clock64();
-        float* dbg = p.C + (size_t)m0 * p.ldc + n0;
-        dbg[0] = (float)(tl0 & 0xffffff); dbg[1] = (float)(tl1 - tl0); dbg[2] = (float)(tl2 - tl1); dbg[3] = (float)(tl3 - tl2);
-        dbg[4] = (float)(__builtin_amdgcn_s_getreg((16 - 1) << 11 | 0 << 6 | 4));      // HW_ID[15:0]: wave, simd, pipe, cu, sh, se
-        dbg[5] = (float)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20));      // XCC_ID
-    }
-#endif
 }
 
 // ---- N = 64 variant: 128 x 64 x 32 tiles, the four waves stacked along M (32 rows x 64 columns each) -----------------------------
@@ -1517,12 +1454,6 @@ float* amax_offered_output(const float* out, long rows, int cols, int ld, int ne
     return nullptr;
 }
 static void amax_flush(hipStream_t st, AmaxBatch& batch) {
-    static const bool dump = getenv("MLSP_AMAX_DUMP") != nullptr;          // read-once diagnostic (tools/r6): what each measuring launch reads
-    if (dump && batch.n) {
-        fprintf(stderr, "amax launch:");
-        for (int i = 0; i < batch.n; ++i) fprintf(stderr, " [%ld x %d ld %d = %.1f MB]", batch.args.op[i].rows, batch.args.op[i].cols, batch.args.op[i].ld, batch.args.op[i].rows * 4e-6 * batch.args.op[i].cols);
-        fprintf(stderr, "\n");
-    }
     if (batch.n) hipLaunchKernelGGL(amax_partials_kernel, dim3(batch.n * AMAX_PARTS), dim3(512), 0, st, batch.args);
     batch.n = 0;
 }
@@ -1724,15 +1655,12 @@ int gemm_pick_split(int M, int N, int K) {
 // launch on the headline step, tools/cmp_dump.py, and per shape, tools/x6/lib_bench: the split kernel's longer prologue loses at K = 64 and,
 // at K = 128, on grids too small to hide it: few rows AND a single column tile)
 static bool gemm_split_pays(int M, int N, int ktiles) {
-    static const bool always = getenv("MLSP_GEMM_SPLIT_ALWAYS") != nullptr;        // read-once A/B switch (tools/x6/lib_bench)
-    return always || ktiles >= 8 || (ktiles >= 4 && (N >= 256 || M >= 16384));
+    return ktiles >= 8 || (ktiles >= 4 && (N >= 256 || M >= 16384));
 }
 static int gemm_pick_bm(int M, int N, int K) {
     long tiles128 = (long)((M + 127) / 128) * ((N + BN - 1) / BN);
     // the split kernel amortises its operand split over the tile: 128 rows unless the grid would not fill the 512 workgroup slots
     const long few = (tl_call_precision == 2 && gemm_split_pays(M, N, (K + BK - 1) / BK)) ? 512 : 1536;
-    static const bool force64 = getenv("MLSP_GEMM_BM64") != nullptr;            // read-once experiment switch (tools/x6/lib_bench): 64-row tiles wherever K is not split
-    if (force64 && gemm_pick_split(M, N, K) == 1 && M >= 256) return 64;
     return (gemm_pick_split(M, N, K) == 1 && tiles128 < few && M >= 256) ? 64 : 128;
 }
 int gemm_stat_parts(int M, int N, int K) {
@@ -2029,17 +1957,14 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     if (ns > 1) { p.C = slab; p.ldc = N; }
     p.xcd_map = p.ntm >= 16 && p.ntn > 1;
     dim3 grid(p.xcd_map ? ((p.ntm + 7) / 8) * 8 * p.ntn : p.ntm * p.ntn, ns);
-    static const bool no_xcd2 = getenv("MLSP_GEMM_NO_XCD2") != nullptr;       // read-once A/B switch (tools/ab)
-    bool xcd2 = false;                                                        // (decided below, once the kernel is known: split kernel only)
     const bool prof = g_prof.on && g_prof.used < PROF_MAX_PAIRS;
     // FAST: every tile interior (M, N, K-range multiples of the tile), 16-byte loads legal on both operands
     // (byte offsets inside an operand tile's K range are 32-bit buffer offsets)
     const long a_span = ta ? (long)p.ksplit * lda * 4 : 128L * lda * 4 + (long)p.ksplit * 4;
     const long b_span = !tb ? (long)p.ksplit * ldb * 4 : 128L * ldb * 4 + (long)p.ksplit * 4;
     const bool fast = p.a_vec && p.b_vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && a_span < (1L << 31) - 4096 && b_span < (1L << 31) - 4096;
-    static const bool old_epilogue = getenv("MLSP_GEMM_OLD_EPILOGUE") != nullptr;       // read-once A/B switch (tools/ab)
     // lean output pass: every row of a tile takes the same per-cloud bias row, byte offsets inside a wave's region fit 31 bits
-    p.fast_out = (fast && (!gbias || rows_per_group % bm == 0) && (long)p.ldc * 4 * 64 < (1L << 30) && !old_epilogue) ? 1 : 0;
+    p.fast_out = (fast && (!gbias || rows_per_group % bm == 0) && (long)p.ldc * 4 * 64 < (1L << 30)) ? 1 : 0;
     p.gmode = 0; p.gtiles = 1; p.a_gs = p.b_gs = 0; p.Bg[0] = p.Bg[1] = p.Bg[2] = p.Bg[3] = B;
     if (grp) {
         const int per = (grp->mode == 1 ? N : M) / grp->G;                  // columns (mode 1) / rows (mode 2) of one group
@@ -2053,17 +1978,15 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     const bool xf_split = xf && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && (xf->which != 1 || kts * BK <= SX_XF_KMAX);
     if (grp && xf && !xf_split) return MLSP_ERR_UNSUPPORTED;             // (the fp32 transform kernels take no groups: nothing launched)
     // split-K launches of gemm_split_kernel with few row panels (weight gradients): XCD-grouped (split, panel) order, see the kernel
-    xcd2 = !no_xcd2 && !p.xcd_map && ns > 1 && p.ntn > 1 && (p.ntm * ns) % 8 == 0 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) &&
+    const bool xcd2 = !p.xcd_map && ns > 1 && p.ntn > 1 && (p.ntm * ns) % 8 == 0 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) &&
            (!xf || xf_split);
-    static const bool no_xcd3 = getenv("MLSP_GEMM_NO_XCD3") != nullptr;       // read-once A/B switch (tools/ab)
-    const bool xcd3 = !no_xcd3 && !p.xcd_map && ns > 1 && ns % 8 == 0 && p.ntm > 1 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && (!xf || xf_split);
+    const bool xcd3 = !p.xcd_map && ns > 1 && ns % 8 == 0 && p.ntm > 1 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && (!xf || xf_split);
     if (xcd3) { p.xcd_map = 3; grid = dim3(p.ntm * p.ntn * ns, 1); }       // (all tiles of a split on one XCD: see the kernel)
     else if (xcd2) { p.xcd_map = 2; grid = dim3(p.ntm * p.ntn * ns, 1); }
     // (mode 1, N = 64: the bf16 kernel's tiles are 128 columns wide, so these launches used to fall to the bounds-checked f32 kernel at half-empty
-    // tiles -- 33 us where the 64-column f32 kernel takes 12; exact products are within what mode 1 promises.  Read-once A/B switch.)
-    static const bool no_n64_bf16 = getenv("MLSP_GEMM_NO_N64_BF16") != nullptr;
+    // tiles -- 33 us where the 64-column f32 kernel takes 12; exact products are within what mode 1 promises.)
     const bool n64 = !dy && !grp && !xf && N == 64 && p.a_vec && p.b_vec && M % 128 == 0 && K % BK == 0 && !(ta && tb) && !gbias && (!stat_part || (bm == 128 && ns == 1)) && !sel_gamma &&
-                     (!bias || (ns == 1 && (((uintptr_t)bias) & 3) == 0)) && (tl_call_precision != 1 || !no_n64_bf16) && (ns == 1 || p.ldc == N);
+                     (!bias || (ns == 1 && (((uintptr_t)bias) & 3) == 0)) && (ns == 1 || p.ldc == N);
     // two-piece f16 products (mode 3) on this launch?  The split kernel, and a bound for both operands: partial maxima of the operands as
     // they lie in memory (measured by ONE streaming launch here, or earlier in this API call), the analytic bound for a transformed one
     // (batch statistics at hand).  Anything missing: the three-piece bf16 products (same kernel family, same accuracy class).
@@ -2076,7 +1999,6 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         // 25 for its 67 MB input); the set-abstraction layers' K = 128 contractions over 262144 rows do not (tools/x6/lib_bench: 90 us with
         // the pass against 70 on six products; configs[3] 3.58 -> 3.46 ms) and stay on the six products unless their bounds are free.
         {
-            static const bool always = getenv("MLSP_AMAX_ALWAYS") != nullptr;          // read-once A/B switch
             double mbytes = 0.0;
             auto need = [&](const float* X, long rows, int cols, int ld) { if (!amax_at_hand(X, rows, cols, ld)) mbytes += (double)rows * cols * 4.0; };
             if (!(xf && xf->which == 1) && !(dy && dy->amax))
@@ -2085,7 +2007,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
             else if (grp && grp->mode == 1) { for (int g = 0; g < grp->G; ++g) need(grp->Bg[g], tb ? N / grp->G : K, tb ? K : N / grp->G, ldb); }
             else need(B, tb ? N : K, (tb ? K : N) + ((grp && grp->mode == 2) ? (int)((grp->G - 1) * grp->b_gs) : 0), ldb);
             const double gain_us = 0.33 * (2.0 * M * N * K) / 150e6, cost_us = 3.0 + mbytes / 3e6;
-            if (mbytes > 0.0 && gain_us < cost_us && !always) ok = false;
+            if (mbytes > 0.0 && gain_us < cost_us) ok = false;
         }
         if (!ok) { }
         else if (xf && xf->which == 1) ok = xf->mean && xf->invstd;

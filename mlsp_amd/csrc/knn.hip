@@ -288,11 +288,7 @@ __global__ __launch_bounds__(256) void knn_mfma3_kernel(const float* __restrict_
             // selection for query row r of the current tile
             float pd = fmaf(2.0f, accCur[r], -xxc) - xxq[r];
             if (j >= N) pd = -INFINITY;
-#ifdef KNN_PROBE_NOSELECT
-            unsigned long long m = 0; lv[r] = fmaxf(lv[r], pd);
-#else
             unsigned long long m = __ballot(pd > thr[r]);
-#endif
             if (m) {
                 // everything that steers the insertion is wave-uniform (the ballot is an SGPR pair): the survivor of
                 // each half is broadcast with v_readlane, the tail shifts down one lane with a DPP wave_shr -- no
@@ -411,9 +407,7 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
     float xxstage = 0.f;                                  // candidate norms travel with the tile (no exposed load in r2s)
     auto g2r_tile = [&](int t) {
         const int j0 = t * 32;
-#ifndef KNN4_NO_XXPF
         if (tid < 32) xxstage = (t < ntiles && j0 + tid < N) ? xxb[j0 + tid] : 0.f;
-#endif
 #pragma unroll
         for (int p = 0; p < NLD; ++p) {
             int f = tid + 256 * p;
@@ -441,22 +435,12 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
                 for (int e = 0; e < 4; ++e) T[(c + e) * KM_STRIDE + cand] = stage[p][e];
             }
         }
-#ifndef KNN4_NO_XXPF
         if (tid < 32) cxx[(t % 3) * 32 + tid] = xxstage;
-#else
-        if (tid < 32) {
-            int j = t * 32 + tid;
-            cxx[(t % 3) * 32 + tid] = (t < ntiles && j < N) ? xxb[j] : 0.f;
-        }
-#endif
     };
 
     // one full sweep over the candidate tiles; sel(r, pd, t) is invoked for every query row of every tile
     auto sweep = [&](auto&& sel) {
         f32x16 accCur, accNext;
-#ifdef KNN4_PROBE_NOSEL
-        float cmx = -INFINITY;
-#endif
 #pragma unroll
         for (int r = 0; r < 16; ++r) { accCur[r] = 0.f; accNext[r] = 0.f; }
         __syncthreads();                       // previous sweep is done with the tile buffers
@@ -474,9 +458,7 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
         for (int t = 0; t < ntiles; ++t) {
             __syncthreads();
             const bool have_next = t + 1 < ntiles;
-#ifndef KNN4_PROBE_NOGLOBAL
             if (t + 2 < ntiles) g2r_tile(t + 2);
-#endif
             const float* T = tiles + ((t + 1) & 1) * TILE + h * KM_STRIDE + l31;
             const float xxc = cxx[(t % 3) * 32 + l31];
             const int j = t * 32 + l31;
@@ -497,22 +479,13 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
                 }
                 float pd = fmaf(2.0f, accCur[r], -xxc) - xxq[r];
                 if (j >= N) pd = -INFINITY;
-#ifdef KNN4_PROBE_NOSEL
-                cmx = fmaxf(cmx, pd);
-#else
                 sel(r, pd, t);
-#endif
-#ifndef KNN4_NO_SCHED_BARRIER
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
             if (t + 2 < ntiles) r2s_tile(t & 1, t + 2);
 #pragma unroll
             for (int r = 0; r < 16; ++r) accCur[r] = accNext[r];
         }
-#ifdef KNN4_PROBE_NOSEL
-        if (cmx == 12345.f) idx[1] = 1;
-#endif
     };
 
     // ---- pass A: per-lane chunk maxima -> tau = k-th largest of the 32 lane values of each query
@@ -537,10 +510,6 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
         thr[r] = h ? t1 : t0;
     }
 
-#if defined(KNN4_PROBE) && KNN4_PROBE == 1
-    if (thr[0] == 12345.f) idx[0] = 1;
-    return;
-#endif
     // ---- pass B: ballot-compaction of the survivors (pd >= tau) into the per-query buffers
     int cnt[16];
 #pragma unroll
@@ -562,10 +531,6 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
     bool over = false;
 #pragma unroll
     for (int r = 0; r < 16; ++r) over |= cnt[r] > KNN4_CAP;
-#if defined(KNN4_PROBE) && KNN4_PROBE == 2
-    if (over) idx[0] = cnt[3];
-    return;
-#endif
 
     if (!__syncthreads_or(over ? 1 : 0)) {
         // ---- exact rank select among the survivors
@@ -715,11 +680,7 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
                                                         int ld, int N, int C, int k, int* __restrict__ idx, int B, const int* __restrict__ only_clouds) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int TILE = CT * KM_STRIDE;
-#ifndef KNN5_NO_BF16A
     constexpr bool AP = (CT == 64 || (CT == 128 && KB == 0)) && !RES && VEC;     // pass A on the bf16 matrix cores (header comment above the kernel; C = 128 with k > 24 is out of registers)
-#else
-    constexpr bool AP = false;
-#endif
     constexpr int PA = CT + 8;                              // bf16 elements per candidate row of a pass-A image (16-byte aligned rows)
     constexpr int TILEA = 32 * PA;                          // floats of one pass-A tile image: hi rows [32][PA] bf16, then lo rows
     constexpr int TILE_ALLOC = (AP && TILEA > TILE) ? TILEA : TILE;
@@ -805,11 +766,6 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
         for (int j = tid; j < N; j += 512) cxx[j] = xxb[j];
     }
 
-#if defined(KNN5_PROBE) && KNN5_PROBE == 3
-    __syncthreads();
-    if (tiles[tid] == 12345.f) idx[0] = 1;
-    return;
-#endif
     // streaming mode: the 256 threads of a half stage that half's tiles (registers -> LDS, k-major)
     constexpr int NLD = VEC ? (32 * CT / 4 + 255) / 256 : (32 * CT + 255) / 256;
     f32x4 stagev[VEC ? NLD : 1];
@@ -890,9 +846,6 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
     auto sweep = [&](auto&& sel, auto&& at_mid, auto approx_tag) {
         constexpr bool APX = AP && decltype(approx_tag)::value;        // this sweep computes its tiles with the split-bf16 products
         f32x16 accCur, accNext;
-#ifdef KNN5_PROBE_NOSEL
-        float cmx = -INFINITY;
-#endif
 #pragma unroll
         for (int r = 0; r < 16; ++r) { accCur[r] = 0.f; accNext[r] = 0.f; }
         __syncthreads();                       // previous sweep is done with the tile buffers / RES image is complete
@@ -979,22 +932,13 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
                     }
                 }
                 const float pd = fmaf(2.0f, accCur[r], -xxc) - xxq[r];
-#ifdef KNN5_PROBE_NOSEL
-                cmx = fmaxf(cmx, pd);
-#else
                 sel(r, pd, j);
-#endif
-#ifndef KNN5_NO_SCHED_BARRIER
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
             if (!RES && tl + 2 < nt2) { if (APX) r2s_tileA(tl & 1, tl + 2); else r2s_tile(tl & 1, tl + 2); }
 #pragma unroll
             for (int r = 0; r < 16; ++r) accCur[r] = accNext[r];
         }
-#ifdef KNN5_PROBE_NOSEL
-        if (cmx == 12345.f) idx[1] = 1;
-#endif
     };
 
     // ---- pass A: chunk maxima of this half
@@ -1016,10 +960,6 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
         for (int r = 0; r < 16; ++r) xch[(KB ? ((qg * 2 + ch) * 2 + 1) * 16 + r : (qg * 2 + ch) * 16 + r) * KNN5_XS + lane] = cm[r];
     }
     __syncthreads();
-#if defined(KNN5_PROBE) && KNN5_PROBE == 4
-    if (xch[tid] == 12345.f) idx[0] = 1;
-    return;
-#endif
     // tau = k-th largest of a query's chunk maxima.  One lane per query: the first 32 lanes of waves 0-3 (one per
     // SIMD) pull the 64 values of "their" query into registers and run a bitonic sorting network (672 min/max pairs,
     // no cross-lane traffic, no data-dependent control).  KB = 1: lanes 32-63 sort the 64 maxima of the other candidate
@@ -1095,10 +1035,6 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
     }
     if (KB || AP) load_queries();              // dead across pass A / the tau phase (register budget), read here
 
-#if defined(KNN5_PROBE) && KNN5_PROBE == 1
-    if (thr[0] == 12345.f) idx[0] = 1;
-    return;
-#endif
     if (!KB) {
         // ---- pass B: survivors of this half -> this wave's key buffers
         u64* mybuf = bufk + (size_t)(qg * 2 + ch) * 32 * KNN5_CAP;
@@ -1119,10 +1055,6 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) over |= cnt[r] > KNN5_CAP;
 
-#if defined(KNN5_PROBE) && KNN5_PROBE == 2
-        if (over) idx[0] = cnt[3];
-        return;
-#endif
         if (__syncthreads_or(over ? 1 : 0)) {
             // ---- pass C (exact for any input): sequential insertion over this half, lane-distributed sorted lists
             float lv[16];
@@ -1344,9 +1276,7 @@ static int launch_knn_mfma5_ct(hipStream_t st, const float* x, int ld, const flo
 
 static size_t knn5_lds_bytes(int CT, int N, bool res, bool kb, bool vec = false) {
     size_t tile = (size_t)CT * KM_STRIDE;
-#ifndef KNN5_NO_BF16A
     if ((CT == 64 || (CT == 128 && !kb)) && !res && vec && (size_t)32 * (CT + 8) > tile) tile = (size_t)32 * (CT + 8);     // pass-A images (kernel: TILE_ALLOC)
-#endif
     const size_t keys = kb ? (size_t)2 * 128 * KNN5_CAPT : (size_t)2 * 4 * 2 * 32 * KNN5_CAP;     // floats
     const size_t fl = (res ? (size_t)(N / 32) * tile + N : 4 * tile + 192) + keys + 128 + 256;
     return fl * sizeof(float);
@@ -1410,23 +1340,20 @@ int launch_knn6w(hipStream_t st, const float* x, int ld, int B, int N, int C, in
 int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx_ws, void* planes, size_t plane_bytes) {
     if (!x || !idx || !xx_ws || B <= 0 || N <= 0 || C <= 0 || k <= 0 || k > N || ld < C) return MLSP_ERR_ARG;
     int P = B * N;
-    // v6 (knn6.hip): k <= 24 on whole 128-query chunks -- the five graph stages of DGCNN.  MLSP_KNN_V5=1: read-once A/B switch.
-    static const bool force_v5 = getenv("MLSP_KNN_V5") != nullptr;
-    static const bool v6_all = getenv("MLSP_KNN_V6_ALL") != nullptr;
-    static const bool no_vex = getenv("MLSP_KNN_NO_VEX") != nullptr;         // read-once A/B switch: C <= 3 back on the MFMA kernel
     // C <= 3 (raw and transformed cloud): the v6 skeleton with vector-exact sweeps (knn6.hip VEX)
-    if (!force_v5 && !no_vex && planes && knn6_vex_supported(B, N, C, k) && plane_bytes >= knn6_vex_bytes(P)) {
+    if (planes && knn6_vex_supported(B, N, C, k) && plane_bytes >= knn6_vex_bytes(P)) {
         const int rc = launch_knn6_vex(st, x, ld, B, N, C, k, idx, xx_ws, planes);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
-    if (!force_v5 && planes && knn6_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) && (C > 16 || v6_all)) {   // (C <= 16 stays on v5 until v6's selection phases beat it there)
+    // v6 (knn6.hip): k <= 24 on whole 128-query chunks -- the five graph stages of DGCNN
+    if (planes && knn6_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) && C > 16) {   // (C <= 16 stays on v5 until v6's selection phases beat it there)
         const int rc = launch_knn6(st, x, ld, B, N, C, k, idx, xx_ws, planes);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
     // 24 < k <= 40 (PointSegDA's k = 40): the wide v6 kernel, with the v5 kernel behind it for the clouds it flags (list overflow: massive
     // ties; non-finite bounds) -- v5's workgroups of unflagged clouds return at once.  Only where v5 itself takes the shape.
     // Every C <= 128: at C = 3 (B = 16, N = 2048, k = 40) 82 us against v5's 117, C = 64 152 / 235, C = 128 210 / 435.
-    if (!force_v5 && planes && knn6w_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) &&
+    if (planes && knn6w_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) &&
         launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx, nullptr, true) == 0) {
         int* flags = nullptr;
         const int rc = launch_knn6w(st, x, ld, B, N, C, k, idx, xx_ws, planes, &flags);
@@ -1439,10 +1366,8 @@ int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int 
     if (C <= 256) {
         // two-pass threshold select pays once there are enough candidates per query; small clouds keep v3
         if (k <= 32 && C <= 128 && N >= 256) {
-#ifndef KNN_NO_V5
             const int rc = launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx);
             if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-#endif
             return launch_knn_mfma4(st, x, ld, xx_ws, B, N, C, k, idx);
         }
         if (k > 24 && k <= 64 && C <= 128 && N >= 128) {       // 128 chunk maxima per query need N >= 128
@@ -1535,10 +1460,6 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
     for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o, 64);
     if ((tid & 63) == 0) wsum[tid >> 6] = below;
     __syncthreads();
-#if defined(RV_PROBE) && RV_PROBE == 1
-    if (below == -12345) rev_off[0] = 1;
-    return;
-#endif
     int s0 = 0;
     for (int w = 0; w < (nt >> 6); ++w) s0 += wsum[w];   // edges into the slices before this one
     // exclusive scan of the slice's counts by one wave
@@ -1572,9 +1493,6 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
     }
     if (b == B - 1 && part == nsplit - 1 && tid == 0) rev_off[(size_t)B * N] = gbase + E;
     __syncthreads();
-#if defined(RV_PROBE) && RV_PROBE == 2
-    return;
-#endif
     // fill + order this slice's lists in LDS, then one coalesced copy out: the ordering never touches global memory
     // (a slice with more than RV_CAP entries orders in place in global memory instead)
     int* ent = in_lds ? lent : rev_ent + gbase + s0;
@@ -1604,10 +1522,6 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
         }
     }
     __syncthreads();
-#if defined(RV_PROBE) && RV_PROBE == 3
-    if (ent[tid] == -12345) rev_off[0] = 1;            // (keeps the fill pass alive in the probe build)
-    return;
-#endif
     if (in_lds) {
         // order every list by (i, slot) by RANK: 16 lanes per list, every lane ranks its entries against the whole list (the 16 lanes
         // read the same LDS words: broadcasts) and writes them straight to their final place.  Lists of more than 64 entries
@@ -1667,10 +1581,6 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
             }
         }
         __syncthreads();
-#if defined(RV_PROBE) && RV_PROBE == 4
-        if (lord[tid] == -12345) rev_off[0] = 1;
-        return;
-#endif
         for (int i = tid; i < sn; i += nt) rev_ent[gbase + s0 + i] = lord[i];      // one coalesced copy out
         return;
     }

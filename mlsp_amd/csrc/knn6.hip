@@ -177,15 +177,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
     float* lmn = (float*)(wlbase + 8 * 512);                  // [128 queries][4 quarters] min of -xc_j / 2 over the list's survivors
     const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)sm);       // LDS byte address of `lists`
 
-#ifdef K6_STAMP
-    long long stamp[10];
-    int st_items = 0, st_flushes = 0;
-    long long st_f2 = 0;
-#define K6_T(i_) stamp[i_] = (long long)__builtin_amdgcn_s_memtime()
-#else
-#define K6_T(i_)
-#endif
-    K6_T(0);
     float xcmax, xxmax;
     {
         float m = 0.f, mr = 0.f;
@@ -308,7 +299,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
         }
     };
 
-    K6_T(1);
     // ---- pass A: 16 running maxima per lane (acc domain: a = dot' - xc_j / 2 is monotone in the distance for a fixed query)
     {
         float cm[16];
@@ -318,16 +308,11 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) cm[r] = fmaxf(cm[r], acc[r]);
         });
-        K6_T(2);
         float* dst = xch + (qg * 32 + l31) * K6_XS + (ch * 2 + h) * 16;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) { const f32x4 v = {cm[4 * g4], cm[4 * g4 + 1], cm[4 * g4 + 2], cm[4 * g4 + 3]}; *(f32x4*)(dst + 4 * g4) = v; }
     }
     __syncthreads();
-#if defined(K6_PROBE) && K6_PROBE == 1
-    return;
-#endif
-    K6_T(3);
     // tau = k-th largest of a query's 64 maxima: one lane per query (the ch = 0 wave of a group: one wave per SIMD; lanes 32-63 mirror), bitonic
     // network in registers
     if (ch == 0) {
@@ -358,10 +343,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
         if (lane < 32) tauv[qs] = t;
     }
     __syncthreads();                                          // tau complete; the exchange image (aliases the lists) is dead from here on
-#if defined(K6_PROBE) && K6_PROBE == 2
-    return;
-#endif
-    K6_T(4);
     float thr = tauv[qg * 32 + l31] - Eq;                     // acc domain: pd' >= tau_pd - 2 E  <=>  a >= a_tau - E
     thr = thr == thr ? thr : -INFINITY;                       // (a non-finite bound Eq sends the workgroup through the exact path: `ovf` below)
 
@@ -392,7 +373,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
     // overflow (massive ties), or no usable bound: a non-finite norm in the cloud (the approximate values of a NaN row are NaN and survive
     // no comparison, so they would not overflow anything: ask for the exact path outright)
     const int ovf = (top > base + K6_CAP * 8 || !(Eq < INFINITY)) ? 1 : 0;
-    K6_T(5);
     bool exact_lists = false;
     if (__syncthreads_or(ovf)) {
         // ------------------------------------------------------------------------------------------------------------ exact path (rare)
@@ -462,7 +442,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
         }
         exact_lists = true;
     }
-    K6_T(6);
     // ---- F0: every lane moves ITS list to the pd domain (pd' = 2 a - xc_q; the exact path stored pd itself) and fills it to the end with
     //      {-inf, 0} (never ahead of, never close to a real entry: the counting loops of the slow final read whole blocks unmasked)
     {
@@ -486,25 +465,10 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
         lmn[(qg * 32 + l31) * 4 + ch * 2 + h] = mn;
     }
     __syncthreads();
-#if defined(K6_PROBE) && K6_PROBE == 3
-    return;
-#endif
 
     // ---------------------------------------------------------------------------------------------------------------- final: exact ranks
-    K6_T(7);
     const bool xvec = (ld & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (C & 3) == 0;
     auto list_at = [&](int qlc_, int t) -> char* { return lists + (size_t)((((qg * 2 + (t >> 1)) * 2 + (t & 1)) * 32 + qlc_) * K6_LSTR); };
-#ifdef K6_STAMP
-    auto put_stamps = [&]() {
-        K6_T(8);
-        __syncthreads();
-        if (lane == 0 && blockIdx.x < 32) {       // diagnostic build only (tools/knn6_stamps.py): stamps go behind the fragment image in the caller's workspace
-            int* o = (int*)(const_cast<char*>(planes) + (size_t)B * N * CT * 4 + (size_t)B * N * 4) + (blockIdx.x * 8 + wave) * 16;
-            for (int i = 1; i <= 8; ++i) o[i - 1] = (int)(stamp[i] - stamp[i - 1]);
-            o[8] = (int)st_f2; o[9] = st_items; o[10] = st_flushes; o[11] = (int)(stamp[8] - stamp[0]);
-        }
-    };
-#endif
     // ---- fast final (every query of the group has at most 32 survivors -- the normal case): FOUR LANES PER QUERY.  Wave (qg, ch) finishes queries
     // ch * 16 .. + 15 of its group; lane l serves query l & 15 and holds rank positions 8 m .. 8 m + 7 of its 32 (m = l >> 4).  The four lanes pull the
     // query's survivors into registers and sort them by pd' with a bitonic network whose exchanges at distance 8 / 16 cross lanes (v_permlane16 /
@@ -601,9 +565,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
             for (int i = 0; i < 7; ++i) amb |= (8 * m + i + 1 < n && !(pv[i] - pv[i + 1] > E2)) ? (3u << i) : 0u;
             amb |= (m < 3 && 8 * m + 8 < n && !(pv[7] - nxt0 > E2)) ? 0x80u : 0u;
             amb |= (m > 0 && 8 * m < n && !(prv7 - pv[0] > E2)) ? 1u : 0u;
-#if defined(K6_PROBE) && K6_PROBE == 4
-            amb = 0u;
-#endif
             const int nfl = __builtin_popcount(amb);           // this lane's flagged entries; the query's: the four lanes' sum
             const int f0 = __shfl(nfl, ql, 64), f1 = __shfl(nfl, ql + 16, 64), f2 = __shfl(nfl, ql + 32, 64), f3 = __shfl(nfl, ql + 48, 64);
             const int nflag = f0 + f1 + f2 + f3;
@@ -621,10 +582,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
             for (int o = 32; o > 0; o >>= 1) fmaxw = max(fmaxw, __shfl_xor(fmaxw, o, 64));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-#ifdef K6_STAMP
-            const long long f0_ = (long long)__builtin_amdgcn_s_memtime();
-            st_items += nfl; st_flushes = fmaxw;
-#endif
             // Canonical distances of the flagged pairs, DENSELY packed over the wave's lanes: pair i of the wave = (query, slot) by a prefix sum of
             // the 16 queries' flag counts (the counts differ a lot from query to query: slot-by-slot rounds ran at a third of the lanes).  Both rows
             // fetched whole (2 x 16 x 16 bytes in flight per lane at C = 64), fmaf chain channels ascending.  (Staging the rows through LDS with
@@ -674,9 +631,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
-#ifdef K6_STAMP
-            st_f2 += (long long)__builtin_amdgcn_s_memtime() - f0_;
-#endif
             {
                 int c = 0;
 #pragma unroll
@@ -724,9 +678,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
                     if (pos < k && pos < n) out[pos] = jv[a];
                 }
             }
-#ifdef K6_STAMP
-            put_stamps();
-#endif
             return;
         }
     }
@@ -846,9 +797,6 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
             flush();
         }
     }
-#ifdef K6_STAMP
-    put_stamps();
-#endif
 }
 
 

@@ -279,9 +279,8 @@ static int multi_check(const float* X, int ldx, int M, const mlsp_seg_t* segs, i
 // Length of the run of segments starting at s that ONE block-diagonal GEMM launch can take (gemm.hip GemmGroups): same shape and
 // weight pitch, no bias, input slices back to back, widths a multiple of the 128-wide tile, interior 16-byte-aligned operands.
 static int multi_group_run(const float* X, int ldx, int M, const mlsp_seg_t* segs, int nseg, int s, const mlsp_defer_t* in = nullptr) {
-    static const bool off = getenv("MLSP_NO_GROUPED_GEMM") != nullptr;          // read-once A/B switch
     const mlsp_seg_t& a = segs[s];
-    if (off || gemm_precision_mode() == 1 || a.bias || a.Cin % 128 || a.Cout % 128 || M % 128 || ldx % 4 || a.ldw % 4 || (((uintptr_t)X | (uintptr_t)a.W) & 15)) return 1;
+    if (gemm_precision_mode() == 1 || a.bias || a.Cin % 128 || a.Cout % 128 || M % 128 || ldx % 4 || a.ldw % 4 || (((uintptr_t)X | (uintptr_t)a.W) & 15)) return 1;
     int n = 1;
     while (s + n < nseg && n < 4) {
         const mlsp_seg_t& b = segs[s + n];
@@ -457,8 +456,7 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
     const float ik = dropout_inv_keep8(pd);
     // masked gradient + its sums in hand: when every dgrad / weight-gradient launch of this layer can form dY = (d' + y * nk2 + c0) * sc in
     // its A operand loads (gemm.hip gemm_split_kernel<.., DY>) the apply pass and the dY tensor are skipped altogether
-    static const bool dy_off = getenv("MLSP_BWD_DY_OFF") != nullptr;        // read-once A/B switch (tools/ab)
-    bool use_dy = pre_stats && training && !dy_off && !any_mat;
+    bool use_dy = pre_stats && training && !any_mat;
     for (int s = 0, yc = 0; s < nseg && use_dy; yc += run[s] * segs[s].Cout, s += run[s]) {
         const mlsp_seg_t& g = segs[s];
         if (dX) use_dy = gemm_dy_supported(false, false, M, run[s] * g.Cin, g.Cout, dZ + yc, Ctot, g.W, g.ldw);

@@ -292,12 +292,8 @@ __global__ __launch_bounds__(256) void thin_tn_kernel(const float* __restrict__ 
 }
 
 int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit);
-#ifndef THIN_SN_BLOCKS
 #define THIN_SN_BLOCKS 1024  // workgroups of the small-N kernel at most (512: 24.9 / 8.1 us, 1024: 21.2 / 7.2 us for the 16- / 3-channel layers)
-#endif
-#ifndef THIN_TN_ROWS
 #define THIN_TN_ROWS 64      // rows of the K dimension per workgroup (one partial slab each)
-#endif
 
 // rows of the K dimension per workgroup: 64 with 16 accumulator quads per thread, 32 with 4 (measured: 6.8 -> 6.2 us for the 3-channel
 // layers, 21.4 -> 27.7 us for the 16-channel one at 32)

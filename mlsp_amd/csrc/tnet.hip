@@ -234,11 +234,7 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd2_kernel(TnetFwdArgs p) {
             const int pt = row / K, s = row - pt * K;
             const bool ok = item < TF_ROWS * 4 && pt < np;
             okm_ |= ok ? 1 << u : 0;
-#ifdef TF_PROBE_NOGATHER
-            jraw[u] = t0 + pt - (t0 / p.N) * p.N;
-#else
             jraw[u] = p.idx[ok ? (size_t)(t0 + pt) * K + s : (size_t)0];
-#endif
         }
     };
     bool have = tn_tile(0, Bc, p.N, PT, pt0, npts);
@@ -325,7 +321,6 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd2_kernel(TnetFwdArgs p) {
                 }
             }
         };
-#ifndef TF_PROBE_NOMFMA
 #pragma unroll
         for (int b = 0; b < 5; ++b) {
 #pragma unroll
@@ -345,18 +340,6 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd2_kernel(TnetFwdArgs p) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) epi(4, r);
-#else
-#pragma unroll
-        for (int b = 0; b < 5; ++b) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-            acc[b][0] = Hs[(32 * b + l31) * TF_PITCH + h] * w2[b].x;
-        }
-#pragma unroll
-        for (int b = 0; b < 5; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) epi(b, r);
-#endif
         ssum += s1; ssq += s2;
 #pragma unroll
         for (int q = 0; q < PT; ++q) {
@@ -460,19 +443,9 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
             const int pt = row / K, s = row - pt * K;
             const bool ok = item < TF_ROWS * 4 && pt < np;
             okm_ |= ok ? 1 << u : 0;
-#ifdef TF_PROBE_NOGATHER
-            jraw[u] = t0 + pt - (t0 / p.N) * p.N;
-#else
             jraw[u] = p.idx[ok ? (size_t)(t0 + pt) * K + s : (size_t)0];
-#endif
         }
     };
-#ifdef TF3_STAMPS
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
-#define TF3_STAMP(i_) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tsum[i_] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define TF3_STAMP(i_)
-#endif
     bool have = tn_tile(0, Bc, p.N, PT, pt0, npts);
     int jraw[3] = {0, 0, 0}, okm = 0, jbase = 0;
     if (have) { tile_rows(pt0, npts, jraw, okm); jbase = (pt0 / p.N) * p.N; }
@@ -497,12 +470,9 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
         const bool haven = tn_tile(m + 1, Bc, p.N, PT, pt0n, nptsn);
         int jnext[3], okn;
         tile_rows(haven ? pt0n : pt0, haven ? nptsn : 0, jnext, okn);
-        TF3_STAMP(0);
         __syncthreads();                              // every wave is done reading the previous tile's H (and Vs)
-        TF3_STAMP(1);
         if (tid < PT * 16) *(f32x4*)(Vs + 4 * tid) = vstage;
         __syncthreads();
-        TF3_STAMP(2);
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             const int item = tid + 256 * u, row = item >> 2, qt = item & 3;
@@ -529,9 +499,7 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
                 }
             }
         }
-        TF3_STAMP(3);
         __syncthreads();
-        TF3_STAMP(4);
         // ---- Z = H W2^T for this wave's 32 columns, one row block after the other; the register epilogue of block b - 1 (per point
         //      max / min over its K rows with the first arg-max, BN2 sums: ~6 vector instructions per element) is issued BETWEEN the
         //      MFMAs of block b.  A vector instruction that has to squeeze in between another wave's back-to-back MFMAs waits about one
@@ -603,7 +571,6 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        TF3_STAMP(5);
 #pragma unroll
         for (int r = 0; r < 16; ++r) epi(4, r);
         ssum += s1; ssq += s2;
@@ -618,7 +585,6 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
                 p.argsel[(size_t)(pt0 + q) * TN_C2 + o] = (uint8_t)bslot[q];
             }
         }
-        TF3_STAMP(6);
         have = haven; pt0 = pt0n; npts = nptsn;
 #pragma unroll
         for (int u = 0; u < 3; ++u) jraw[u] = jnext[u];
@@ -631,15 +597,7 @@ __global__ __launch_bounds__(256, 2) void tnet_edge_fwd3_kernel(TnetFwdArgs p) {
         p.part[((size_t)blockIdx.x * 2 + 0) * TN_C2 + o] = ssum;
         p.part[((size_t)blockIdx.x * 2 + 1) * TN_C2 + o] = ssq;
     }
-#ifdef TF3_STAMPS
-    if (tid == 0) {                                            // diagnostic build only: overwrites this workgroup's BN2 partial
-        unsigned long long* o2 = (unsigned long long*)(p.part + (size_t)blockIdx.x * 2 * TN_C2);
-        o2[0] = 0x5446335354414d50ull;
-        for (int q = 0; q < 8; ++q) o2[1 + q] = tsum[q];
-    }
-#endif
 }
-#undef TF3_STAMP
 
 
 // t = act(scale2 * zsel + shift2)        [P][128]
@@ -1099,7 +1057,6 @@ template <int MODE, int KR> __global__ __launch_bounds__(512) void tnet_edge_bwd
         const uint32_t* at = L.aT[m & 1];
         for (int half = 0; half < 2; ++half) {
             if ((half == 0) == (wave < 4)) {
-#ifndef TG_PROBE_NOMFMA
                 // the two accumulation chains alternate: a wave alone keeps the matrix pipe full (a chain by itself waits for each result)
 #pragma unroll 4
                 for (int kk = 0; kk < 16; ++kk) {
@@ -1112,11 +1069,9 @@ template <int MODE, int KR> __global__ __launch_bounds__(512) void tnet_edge_bwd
                     accP = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1, accP, 0, 0, 0);
                     accG = __builtin_amdgcn_mfma_f32_32x32x2f32(ga1, gb1, accG, 0, 0, 0);
                 }
-#endif
             } else {
                 // ---- S[row(pt, arg)][lane] = sum_o g[pt][o] W2[o][lane] over the channels whose arg-max is that row: one wave per
                 // (point, 32-slot range) keeps its rows in the indexed register block, adds in ascending o, then stores the rows
-#ifndef TG_PROBE_NOSCATTER
                 if (wave < npts * nsw) {
                     const int spt = wave / nsw, s0 = (wave - spt * nsw) * 32;
                     const int gv0 = __float_as_int(gt[spt * TN_C2 + lane]), gv1 = __float_as_int(gt[spt * TN_C2 + 64 + lane]);
@@ -1155,12 +1110,10 @@ template <int MODE, int KR> __global__ __launch_bounds__(512) void tnet_edge_bwd
                     for (int i = 0; i < NB; ++i)
                         if (s0 + i < k) sb[i * TN_C1] = MODE == 1 ? (i < 8 ? acc2[i & 7] : acc[(i - 8) & 31]) : acc[i & 31];
                 }
-#endif
                 // ---- G1[16 wave + i][lane] += g[pt][o] H'[row(pt, arg)][lane]: KR (>= k, or 32 when RANGED) of the point's H' rows are
                 // loaded into the indexed register block, the 16 entries then cost one indexed FMA each.  Rows past k are the next
                 // points' rows (or, past the tile, whatever follows in LDS, zeroed at kernel start): finite, and only ever multiplied
                 // by an exact zero.
-#ifndef TG_PROBE_NOG1
                 for (int pt = 0; pt < npts; ++pt) {
                     const int gvi = __float_as_int(gt[pt * TN_C2 + 16 * wave + (lane & 15)]);
                     const uint32_t av = at[pt * (TN_C2 / 4) + 4 * wave + (lane & 3)];
@@ -1186,7 +1139,6 @@ template <int MODE, int KR> __global__ __launch_bounds__(512) void tnet_edge_bwd
                         tg_fma_src8<MODE>(accO + 8, rows2, rows, ae[2], ae[3], (const uint32_t(&)[8])ge[8], s0);
                     }
                 }
-#endif
             }
         }
         if (haven) { store_rows(L.Hs[(m & 1) ^ 1], jn, u, v); store_scal((m & 1) ^ 1, gq, aq); }
@@ -1206,11 +1158,7 @@ template <int MODE, int KR> __global__ __launch_bounds__(512) void tnet_edge_bwd
                 const int dr = (r & 3) + 8 * (r >> 2);
                 const float sv = sp[dr * TN_C1];
                 const float hv = hp[dr * TG_HP];
-#ifdef TG_PROBE_NOEPI
-                if (row0 + dr < nvalid && sv == 123.456f) {
-#else
                 if (row0 + dr < nvalid) {
-#endif
                     const float dH = (sv - accP[r]) - cvc;
                     const float a = hv > 0.f ? hv : hv * rslope;
                     const float d = dH * (hv > 0.f ? 1.f : slope);
@@ -1494,12 +1442,6 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; acch[0][r] = 0.f; acch[1][r] = 0.f; }
     double sd[2] = {0.0, 0.0}, sdh[2] = {0.0, 0.0}, shs[2] = {0.0, 0.0};
 
-#ifdef TB_STAMPS
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define TB_STAMP(i_) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tsum[i_] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define TB_STAMP(i_)
-#endif
     bool pend = false; int ppt0 = 0, pnvalid = 0;              // waves 0-3: the epilogue of (channel tile 1, previous tile) is still due
     wc.init(wp, P / N, N, TP);
     wn = wc; wn.next(wp);
@@ -1519,9 +1461,6 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
     }
     RowIdx jn = row_index(wn);
     __syncthreads();
-#ifdef TB_STAMPS
-    tprev = __builtin_amdgcn_s_memtime();
-#endif
     while (wc.ok(wp)) {
         const int pt0 = wc.cloud * N + wc.tic * TP, npts = min(TP, N - wc.tic * TP);
         const int pt0n = wn.ok(wp) ? wn.cloud * N + wn.tic * TP : pt0, nptsn = wn.ok(wp) ? min(TP, N - wn.tic * TP) : 0;
@@ -1532,7 +1471,6 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
         load_rows(jrow, pt0n, u, vst);                         // next tile's rows and scalars in flight during this tile's products
         load_scal(pt0n, nptsn, gv, ab);
         const RowIdx jnn = row_index(wnn);
-        TB_STAMP(0);
         int opq;                                               // an opaque zero: keeps the role-specific addressing below out of the loop-invariant set
         asm volatile("s_mov_b32 %0, 0" : "=s"(opq));
         if (wave < 4) {
@@ -1647,10 +1585,8 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
                 }
             };
             pass(std::integral_constant<int, 0>{}, pend, ppt0, pnvalid);
-            TB_STAMP(1);
             pass(std::integral_constant<int, 1>{}, true, pt0, nvalid);
             pend = true; ppt0 = pt0; pnvalid = nvalid;
-            TB_STAMP(3);
         } else {
             // ---- G1 += gsel^T H' and the Gram tile (gi, gj): K = the tile's rows; A fragment = channel `go_` of the 8 rows of the k16 step
             const int go_ = 32 * mt + l31 + opq;               // this lane's output channel o as the M index of G1
@@ -1713,15 +1649,11 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            TB_STAMP(1);
         }
         L.Vs[tid] = vst;                                       // (Vs is only read between the two barriers)
         __syncthreads();                                       // every wave has read its fragments: the images may be overwritten
-        TB_STAMP(4);
         if (wn.ok(wp)) { store_rows(jrow, u); store_scal(nptsn, gv, ab); }
-        TB_STAMP(5);
         __syncthreads();
-        TB_STAMP(6);
         wc = wn; wn = wnn; wnn.next(wp); jn = jnn;
     }
     if (wave < 4 && pend) {                                    // the last tile's second channel tile
@@ -1769,16 +1701,7 @@ __global__ __launch_bounds__(512) void tnet_edge_bwds_kernel(
         if (kind < 2) part1[((size_t)blockIdx.x * 2 + kind) * TN_C1 + c] = t;
         else slab[TN_C2 * TN_C1 + TN_C1 * TN_C1 + c] = (float)t;
     }
-#ifdef TB_STAMPS
-    __syncthreads();
-    if (lane == 0 && (wave == 0 || wave == 4)) {              // diagnostic build only: overwrites this workgroup's G1 partial
-        unsigned long long* o = (unsigned long long*)slab + (wave ? 16 : 0);
-        o[0] = 0x5354414d50533031ull + (wave ? 1 : 0);
-        for (int q = 0; q < 8; ++q) o[1 + q] = tsum[q];
-    }
-#endif
 }
-#undef TB_STAMP
 
 // Fold dh' onto the points (BN1 backward in closed form), wave per point, lane = channel (64):
 //   g_e = scale1*(dh'_e - m1 - hhat_e*m2);  dv_i = sum_s g_(i,s);  du_j = sum_{e in rev(j)} g_e
@@ -1850,18 +1773,14 @@ int launch_tnet_edge_fwd(hipStream_t st, const float* uv, const int* idx, const 
         a.TP = TF_ROWS / k;
         a.ntiles = (P / N) * ((N + a.TP - 1) / a.TP);
         // tnet_edge_fwd3_kernel (split products on the bf16 cores; closer to float64 than the f32-MFMA kernel: 1.7e-7 vs 2.0e-7 rel-L2,
-        // tools/tnet_acc.py) whenever the call's `precision` asks for products on the bf16 cores (modes 1 and 2), tnet_edge_fwd2_kernel
-        // (f32 MFMA) in mode 0 -- the product mode decides, at every size: B = 32, N = 1024 forward op 222 -> 173 us, B = 8 81 -> 70 us; small
+        // tests/test_gpu_kernels.py::test_tnet_forward_kernels_vs_float64) whenever the call's `precision` asks for products on
+        // the bf16 cores (modes 1 and 2), tnet_edge_fwd2_kernel (f32 MFMA) in mode 0 -- the product mode decides, at every size: B = 32, N = 1024 forward op 222 -> 173 us, B = 8 81 -> 70 us; small
         // launches are enqueue-bound and the two kernels take the same time (tools/time_tnet.py: 88 vs 84 us at B = 4, N = 128).
-        // Read-once A/B switches: MLSP_TNET_FWD_SPLIT=1 / MLSP_TNET_FWD_F32=1.
-        static const bool split_env = getenv("MLSP_TNET_FWD_SPLIT") != nullptr, f32_env = getenv("MLSP_TNET_FWD_F32") != nullptr;
-        const bool split_products = !f32_env && (split_env || gemm_precision_mode() != 0);
-        if (!split_products) {
+        if (gemm_precision_mode() == 0) {
             if (k == 20) hipLaunchKernelGGL((tnet_edge_fwd2_kernel<20>), dim3(grid), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((tnet_edge_fwd2_kernel<40>), dim3(grid), dim3(256), 0, st, a);
         } else {
-            static const bool six_env = getenv("MLSP_TNET_BF16_SIX") != nullptr;      // A/B: mode 1 on the six-product kernels (rounds 3-5)
-            const bool onep = gemm_precision_mode() == 1 && !split_env && !six_env;
+            const bool onep = gemm_precision_mode() == 1;
             if (k == 20 && !onep) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<20>), dim3(grid), dim3(256), 0, st, a);
             else if (k == 20) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<20, true>), dim3(grid), dim3(256), 0, st, a);
             else if (!onep) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<40>), dim3(grid), dim3(256), 0, st, a);
@@ -1913,20 +1832,17 @@ int launch_tnet_edge_bwd(hipStream_t st, const float* uv, const int* idx, const 
     const int TP = tnet_points_per_tile(k);
     if (TP <= 0) return MLSP_ERR_UNSUPPORTED;
     const int ntiles = (P / N) * ((N + TP - 1) / TP);
-    static const bool use_old = getenv("MLSP_TNET_BWD_OLD") != nullptr;       // A/B switch (tools/time_tnet.py): the round-1 kernel
-    if (!use_old && slope > 0.f) {                             // the pre-activation is recovered from the activated value: needs a bijection
+    if (slope > 0.f) {                             // the pre-activation is recovered from the activated value: needs a bijection
         const int nb = tnet_bwd_grid(ntiles);
         float* slabs = scratch;
         float* Mc = slabs + (size_t)nb * TG_SLAB;
         float* R = Mc + TN_C1 * TN_C1 + TN_C1;
         hipLaunchKernelGGL(tnet_bwd_prep_kernel, dim3(TN_C1 / 4 + 1), dim3(256), 0, st, W2, coef, bn2, Mc);
         // products on the bf16 cores (modes 1 and 2): the dense split form (tnet_edge_bwds_kernel); mode 0 keeps exact fp32 products with
-        // the register-indexed sparse half.  Read-once A/B switch: MLSP_TNET_BWD_F32=1.
-        static const bool f32_env = getenv("MLSP_TNET_BWD_F32") != nullptr;
-        if (!f32_env && gemm_precision_mode() != 0 && k % 2 == 0 && k >= 8 && k <= 64) {
+        // the register-indexed sparse half.
+        if (gemm_precision_mode() != 0 && k % 2 == 0 && k >= 8 && k <= 64) {
             const size_t lds = sizeof(TnetBwdSLds);
-            static const bool six_env = getenv("MLSP_TNET_BF16_SIX") != nullptr;      // A/B: mode 1 on the six-product kernel (rounds 4-5)
-            auto kern = (gemm_precision_mode() == 1 && !six_env) ? tnet_edge_bwds_kernel<true> : tnet_edge_bwds_kernel<false>;
+            auto kern = gemm_precision_mode() == 1 ? tnet_edge_bwds_kernel<true> : tnet_edge_bwds_kernel<false>;
             hipError_t e = mlsp_lds_limit((const void*)kern, lds);
             if (e != hipSuccess) return (int)e;
             hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, st, uv, idx, bn1, W2, Mc, g, argsel, dhp, slabs, part1, P, N, k, TP, slope);

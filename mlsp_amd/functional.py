@@ -5,7 +5,6 @@ or B*N*k edges).  The module layer (Models.py / model_utils.py) converts from an
 reference's channel-major [B, C, N] at its boundary only.
 """
 import itertools
-import os
 import threading
 
 import torch
@@ -40,7 +39,7 @@ def _rows(t, allow_bf16=False):
     return t
 
 
-_SHARE_BOUNDS = os.environ.get("MLSP_NO_OPERAND_BOUNDS") is None       # read-once A/B switch: off = every C call measures what it needs
+_SHARE_BOUNDS = True       # False: every C call measures what it needs
 
 
 class OperandBounds:
@@ -940,13 +939,13 @@ def tnet_edge_supported(W1, W2, k):
 # Deferred activations of chained layers (DeferredAct below): a Linear+BN+act(+dropout) layer whose consumers are all GEMM layers writes
 # only its pre-BatchNorm output; the consumers apply scale / shift / activation / dropout while they stage their operand
 # (gemm_split_kernel<.., XF, XD>, the f32 transform kernels, the thin streaming kernels).  On by default in the "bf16x6" and "fp32" product
-# modes with fp32 activation storage; MLSP_DEFERRED_ACT=0 restores the materialised chain (an A/B switch, read once).
-_DEFER_CHAINS = os.environ.get("MLSP_DEFERRED_ACT", "1") not in ("0", "")
+# modes with fp32 activation storage; False restores the materialised chain.
+_DEFER_CHAINS = True
 
 
-# BatchNorm-backward sums of a deferred layer, produced by its consumers' dgrads (csrc/gemm.hip gemm_out_bs, thin.hip): MLSP_BWD_STATS_FUSED=0
-# restores the streaming reduction pass (an A/B switch, read once).
-_FUSE_BWD_STATS = os.environ.get("MLSP_BWD_STATS_FUSED", "1") not in ("0", "")
+# BatchNorm-backward sums of a deferred layer, produced by its consumers' dgrads (csrc/gemm.hip gemm_out_bs, thin.hip): False restores
+# the streaming reduction pass.
+_FUSE_BWD_STATS = True
 
 
 class BwdStats:

@@ -218,6 +218,29 @@ def test_no_process_wide_dispatch_state_in_the_library():
     assert lib.mlsp_gemm_f32(0, 0, 8, 8, 8, None, 8, None, 8, None, 8, None, 7, None, 0, None) == -1
 
 
+def test_environment_reads_are_the_documented_ones():
+    """What a call computes is a function of its arguments and its `precision`, not of the environment the process started with: the only
+    MLSP_* environment name in the built library is MLSP_PROF_DUMP (a listing of profiled launches; it changes no kernel choice), and the
+    Python package reads only MLSP_GEMM_PRECISION (the process default mode) and MLSP_HIP_LIB (which library to load)."""
+    import glob
+    so = os.path.join(ROOT, "mlsp_amd", "libmlsp_hip.so")
+    if not os.path.exists(so):
+        pytest.skip("library not built here")
+    header = open(os.path.join(ROOT, "include", "mlsp_hip.h")).read()
+    abi_names = set(re.findall(r"#\s*define\s+(MLSP_\w+)", header))
+    names = {m.decode() for m in re.findall(rb"MLSP_[A-Z0-9_]+", open(so, "rb").read())} - abi_names
+    assert names == {"MLSP_PROF_DUMP"}, sorted(names)
+    keys = set()
+    for f in glob.glob(os.path.join(ROOT, "mlsp_amd", "*.py")):
+        src = open(f).read()
+        assert not re.search(r"\bgetenv\b|environ\s*(\[|\.(?!get\b))", src), f
+        for m in re.finditer(r"environ\.get\(([^,)]*)", src):
+            arg = m.group(1).strip()
+            assert re.fullmatch(r"[\"'][A-Z0-9_]+[\"']", arg), (f, arg)
+            keys.add(arg[1:-1])
+    assert keys == {"MLSP_GEMM_PRECISION", "MLSP_HIP_LIB"}, sorted(keys)
+
+
 def test_gemm_precision_is_per_thread_and_saved_per_call():
     """`with gemm_precision(m)` changes what THIS thread's forwards pass; another thread keeps the process default; set() moves the default."""
     import threading

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import golden_common as gc
-from oracle import knn_canon, ref_cpu
+from oracle import knn_canon, ref_cpu, ref_torch_modules
 
 pytestmark = pytest.mark.gpu
 
@@ -1059,17 +1059,77 @@ def test_tnet_edge_bf16_operands_vs_fp32_products(dev, B, N, k):
             assert rel > 1e-5, (name, rel)
 
 
+def _tnet_edge_f64(xp, idx, W1, g1, b1, W2, g2, b2, slope, sel=None):
+    """The T-Net per-edge stage through the reference's op sequence (oracle/ref_torch_modules.py: edge features, then 1x1 Conv2d +
+    BatchNorm2d on batch statistics + LeakyReLU twice, max over k), in the precision of its arguments: xp [P, C], idx [B, N, k] -> [P, 128].
+    sel [P, 128] (optional): the slot each max takes, instead of the arg-max of its own values."""
+    B, N, k = idx.shape
+    h = ref_torch_modules.edge_features(xp.view(B, N, -1).transpose(2, 1), k, lambda *_: idx)
+    for W, g, b in ((W1, g1, b1), (W2, g2, b2)):
+        h = F.leaky_relu(F.batch_norm(F.conv2d(h, W[:, :, None, None]), None, None, g, b, True, 0.1, 1e-5), slope)
+    z = h.max(dim=-1)[0] if sel is None else h.gather(-1, sel.long().view(B, N, -1).transpose(2, 1)[..., None])[..., 0]
+    return z.transpose(2, 1).reshape(B * N, -1)
+
+
 @pytest.mark.parametrize("B,N,k", [(8, 512, 20), (4, 512, 40)])
-def test_tnet_backward_gram_form_vs_round1_kernel(dev, B, N, k):
-    """Three independent backward kernels of the fused stage: the dense split-product Gram form (the default), the f32 Gram form with the
-    register-indexed sparse part (MLSP_TNET_BWD_F32=1) and the round-1 kernel (three MFMA products on the dZ tile, MLSP_TNET_BWD_OLD=1);
-    the switches are read once per process, hence the subprocesses."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("cmp_tnet_bwd", os.path.join(os.path.dirname(__file__), "..", "tools", "cmp_tnet_bwd.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    for name, err in mod.compare(B, N, k).items():
-        assert err < 1e-4, (name, err)
+def test_tnet_backward_kernels_vs_float64(dev, B, N, k):
+    """The three backward kernels of the fused stage, each reached through the C ABI: the dense split-product Gram form
+    (tnet_edge_bwds_kernel, products on the bf16 cores), the f32 Gram form with the register-indexed sparse part (tnet_edge_bwdg_kernel,
+    mode "fp32": the same forward taken back with the other mode) and the round-1 kernel (tnet_edge_bwd_kernel, the path for slope <= 0:
+    the Gram forms recover the pre-activation from the activated value, which needs a bijection).  Each against the float64 gradients of
+    the reference's op sequence on the same inputs, with the max over k taking the slots the forward kernel chose; the two Gram forms
+    also against each other."""
+    from mlsp_amd import _lib
+    Fh = _fh()
+    P = B * N
+    g = torch.Generator().manual_seed(5)
+    # Dyadic coordinates and first weights: the first conv's outputs are multiples of 2^-12, exact in fp32 and float64, and beta1 puts
+    # BN1's zero half-way between two of them -- no first-layer pre-activation lies within 2^-13 of the kink (in units of the BN scale),
+    # far beyond fp32 rounding, so the LeakyReLU derivative of every edge is the same in both evaluations.
+    xp = torch.randint(-256, 257, (P, 3), generator=g).float() / 256
+    W1 = torch.randint(-16, 17, (64, 6), generator=g).float() / 16
+    W2 = torch.randn(128, 64, generator=g) / 8
+    g1, g2 = torch.rand(64, generator=g) + 0.5, torch.rand(128, generator=g) + 0.5
+    b2 = torch.randn(128, generator=g)
+    w = torch.randn(P, 128, generator=g)
+    idx = torch.from_numpy(knn_canon.knn_point_major(xp.view(B, N, 3), k).astype(np.int64))
+    y = F.conv2d(ref_torch_modules.edge_features(xp.double().view(B, N, 3).transpose(2, 1), k, lambda *_: idx), W1.double()[:, :, None, None])
+    mean, sc = y.mean((0, 2, 3)), g1.double() / torch.sqrt(y.var((0, 2, 3), unbiased=False) + 1e-5)
+    b1 = (sc * (mean - (torch.round(mean * 4096) + 0.5) / 4096)).float()
+    leaves0 = (xp, W1, g1, b1, W2, g2, b2)
+    names = ("dx", "dW1", "dg1", "db1", "dW2", "dg2", "db2")
+
+    def run(slope, bwd_mode=None):
+        leaves = [t.to(dev).requires_grad_(True) for t in leaves0]
+        graph = Fh.graph_from_indices(idx.to(dev), B, N, k)
+        rs = [torch.zeros(64, device=dev), torch.ones(64, device=dev), torch.zeros(128, device=dev), torch.ones(128, device=dev)]
+        with Fh.gemm_precision("f16x3"), Fh.recorded_selections() as rec:
+            out = Fh.tnet_edge(leaves[0], graph, leaves[1], leaves[2], leaves[3], rs[0], rs[1], leaves[4], leaves[5], leaves[6], rs[2], rs[3],
+                               True, slope=slope)
+        if bwd_mode is not None:
+            out.grad_fn.prec = _lib.GEMM_PRECISION_MODES[bwd_mode]    # (the Function hands its forward's mode to its backward: overridden here)
+        out.backward(w.to(dev))
+        return rec.sel[0], [t.grad.cpu().double() for t in leaves]
+
+    def truth(slope, sel):
+        leaves = [t.double().requires_grad_(True) for t in leaves0]
+        _tnet_edge_f64(*leaves[:1], idx, *leaves[1:], slope, sel.cpu()).backward(w.double())
+        return [t.grad for t in leaves]
+
+    def err(a, q):
+        return ((a - q).abs().max() / q.abs().max()).item()
+
+    sel, split = run(0.2)
+    sel_g, gram = run(0.2, "fp32")
+    assert torch.equal(sel, sel_g)
+    want = truth(0.2, sel)
+    sel0, old = run(0.0)
+    want0 = truth(0.0, sel0)
+    for i, name in enumerate(names):
+        assert err(split[i], gram[i]) < 1e-4, (name, "split vs f32 Gram form", err(split[i], gram[i]))
+        assert err(split[i], want[i]) < 1e-4, (name, "split Gram form", err(split[i], want[i]))
+        assert err(gram[i], want[i]) < 1e-4, (name, "f32 Gram form", err(gram[i], want[i]))
+        assert err(old[i], want0[i]) < 1e-4, (name, "round-1 kernel", err(old[i], want0[i]))
 
 
 @pytest.mark.parametrize("fused_stats", [False, True])
@@ -1449,18 +1509,28 @@ def test_gemm_split_layouts_agree_and_are_linear(dev):
         assert (lin.norm() / scale).item() < 1e-6
 
 
-def test_tnet_forward_accuracy_both_product_kernels(dev):
+def test_tnet_forward_kernels_vs_float64(dev):
     """The fused T-Net per-edge stage against a float64 evaluation of the reference's op sequence at (B=8, N=1024, k=20) and (4, 2048, 40):
-    relative L2 <= 4e-7 for the f32-MFMA kernel (MLSP_TNET_FWD_F32=1) and for the split-products kernel (MLSP_TNET_FWD_SPLIT=1; the default from
-    1024 tiles up, i.e. at both of these shapes).  The switches are read once per process, hence the subprocesses."""
-    import subprocess, sys
-    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-    for env_extra in ({"MLSP_TNET_FWD_F32": "1"}, {"MLSP_TNET_FWD_SPLIT": "1"}):
-        env = {k: v for k, v in os.environ.items() if k not in ("MLSP_TNET_FWD_F32", "MLSP_TNET_FWD_SPLIT")}
-        env.update(env_extra)
-        r = subprocess.run([sys.executable, os.path.join(root, "tools", "tnet_acc.py"), "--check"], env=env, capture_output=True, text=True, timeout=300)
-        print(env_extra, r.stdout.strip().splitlines()[-2:])
-        assert r.returncode == 0, (env_extra, r.stdout[-500:], r.stderr[-500:])
+    relative L2 <= 4e-7 for the f32-MFMA kernel (tnet_edge_fwd2_kernel, mode "fp32") and for the split-products kernel
+    (tnet_edge_fwd3_kernel, modes "bf16x6" and "f16x3")."""
+    Fh = _fh()
+    g = torch.Generator().manual_seed(1)
+    for B, N, k in ((8, 1024, 20), (4, 2048, 40)):
+        P = B * N
+        xp = torch.rand(P, 3, generator=g) * 2 - 1
+        W1, W2 = torch.randn(64, 6, generator=g) * 0.5, torch.randn(128, 64, generator=g) * 0.2
+        g1, b1 = torch.rand(64, generator=g) + 0.3, torch.randn(64, generator=g) * 0.1
+        g2, b2 = torch.rand(128, generator=g) + 0.3, torch.randn(128, generator=g) * 0.1
+        idx = torch.from_numpy(knn_canon.knn_point_major(xp.view(B, N, 3), k).astype(np.int64))
+        want = _tnet_edge_f64(xp.double(), idx, *(t.double() for t in (W1, g1, b1, W2, g2, b2)), 0.2)
+        graph = Fh.graph_from_indices(idx.to(dev), B, N, k)
+        for mode in ("fp32", "bf16x6", "f16x3"):
+            rs = [torch.zeros(64, device=dev), torch.ones(64, device=dev), torch.zeros(128, device=dev), torch.ones(128, device=dev)]
+            with Fh.gemm_precision(mode):
+                got = Fh.tnet_edge(xp.to(dev), graph, W1.to(dev), g1.to(dev), b1.to(dev), rs[0], rs[1], W2.to(dev), g2.to(dev), b2.to(dev),
+                                   rs[2], rs[3], True)
+            rel = ((got.double().cpu() - want).norm() / want.norm()).item()
+            assert rel <= 4e-7, (B, N, k, mode, rel)
 
 
 @pytest.mark.parametrize("Cm,Ci,Co", [(64, 6, 64), (64, 128, 64), (7, 3, 5), (130, 257, 33)])
