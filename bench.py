@@ -7,9 +7,13 @@ all-reduce of the flat 18.2 MB gradient bucket per step.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel
-(HIP-event timed inside the timed region through the library's profiling hook) and `cpu_baseline`
-(the CPU oracle restating the reference's op sequence, timed on this box's host cores, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline needs: set-up, warm-up,
+the timed steps, --dump-outputs, the line.  --full adds, after the timed steps and in the same process, everything else the line has
+carried: `roofline` / `roofline_kernels` / `executed_*` from HIP-event-profiled steps through the library's profiling hook, the launches
+counted by torch.profiler, the same step on the other GEMM product modes (`fp32_mfma`, `bf16x6_split`), the all-reduce alone (N > 1:
+`distributed`), `secondary` (configs[3], configs[4], the trainer-shaped step) and `cpu_baseline` (the CPU oracle restating the reference's
+op sequence, timed on this box's host cores); the last two at N=1 only.  --no-secondary / --no-cpu-baseline / --no-fp32-leg drop parts
+of a --full run.
 
 --steps K is the number of timed steps of the headline: K steps in all, one block by default (--repeats R: R blocks, the median
 block's time per step is `ms_per_step`), after --warmup steps and two untimed settle blocks of SETTLE_STEPS steps.  --dump-outputs DIR
@@ -711,9 +715,12 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="STRONG scaling: this many clouds in total, split over the ranks (SURVEY 8d config (2) secondary: 32). "
                          "Default 0 = weak scaling, 32 clouds per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] runs after the headline")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the comparison blocks with every GEMM on the f32 MFMA")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what is not the headline: roofline / per-kernel figures, counted launches, the "
+                         "other GEMM product modes, the all-reduce alone (N > 1), the secondary workloads and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs[3] / configs[4] / trainer-shaped runs")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="with --full: skip the comparison blocks on the other GEMM product modes")
     ap.add_argument("--stub", action="store_true", help="launcher self-test: gloo ranks, no GPU, no kernels (never a measurement)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32")
@@ -835,8 +842,42 @@ def main():
     dt, blocks, loss = median_leg()
     assert torch.isfinite(loss).item()
     dumped = dump_outputs(a.dump_outputs, model, loss, keep["logits"]) if keep is not None else None
+    pts = b_local * NPTS * n_gpus * a.steps
+    value = pts / dt
 
-    # HIP events around every launch of the priced kernel families: a separate, untimed block AFTER the timing
+    def headline():
+        """The fields of the line that need nothing but the timed blocks (rank 0)."""
+        out = {"metric": "points/sec fwd+bwd, DGCNN+MLSP B=32 N=1024 k=20", "value": value, "unit": "points/s",
+               "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
+               "blocks_ms_per_step": {"n": len(blocks), "steps": sizes, "median": 1e3 * dt / a.steps, "min": 1e3 * min(blocks),
+                                      "max": 1e3 * max(blocks), "untimed_settle_blocks": [round(1e3 * t, 3) for t in settle]},
+               "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "timing_note": "cyclic GC collected before and paused inside every timed block (timeit's convention)",
+               "config": {"workload": "DGCNN encoder + 3 MLSP heads + losses, fwd+bwd+Adam, B=%d/GPU N=1024 k=20 fp32 "
+                                      "(BASELINE.json configs[1]), dropout 0.5, BN train" % b_local,
+                          "global_batch": b_local * n_gpus, "points_per_cloud": NPTS, "k": K_NN,
+                          "parallelism": "dp%d" % n_gpus, "grad_allreduce": "1 x flat 18.2 MB fp32 per step (RCCL); no host-side exchange (presence='uniform', verified in-band)",
+                          "gemm_products": "%s (f16x3 = fp32 operands, scaled by a per-workgroup power of two, split into two f16 pieces (11 + 11 "
+                                           "bits), three piece products, fp32 accumulation; bf16x6 = three bf16 pieces, six piece products.  "
+                                           "Either way an fp32 computation: error vs float64 below the f32-MFMA chain's, tests/test_gpu_kernels.py::"
+                                           "test_gemm_split_bf16_accuracy holds both to the same bar; MLSP_GEMM_PRECISION=fp32 runs every GEMM on "
+                                           "the f32 MFMA, =bf16x6 on the six-product split)" % Fh.gemm_precision.current}}
+        out["reference_flop_equivalent_frac"] = value / n_gpus * FLOP_PER_POINT / 1e12 / PEAK_FP32_TFLOPS
+        out["full"] = a.full
+        return out
+
+    if not a.full:
+        # a plain run: the headline and nothing else (no further steps, no further GPU work)
+        if rank == 0:
+            out = headline()
+            if dumped is not None:
+                out["dump_outputs"] = dumped
+            print(json.dumps(out))
+        if distributed:
+            dist.destroy_process_group()
+        return
+
+    # --full from here on.  HIP events around every launch of the priced kernel families: a separate, untimed block AFTER the timing
     prof_steps = 3
     rows, prof, prof_dt = profiled_steps(lib, one_step, prof_steps)
 
@@ -890,23 +931,7 @@ def main():
                 x6_leg, x6_blocks, _ = median_leg()
 
     if rank == 0:
-        pts = b_local * NPTS * n_gpus * a.steps
-        value = pts / dt
-        out = {"metric": "points/sec fwd+bwd, DGCNN+MLSP B=32 N=1024 k=20", "value": value, "unit": "points/s",
-               "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-               "blocks_ms_per_step": {"n": len(blocks), "steps": sizes, "median": 1e3 * dt / a.steps, "min": 1e3 * min(blocks),
-                                      "max": 1e3 * max(blocks), "untimed_settle_blocks": [round(1e3 * t, 3) for t in settle]},
-               "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "timing_note": "cyclic GC collected before and paused inside every timed block (timeit's convention)",
-               "config": {"workload": "DGCNN encoder + 3 MLSP heads + losses, fwd+bwd+Adam, B=%d/GPU N=1024 k=20 fp32 "
-                                      "(BASELINE.json configs[1]), dropout 0.5, BN train" % b_local,
-                          "global_batch": b_local * n_gpus, "points_per_cloud": NPTS, "k": K_NN,
-                          "parallelism": "dp%d" % n_gpus, "grad_allreduce": "1 x flat 18.2 MB fp32 per step (RCCL); no host-side exchange (presence='uniform', verified in-band)",
-                          "gemm_products": "%s (f16x3 = fp32 operands, scaled by a per-workgroup power of two, split into two f16 pieces (11 + 11 "
-                                           "bits), three piece products, fp32 accumulation; bf16x6 = three bf16 pieces, six piece products.  "
-                                           "Either way an fp32 computation: error vs float64 below the f32-MFMA chain's, tests/test_gpu_kernels.py::"
-                                           "test_gemm_split_bf16_accuracy holds both to the same bar; MLSP_GEMM_PRECISION=fp32 runs every GEMM on "
-                                           "the f32 MFMA, =bf16x6 on the six-product split)" % Fh.gemm_precision.current}}
+        out = headline()
         if x6_leg is not None:
             out["bf16x6_split"] = {"ms_per_step": 1e3 * x6_leg / a.steps, "value": pts / x6_leg,
                                    "note": "the same step with the GEMM family on the six-product bf16 split (gemm_precision('bf16x6'), the "
@@ -1027,7 +1052,6 @@ def main():
         out["executed_mfma_frac"] = out["executed_tflops"] / PEAK_FP32_TFLOPS
         half_ = getattr(profiled_steps, "split_half", [0.0, 0.0, 0.0, 0.0]) if prof and prof[1] > 0 else [0.0, 0.0, 0.0, 0.0]
         out["executed_16bit_tflops"] = (6 * (split_flop - half_[2] / prof_steps) + 3 * half_[2] / prof_steps) / step_s / 1e12   # the split GEMMs' piece products
-        out["reference_flop_equivalent_frac"] = value / n_gpus * FLOP_PER_POINT / 1e12 / PEAK_FP32_TFLOPS
         if counted and "launches_per_step" in counted:
             out["launches_per_step"] = counted["launches_per_step"]
             out["launches_under_8us_per_step"] = counted["launches_under_8us_per_step"]

@@ -540,10 +540,15 @@ def test_pointmlp_fwd_bwd(dev, M, Cin, Cout, act, use_bias, G, training):
     rm, rv = _rand((Cout,), 7) * 0.1, _rand((Cout,), 8).abs() + 0.5
     dZ = _rand((M, Cout), 9)
 
-    rm_c, rv_c = rm.clone(), rv.clone()
-    Zc = _torch_pointmlp(X, W, bias, gbias, rpg, gamma, beta, rm_c if has_bn else None, rv_c if has_bn else None, training, act)
-    Zc.backward(dZ)
-    leaves = [t for t in (X, W, bias, gbias, gamma, beta) if t is not None]
+    # the reference runs in float64: torch's fp32 CPU BatchNorm backward of the 196608-row case is 6 % (16 threads) to 12 % (one
+    # thread) of max|dX| away from the exact gradient, more than the bar below, and how far depends on the host's thread count
+    def c(t):
+        return t.detach().double().requires_grad_(True) if t is not None else None
+    Xc, Wc, bc, gbc, gc_, betac = c(X), c(W), c(bias), c(gbias), c(gamma), c(beta)
+    rm_c, rv_c = rm.double(), rv.double()
+    Zc = _torch_pointmlp(Xc, Wc, bc, gbc, rpg, gc_, betac, rm_c if has_bn else None, rv_c if has_bn else None, training, act)
+    Zc.backward(dZ.double())
+    leaves = [t for t in (Xc, Wc, bc, gbc, gc_, betac) if t is not None]
     want = [t.grad.clone() for t in leaves]
 
     def d(t):

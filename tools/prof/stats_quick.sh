@@ -4,6 +4,6 @@ TAG=${1:-q}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-fp32-leg > "$OUT/stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-fp32-leg > "$OUT/stats.log" 2>&1
 find "$OUT" -name "*_kernel_trace.csv" -delete
 ls "$OUT/stats" | head -3
