@@ -152,11 +152,13 @@ __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __res
         for (int e = 0; e < 4; ++e) { best[e] = use_max[e] ? -INFINITY : INFINITY; bs[e] = 255; }
         // one coalesced load of the point's index row, then every neighbour row address comes from a lane shuffle:
         // the k row gathers are independent and issue back-to-back instead of chaining index -> row per neighbour
-        const int jv = lane < k ? base + irow[lane] : base;
+        // (k > 64: one load per 64 slots -- NP divides 64, so the lanes of an iteration read the same load)
+        int jv = base;
         for (int s0 = 0; s0 < k; s0 += NP) {            // wave-uniform trip count: every lane takes part in the shuffle
+            if ((s0 & 63) == 0) jv = s0 + lane < k ? base + irow[s0 + lane] : base;
             const int s = s0 + sub;
             const bool ok = s < k;
-            const int j = __shfl(jv, ok ? s : 0, 64);
+            const int j = __shfl(jv, ok ? (s & 63) : 0, 64);
             const f32x4 u = *(const f32x4*)(uv + (size_t)j * ld + c);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -205,8 +207,8 @@ __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __res
     }
 }
 
-// LDS-resident form (whole clouds, N <= 4096, k <= 32, Cout % 16 == 0): a workgroup owns one (cloud, 16-channel slice,
-// point chunk).  The slice of u for the WHOLE cloud (N x 16 floats, 64 KB at N = 1024) and the chunk's neighbour lists
+// LDS-resident form (whole clouds, N <= 4096, k <= 40, Cout % 8 == 0): a workgroup owns one (cloud, ELDS_CS-channel slice,
+// point chunk).  The slice of u for the WHOLE cloud (N x ELDS_CS floats, 32 KB at N = 1024) and the chunk's neighbour lists
 // (u16) are staged in LDS once; the k row gathers of every point then run at LDS rate instead of one L2 round trip per
 // neighbour row.  A thread owns (point, channel quad) and walks its k neighbours in slot order, so the first-occurrence
 // rule needs no cross-lane merge.  Partial BN statistics: one fp64 row per (cloud, chunk), each slice writes its columns.
