@@ -487,6 +487,15 @@ int mlsp_profile_split_kinds(double* out);
 int mlsp_adam_flat_f32(float* P, float* M, float* V, const uint32_t* off, const uint32_t* numel, const float* const* grads, int nseg, double lr,
                        double beta1, double beta2, double weight_decay, double eps, int64_t step, float* step_out, float* tile_amax,
                        mlsp_stream_t stream);
+/* SGD step (torch.optim.SGD: PointDA/trainer.py:258-259, PointDA/train_spst.py, PointSegDA/trainer.py:212-214 with --optimizer SGD) over the flat
+ * parameter buffer P and momentum buffer B in ONE launch; segments, gradients, tiles and tile_amax as mlsp_adam_flat_f32.  B (16-byte
+ * aligned) may be NULL when momentum == 0.  first != 0: B is initialised with the (decayed) gradient instead of updated -- torch's first step.
+ * The element-wise arithmetic restates torch's default multi-tensor SGD (torch/optim/sgd.py _multi_tensor_sgd) type by type: maximize
+ * negates the gradient, then g += (float)weight_decay * p, buf = buf * (float)momentum + (float)(1 - dampening) * g, g = nesterov ? g +
+ * (float)momentum * buf : buf, p += (float)(-lr) * g, every `a + alpha * b` one fma as in torch's ROCm build. */
+int mlsp_sgd_flat_f32(float* P, float* B, const uint32_t* off, const uint32_t* numel, const float* const* grads, int nseg, double lr,
+                      double momentum, double dampening, double weight_decay, int nesterov, int maximize, int first, float* tile_amax,
+                      mlsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ _D, _I64 = _c.c_double, _c.c_int64
 SIGNATURES = {
     "mlsp_abi_version": [],
     "mlsp_adam_flat_f32": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I64, _P, _P, _P],
+    "mlsp_sgd_flat_f32": [_P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _I, _I, _I, _P, _P],
     "mlsp_strerror": [_I],
     "mlsp_workspace_bytes": [_I, _I, _I],
     "mlsp_knn_f32": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P],
@@ -120,7 +121,7 @@ class Bound(_c.Structure):
 
 
 # Sources of ready-made bounds for weight operands (objects with .weight_bounds(tensor) -> (device pointer, n) | None): mlsp_amd.optim.FlatAdam
-# registers itself -- its step kernel leaves the per-tile maxima of the parameters it just updated (functional._weight_bounds asks them).
+# and FlatSGD register themselves -- their step kernel leaves the per-tile maxima of the parameters it just updated (functional._weight_bounds asks them).
 import weakref as _weakref
 weight_bound_providers = _weakref.WeakSet()
 

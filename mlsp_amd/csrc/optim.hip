@@ -1,4 +1,4 @@
-// Adam step of the hot path (PointDA/trainer.py:258-259: optim.Adam(model.parameters(), lr, weight_decay), stepped at :571) over FLAT
+// Optimizer steps of the hot path.  Adam (PointDA/trainer.py:258-259: optim.Adam(model.parameters(), lr, weight_decay), stepped at :571) over FLAT
 // parameter / moment buffers in one launch.
 //
 // torch's fused Adam hands every workgroup one 64 Ki-element chunk of one tensor: 4.55 M parameters are 70-odd mostly full chunks plus 77
@@ -18,19 +18,23 @@
 // elements: this one differs in 0 elements of param / exp_avg / exp_avg_sq, the uncontracted form in 16,285 exp_avg values;
 // profiles/r5_adam_lowering_probe.txt).  This file is compiled with -ffp-contract=off, so the fmas are written out.
 // tests/test_gpu_optim.py asserts bit-identity with torch.optim.Adam(fused=True) step by step.
+//
+// SGD step (the trainers' --optimizer SGD) over a flat parameter buffer and a flat momentum buffer: the same tiles, segment lookup, gradient
+// table and tile_amax epilogue (flat_step_tile, templated on the per-element update), the arithmetic of torch's default multi-tensor SGD
+// (SgdUpdate below).  tests/test_gpu_optim_sgd.py asserts bit-identity with torch.optim.SGD step by step.
 #include "common.h"
 #include "../../include/mlsp_hip.h"
 #include <math.h>
 
-#define ADAM_MAX_SEGS 96
-#define ADAM_TILE 2048            // elements per workgroup (256 threads x 2 quads)
+#define FLAT_MAX_SEGS 96
+#define FLAT_TILE 2048            // elements per workgroup (256 threads x 2 quads)
 
-struct AdamSegs {
+struct FlatSegs {
     int n;
-    int tile_begin[ADAM_MAX_SEGS + 1];      // first tile of every segment; [n] = total
-    unsigned off[ADAM_MAX_SEGS];            // first element of the segment in the flat buffers (a multiple of 4 takes the 16-byte path)
-    unsigned numel[ADAM_MAX_SEGS];
-    const float* grad[ADAM_MAX_SEGS];       // the segment's gradient, contiguous
+    int tile_begin[FLAT_MAX_SEGS + 1];      // first tile of every segment; [n] = total
+    unsigned off[FLAT_MAX_SEGS];            // first element of the segment in the flat buffers (a multiple of 4 takes the 16-byte path)
+    unsigned numel[FLAT_MAX_SEGS];
+    const float* grad[FLAT_MAX_SEGS];       // the segment's gradient, contiguous
 };
 
 __device__ __forceinline__ void adam_one(float& param, float grad, float& ea, float& es, double lr, double b1, double b2, double wd, double eps,
@@ -43,47 +47,115 @@ __device__ __forceinline__ void adam_one(float& param, float grad, float& ea, fl
     param -= step_size * ea / denom;
 }
 
-__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, AdamSegs s, double lr,
-                                                        double b1, double b2, double wd, double eps, float bc1, float bc2s, float step,
-                                                        float* __restrict__ step_out, float* __restrict__ tile_amax) {
+// The per-element update of one optimizer over the flat buffers: one4 updates four parameters at flat element k (16-byte aligned) with
+// their gradients, one1 a single parameter; both read and write the optimizer's own state streams at the same element.
+struct AdamUpdate {
+    float* M;                 // exp_avg
+    float* V;                 // exp_avg_sq
+    double lr, b1, b2, wd, eps;
+    float bc1, bc2s, step;
+    float* step_out;          // nullable: the optimizer's device-side step counter (state_dict)
+    __device__ __forceinline__ void begin(int tile) const {
+        if (tile == 0 && threadIdx.x == 0 && step_out) *step_out = step;
+    }
+    __device__ __forceinline__ void one4(f32x4& pp, const f32x4& gg, unsigned k) const {
+        f32x4 mm = *(const f32x4*)(M + k), vv = *(const f32x4*)(V + k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float p1 = pp[e], m1 = mm[e], v1 = vv[e];
+            adam_one(p1, gg[e], m1, v1, lr, b1, b2, wd, eps, bc1, bc2s);
+            pp[e] = p1; mm[e] = m1; vv[e] = v1;
+        }
+        *(f32x4*)(M + k) = mm; *(f32x4*)(V + k) = vv;
+    }
+    __device__ __forceinline__ void one1(float& pp, float g, unsigned k) const {
+        float mm = M[k], vv = V[k];
+        adam_one(pp, g, mm, vv, lr, b1, b2, wd, eps, bc1, bc2s);
+        M[k] = mm; V[k] = vv;
+    }
+};
+
+// torch.optim.SGD's default path on GPU tensors (torch/optim/sgd.py _multi_tensor_sgd) restated type by type: each foreach op rounds its
+// float result, every scalar reaches it as a float alpha, and each `a + alpha * b` of torch's ROCm build is one fma (tools/sgd_probe,
+// profiles/sgd_lowering_probe.txt).
+struct SgdUpdate {
+    float* B;                 // momentum_buffer (unused when !mom_on)
+    float wd, mom, damp1, neg_lr;      // (float)weight_decay, (float)momentum, (float)(1 - dampening), (float)(-lr)
+    int wd_on, mom_on, nesterov, maximize, first;
+    __device__ __forceinline__ void begin(int) const {}
+    __device__ __forceinline__ float grad(float param, float g) const {
+        if (maximize) g = -g;                                   // _foreach_neg(grads)
+        if (wd_on) g = fmaf(wd, param, g);                      // _foreach_add(grads, params, alpha=weight_decay)
+        return g;
+    }
+    __device__ __forceinline__ float with_momentum(float g, float& buf) const {
+        buf = first ? g : fmaf(damp1, g, buf * mom);           // clone(grad) | _foreach_mul_(bufs, momentum); _foreach_add_(bufs, grads, alpha=1 - dampening)
+        return nesterov ? fmaf(mom, buf, g) : buf;              // _foreach_add_(grads, bufs, alpha=momentum) | grads = bufs
+    }
+    __device__ __forceinline__ void one4(f32x4& pp, const f32x4& gg, unsigned k) const {
+        if (mom_on) {
+            f32x4 bb = first ? f32x4{} : *(const f32x4*)(B + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float b1 = bb[e];
+                const float d = with_momentum(grad(pp[e], gg[e]), b1);
+                bb[e] = b1;
+                pp[e] = fmaf(neg_lr, d, pp[e]);                 // _foreach_add_(params, grads, alpha=-lr)
+            }
+            *(f32x4*)(B + k) = bb;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[e] = fmaf(neg_lr, grad(pp[e], gg[e]), pp[e]);
+        }
+    }
+    __device__ __forceinline__ void one1(float& pp, float g, unsigned k) const {
+        float d = grad(pp, g);
+        if (mom_on) {
+            float b1 = first ? 0.f : B[k];
+            d = with_momentum(d, b1);
+            B[k] = b1;
+        }
+        pp = fmaf(neg_lr, d, pp);
+    }
+};
+
+// One 2048-element tile of the flat parameter buffer P per workgroup, whatever the optimizer: find the segment that owns the tile, update
+// its parameters (16 bytes per lane where the segment's offset and gradient allow), and leave the tile's largest updated magnitude.
+template <class Update>
+__device__ __forceinline__ void flat_step_tile(float* __restrict__ P, const FlatSegs& s, const Update& up, float* __restrict__ tile_amax) {
     // tile_amax (nullable, [gridDim.x]): max |updated parameter| of this workgroup's tile -- a by-product for the GEMMs that read the
     // parameters next (the two-piece f16 products scale every operand by a bound of its magnitude: include/mlsp_hip.h mlsp_bound_t)
     float pmx = 0.f;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && step_out) *step_out = step;     // the optimizer's device-side step counter (state_dict)
+    const int t = blockIdx.x;
+    up.begin(t);
     // which segment owns this tile: binary search over <= 96 tile offsets in the kernel arguments
     int lo = 0, hi = s.n - 1;
-    const int t = blockIdx.x;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (s.tile_begin[mid] <= t) lo = mid; else hi = mid - 1;
     }
     const unsigned n = s.numel[lo];
-    const unsigned e0 = (unsigned)(t - s.tile_begin[lo]) * ADAM_TILE;
+    const unsigned base = s.off[lo];
+    const unsigned e0 = (unsigned)(t - s.tile_begin[lo]) * FLAT_TILE;
     const float* __restrict__ g = s.grad[lo];
-    float* p = P + s.off[lo];
-    float* m = M + s.off[lo];
-    float* v = V + s.off[lo];
-    const bool gvec = (((uintptr_t)g) & 15) == 0 && (s.off[lo] & 3) == 0;      // 16-byte accesses on all four streams
+    float* p = P + base;
+    const bool gvec = (((uintptr_t)g) & 15) == 0 && (base & 3) == 0;      // 16-byte accesses on every stream
 #pragma unroll
-    for (int u = 0; u < ADAM_TILE / 1024; ++u) {
+    for (int u = 0; u < FLAT_TILE / 1024; ++u) {
         const unsigned i = e0 + u * 1024 + threadIdx.x * 4;
         if (i >= n) break;
         if (i + 4 <= n && gvec) {
-            f32x4 pp = *(const f32x4*)(p + i), mm = *(const f32x4*)(m + i), vv = *(const f32x4*)(v + i);
+            f32x4 pp = *(const f32x4*)(p + i);
             const f32x4 gg = *(const f32x4*)(g + i);
+            up.one4(pp, gg, base + i);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float p1 = pp[e], m1 = mm[e], v1 = vv[e];
-                adam_one(p1, gg[e], m1, v1, lr, b1, b2, wd, eps, bc1, bc2s);
-                pp[e] = p1; mm[e] = m1; vv[e] = v1;
-                pmx = fmaxf(pmx, fabsf(p1));
-            }
-            *(f32x4*)(p + i) = pp; *(f32x4*)(m + i) = mm; *(f32x4*)(v + i) = vv;
+            for (int e = 0; e < 4; ++e) pmx = fmaxf(pmx, fabsf(pp[e]));
+            *(f32x4*)(p + i) = pp;
         } else {
             for (unsigned j = i; j < n && j < i + 4; ++j) {
-                float pp = p[j], mm = m[j], vv = v[j];
-                adam_one(pp, g[j], mm, vv, lr, b1, b2, wd, eps, bc1, bc2s);
-                p[j] = pp; m[j] = mm; v[j] = vv;
+                float pp = p[j];
+                up.one1(pp, g[j], base + j);
+                p[j] = pp;
                 pmx = fmaxf(pmx, fabsf(pp));
             }
         }
@@ -96,6 +168,37 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ P, f
         __syncthreads();
         if (threadIdx.x == 0) tile_amax[t] = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
     }
+}
+
+// (one named kernel per optimizer: the names are what kernel traces show)
+__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ P, FlatSegs s, AdamUpdate up, float* __restrict__ tile_amax) {
+    flat_step_tile(P, s, up, tile_amax);
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ P, FlatSegs s, SgdUpdate up, float* __restrict__ tile_amax) {
+    flat_step_tile(P, s, up, tile_amax);
+}
+
+// Launch `kernel` over nseg segments in groups of 96, tiles numbered segment by segment across the groups (tile_amax).
+template <class Update>
+static int flat_launch(void (*kernel)(float*, FlatSegs, Update, float*), float* P, const uint32_t* off, const uint32_t* numel,
+                       const float* const* grads, int nseg, const Update& up, float* tile_amax, mlsp_stream_t st) {
+    size_t tile_base = 0;
+    for (int s0 = 0; s0 < nseg; s0 += FLAT_MAX_SEGS) {
+        FlatSegs a;
+        a.n = nseg - s0 < FLAT_MAX_SEGS ? nseg - s0 : FLAT_MAX_SEGS;
+        int tiles = 0;
+        for (int i = 0; i < a.n; ++i) {
+            if (!grads[s0 + i] || numel[s0 + i] == 0) return MLSP_ERR_ARG;
+            a.tile_begin[i] = tiles;
+            a.off[i] = off[s0 + i]; a.numel[i] = numel[s0 + i]; a.grad[i] = grads[s0 + i];
+            tiles += (int)((numel[s0 + i] + FLAT_TILE - 1) / FLAT_TILE);
+        }
+        a.tile_begin[a.n] = tiles;
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), 0, st, P, a, up, tile_amax ? tile_amax + tile_base : (float*)nullptr);
+        tile_base += tiles;
+    }
+    return mlsp_launch_status();
 }
 
 extern "C" {
@@ -114,23 +217,23 @@ int mlsp_adam_flat_f32(float* P, float* M, float* V, const uint32_t* off, const 
     // (as the reference kernel: pow in double, the corrections handed on as floats)
     const float bc1 = (float)(1.0 - pow(beta1, (double)(float)step));
     const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)(float)step));
-    size_t tile_base = 0;
-    for (int s0 = 0; s0 < nseg; s0 += ADAM_MAX_SEGS) {
-        AdamSegs a;
-        a.n = nseg - s0 < ADAM_MAX_SEGS ? nseg - s0 : ADAM_MAX_SEGS;
-        int tiles = 0;
-        for (int i = 0; i < a.n; ++i) {
-            if (!grads[s0 + i] || numel[s0 + i] == 0) return MLSP_ERR_ARG;
-            a.tile_begin[i] = tiles;
-            a.off[i] = off[s0 + i]; a.numel[i] = numel[s0 + i]; a.grad[i] = grads[s0 + i];
-            tiles += (int)((numel[s0 + i] + ADAM_TILE - 1) / ADAM_TILE);
-        }
-        a.tile_begin[a.n] = tiles;
-        hipLaunchKernelGGL(adam_flat_kernel, dim3(tiles), dim3(256), 0, st, P, M, V, a, lr, beta1, beta2, weight_decay, eps, bc1, bc2s, (float)step,
-                           s0 == 0 ? step_out : (float*)nullptr, tile_amax ? tile_amax + tile_base : (float*)nullptr);
-        tile_base += tiles;
-    }
-    return mlsp_launch_status();
+    // (every group of 96 segments writes step_out: the same value)
+    const AdamUpdate up{M, V, lr, beta1, beta2, weight_decay, eps, bc1, bc2s, (float)step, step_out};
+    return flat_launch(adam_flat_kernel, P, off, numel, grads, nseg, up, tile_amax, st);
+}
+
+// One SGD step (torch.optim.SGD; PointDA/trainer.py:258-259 with --optimizer SGD) over the flat parameter buffer P and momentum buffer B
+// (nullable when momentum == 0), segments and gradients as mlsp_adam_flat_f32.  first != 0: B is initialised with the gradient (torch's
+// first step, where momentum_buffer is a clone) instead of updated.
+int mlsp_sgd_flat_f32(float* P, float* B, const uint32_t* off, const uint32_t* numel, const float* const* grads, int nseg, double lr,
+                      double momentum, double dampening, double weight_decay, int nesterov, int maximize, int first, float* tile_amax,
+                      mlsp_stream_t st) {
+    if (!P || !off || !numel || !grads || nseg <= 0) return MLSP_ERR_ARG;
+    if ((((uintptr_t)P | (uintptr_t)B) & 15) != 0 || (momentum != 0.0 && !B)) return MLSP_ERR_ARG;
+    // (the tests and the alphas as Python forms them: in double, then handed to the foreach ops, which take them as floats)
+    const SgdUpdate up{B, (float)weight_decay, (float)momentum, (float)(1.0 - dampening), (float)(-lr), weight_decay != 0.0, momentum != 0.0,
+                       nesterov != 0, maximize != 0, first != 0};
+    return flat_launch(sgd_flat_kernel, P, off, numel, grads, nseg, up, tile_amax, st);
 }
 
 }  // extern "C"

@@ -22,6 +22,10 @@ parameter `step` / `exp_avg` / `exp_avg_sq` entries (views of the flat moments).
 parameters on one device and the SAME set of parameters holding gradients at every step (they share one step counter); anything else --
 several groups, amsgrad / maximize, a parameter set that changes between steps -- falls back to torch's own per-tensor path for good, on
 the same storage, with the state carried over.
+
+FlatSGD does the same for torch.optim.SGD (the trainers' `--optimizer SGD`): parameters and momentum buffer in flat buffers, ONE launch of
+`mlsp_sgd_flat_f32`, bit-identical to torch's default multi-tensor SGD (tests/test_gpu_optim_sgd.py).  The layout, the fixed set of stepped
+parameters, the rebuild, the hand-over to torch and the published weight bounds are one piece of code for both (_FlatStep).
 """
 import ctypes
 
@@ -81,33 +85,47 @@ def storage_unit_offsets(params, align):
     return offs, (n + align - 1) // align * align
 
 
-class FlatAdam(torch.optim.Adam):
+class _FlatStep:
+    """The flat-buffer machinery FlatAdam and FlatSGD share (mixed in front of their torch optimizer): the storage-unit layout, the fixed
+    set of parameters that step, the rebuild when parameters left the buffer, the hand-over to torch's own path for good, and the tile
+    maxima the step kernel leaves (weight_bounds).  A subclass supplies
+
+      _eligible()                      whether the flat step covers the options / parameters / gradients of this step
+      _state_fits(ps, active)          whether the existing optimizer state can move into flat buffers
+      _adopt_state(ps, active, offs, n, dev) -> dict    its flat state buffers (existing state copied in), merged into the layout
+      _flat_fits(f)                    whether a built layout still serves the current options (else: torch's path from now on)
+      _launch(f, grp, grads, n)        the one launch (grads: ctypes array of n gradient pointers, in the order of the active segments)
+      _LEAVE_MSG                       the warning when the one-launch step is given up ("%s": why)
+    """
     ALIGN = 64
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        params = list(params)
-        on_gpu = any(isinstance(p, torch.Tensor) and p.is_cuda for p in params) or any(
-            isinstance(g, dict) and any(p.is_cuda for p in g["params"]) for g in params)
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fused=on_gpu)
+    def _flat_init(self):
         self._flat = None              # the flat buffers and their layout once built (dict)
         self._active = None            # indices (into the trainable parameter list) of the parameters that step, fixed at the first step
         self._disabled = False         # True: torch's per-tensor path from now on
         self.flat_steps = 0            # steps taken on the flat path (tests)
         self.layouts_built = 0         # (tests: a rebuild happens only when parameters left the buffer)
 
-    def _eligible(self):
+    def _flat_params_ok(self):
+        """one parameter group of dense fp32 parameters on one GPU"""
         if self._disabled or len(self.param_groups) != 1:
             return False
-        g = self.param_groups[0]
-        if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or not g.get("fused"):
-            return False
-        ps = g["params"]
+        ps = self.param_groups[0]["params"]
         dev = ps[0].device
         return all(p.dtype == torch.float32 and p.device == dev and p.is_cuda and not p.is_sparse for p in ps)
 
+    def _state_fits(self, ps, active):
+        return True
+
+    def _flat_fits(self, f):
+        return True
+
+    def _on_leave(self, f):
+        pass
+
     def _build(self):
-        """Lay the trainable parameters out (storage units, see the module docstring), move them and whatever Adam state exists into
-        fresh flat buffers.  None: the existing state does not fit one shared step counter."""
+        """Lay the trainable parameters out (storage units, see the module docstring), move them and whatever optimizer state exists into
+        fresh flat buffers.  None: the existing state does not fit the flat step."""
         ps = [p for p in self.param_groups[0]["params"] if p.requires_grad]
         dev = ps[0].device
         lay = storage_unit_offsets(ps, self.ALIGN)
@@ -118,26 +136,14 @@ class FlatAdam(torch.optim.Adam):
         # (segments -- and with them the step kernel's tiles -- in ADDRESS order: parameters that one GEMM reads as a single operand, adjacent
         # in the buffer but not in model.parameters(), then own one contiguous run of tile maxima: weight_bounds)
         active = sorted(active, key=lambda i: offs[i])
-        steps = {float(self.state[ps[i]]["step"]) for i in active if ps[i] in self.state and "step" in self.state[ps[i]]}
-        have = [i for i in active if ps[i] in self.state and "exp_avg" in self.state[ps[i]]]
-        if len(steps) > 1 or (have and len(have) != len(active)) or any(p in self.state and self.state[p] for i, p in enumerate(ps) if i not in active):
+        if not self._state_fits(ps, active):
             return None
         flat_p = torch.zeros(n, dtype=torch.float32, device=dev)
-        flat_m = torch.zeros(n, dtype=torch.float32, device=dev)
-        flat_v = torch.zeros(n, dtype=torch.float32, device=dev)
         views = [flat_p[o:o + p.numel()].view_as(p) for o, p in zip(offs, ps)]
         torch._foreach_copy_(views, [p.data for p in ps])
         for p, v in zip(ps, views):
             p.data = v                                    # the model now lives in the flat buffer (load_state_dict copies into it)
-        step = torch.full((), steps.pop() if steps else 0.0, dtype=torch.float32, device=dev)
-        host_step = int(round(float(step)))
-        for i in active:
-            p, o = ps[i], offs[i]
-            m, v = flat_m[o:o + p.numel()].view_as(p), flat_v[o:o + p.numel()].view_as(p)
-            if i in have:
-                m.copy_(self.state[p]["exp_avg"])
-                v.copy_(self.state[p]["exp_avg_sq"])
-            self.state[p] = {"step": step, "exp_avg": m, "exp_avg_sq": v}
+        extra = self._adopt_state(ps, active, offs, n, dev)
         self._active = active
         self.layouts_built += 1
         n_act = len(active)
@@ -148,20 +154,19 @@ class FlatAdam(torch.optim.Adam):
             tile_begin.append(t)
             t += (ps[i].numel() + 2047) // 2048
         tile_begin.append(t)
-        return {"params": ps, "offs": offs, "p": flat_p, "m": flat_m, "v": flat_v, "step": step, "host_step": host_step, "seg": seg,
-                "tile_amax": torch.zeros(t, dtype=torch.float32, device=dev), "tile_begin": tile_begin, "amax_versions": None, "amax_map": {}}
+        f = {"params": ps, "offs": offs, "p": flat_p, "seg": seg, "tile_amax": torch.zeros(t, dtype=torch.float32, device=dev),
+             "tile_begin": tile_begin, "amax_versions": None, "amax_map": {}}
+        f.update(extra)
+        return f
 
     def _leave_flat(self, why=None):
-        """torch's per-tensor path from now on (same storage): every stepped parameter gets its own step counter.  `why`: warn once --
-        the results are the same, the one-launch step is lost."""
+        """torch's own path from now on (same storage, the state carried over).  `why`: warn once -- the results are the same, the
+        one-launch step is lost."""
         if why and not self._disabled:
             import warnings
-            warnings.warn("FlatAdam: leaving the one-launch flat step for torch's per-tensor fused Adam (%s); same results, but the "
-                          "optimizer step takes ~5 launches / ~0.1 ms instead of 1 / ~0.02 ms from now on" % why, RuntimeWarning, stacklevel=3)
+            warnings.warn(self._LEAVE_MSG % why, RuntimeWarning, stacklevel=3)
         if self._flat is not None:
-            for i in self._active:
-                st = self.state[self._flat["params"][i]]
-                st["step"] = st["step"].clone()
+            self._on_leave(self._flat)
         self._flat, self._disabled = None, True
 
     # ---- the step -------------------------------------------------------------------------------------------------------------
@@ -171,14 +176,14 @@ class FlatAdam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if not self._eligible():
+        if not self._eligible() or (self._flat is not None and not self._flat_fits(self._flat)):
             if self._flat is not None:
                 self._leave_flat("the parameter groups / options are no longer the ones the flat step covers")
             super().step()
             return loss
         if self._flat is None:
             self._flat = self._build()
-            if self._flat is None:                        # loaded state that does not fit one shared step counter
+            if self._flat is None:                        # loaded state that does not fit the flat step
                 self._disabled = True
                 super().step()
                 return loss
@@ -193,23 +198,18 @@ class FlatAdam(torch.optim.Adam):
         base, offs = f["p"].data_ptr(), f["offs"]
         if any(p.data_ptr() != base + 4 * offs[i] for i, p in enumerate(ps)):
             # parameters left the buffer (module.to(), a rehome_adjacent of a head that ran for the first time): lay them out again
-            # around their new storages, moments and step counter carried over
+            # around their new storages, optimizer state carried over
             f = self._flat = self._build()
             if f is None:
                 self._disabled = True
                 super().step()
                 return loss
             ps, act = f["params"], self._active            # (the rebuild orders the segments by their NEW addresses)
-        grp = self.param_groups[0]
-        b1, b2 = grp["betas"]
         # one launch; every gradient is read where autograd (or the exchange's bucket) left it
         grads = [ps[i].grad if ps[i].grad.is_contiguous() else ps[i].grad.contiguous() for i in act]
         n = len(act)
-        f["host_step"] += 1
         gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads])
-        _lib.check(_lib.load().mlsp_adam_flat_f32(f["p"].data_ptr(), f["m"].data_ptr(), f["v"].data_ptr(), f["seg"][0], f["seg"][1], gp, n,
-                                                  float(grp["lr"]), float(b1), float(b2), float(grp["weight_decay"]), float(grp["eps"]),
-                                                  f["host_step"], f["step"].data_ptr(), f["tile_amax"].data_ptr(), _lib.stream()), "mlsp_adam_flat_f32")
+        self._launch(f, self.param_groups[0], gp, n)
         # the kernel left the magnitude of every updated parameter tile: valid for as long as nobody else writes the parameters (an
         # in-place torch operation bumps the tensor's version counter -- the raw update above does not)
         f["amax_versions"] = [ps[i]._version for i in act]
@@ -261,10 +261,126 @@ class FlatAdam(torch.optim.Adam):
         return f["tile_amax"].data_ptr() + 4 * t0, t1 - t0
 
     def load_state_dict(self, state_dict):
-        # loaded moments are fresh tensors: rebuild the flat buffers from them at the next step (parameters stay where they are)
+        # loaded state holds fresh tensors: rebuild the flat buffers from them at the next step (parameters stay where they are)
         if self._flat is not None:
             self._leave_flat()
             self._disabled = False
         super().load_state_dict(state_dict)
         self._flat = None
         self._active = None
+
+
+class FlatAdam(_FlatStep, torch.optim.Adam):
+    _LEAVE_MSG = ("FlatAdam: leaving the one-launch flat step for torch's per-tensor fused Adam (%s); same results, but the "
+                  "optimizer step takes ~5 launches / ~0.1 ms instead of 1 / ~0.02 ms from now on")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        params = list(params)
+        on_gpu = any(isinstance(p, torch.Tensor) and p.is_cuda for p in params) or any(
+            isinstance(g, dict) and any(p.is_cuda for p in g["params"]) for g in params)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fused=on_gpu)
+        self._flat_init()
+
+    def _eligible(self):
+        if not self._flat_params_ok():
+            return False
+        g = self.param_groups[0]
+        return not (g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or not g.get("fused"))
+
+    def _state_fits(self, ps, active):
+        """one shared step counter, moments for every active parameter or none, no state elsewhere"""
+        steps = {float(self.state[ps[i]]["step"]) for i in active if ps[i] in self.state and "step" in self.state[ps[i]]}
+        have = [i for i in active if ps[i] in self.state and "exp_avg" in self.state[ps[i]]]
+        return not (len(steps) > 1 or (have and len(have) != len(active)) or
+                    any(p in self.state and self.state[p] for i, p in enumerate(ps) if i not in active))
+
+    def _adopt_state(self, ps, active, offs, n, dev):
+        steps = {float(self.state[ps[i]]["step"]) for i in active if ps[i] in self.state and "step" in self.state[ps[i]]}
+        have = {i for i in active if ps[i] in self.state and "exp_avg" in self.state[ps[i]]}
+        flat_m = torch.zeros(n, dtype=torch.float32, device=dev)
+        flat_v = torch.zeros(n, dtype=torch.float32, device=dev)
+        step = torch.full((), steps.pop() if steps else 0.0, dtype=torch.float32, device=dev)
+        host_step = int(round(float(step)))
+        for i in active:
+            p, o = ps[i], offs[i]
+            m, v = flat_m[o:o + p.numel()].view_as(p), flat_v[o:o + p.numel()].view_as(p)
+            if i in have:
+                m.copy_(self.state[p]["exp_avg"])
+                v.copy_(self.state[p]["exp_avg_sq"])
+            self.state[p] = {"step": step, "exp_avg": m, "exp_avg_sq": v}
+        return {"m": flat_m, "v": flat_v, "step": step, "host_step": host_step}
+
+    def _on_leave(self, f):
+        # every stepped parameter gets its own step counter
+        for i in self._active:
+            st = self.state[f["params"][i]]
+            st["step"] = st["step"].clone()
+
+    def _launch(self, f, grp, gp, n):
+        b1, b2 = grp["betas"]
+        f["host_step"] += 1
+        _lib.check(_lib.load().mlsp_adam_flat_f32(f["p"].data_ptr(), f["m"].data_ptr(), f["v"].data_ptr(), f["seg"][0], f["seg"][1], gp, n,
+                                                  float(grp["lr"]), float(b1), float(b2), float(grp["weight_decay"]), float(grp["eps"]),
+                                                  f["host_step"], f["step"].data_ptr(), f["tile_amax"].data_ptr(), _lib.stream()), "mlsp_adam_flat_f32")
+
+
+class FlatSGD(_FlatStep, torch.optim.SGD):
+    """torch.optim.SGD (the trainers' `--optimizer SGD`: PointDA/trainer.py:258-259, PointDA/train_spst.py, PointSegDA/trainer.py:212-214)
+    over one flat parameter buffer and one flat momentum buffer: ONE launch of `mlsp_sgd_flat_f32` per step, bit-identical to torch's
+    default (multi-tensor) SGD on GPU tensors.  Same constructor arguments and validation as torch.optim.SGD; per-parameter
+    `momentum_buffer` entries are views of the flat buffer, and with momentum == 0 there is no state at all.  The step kernel leaves the
+    per-tile magnitude bounds of the updated parameters as FlatAdam's does (weight_bounds).  The flat step needs what FlatAdam's needs
+    (one group of fp32 parameters on one GPU, the same set of parameters holding gradients at every step) and torch's default path
+    (foreach, not fused or differentiable, float lr / momentum / weight_decay); anything else -- or loaded state in which only some
+    stepped parameters have a momentum buffer -- falls back to torch's own path for good, with the state carried over.  Unlike torch's
+    foreach path with nesterov and no weight decay, the gradients are left as autograd made them."""
+    _LEAVE_MSG = ("FlatSGD: leaving the one-launch flat step for torch's multi-tensor SGD (%s); same results, but the optimizer step "
+                  "takes several foreach launches from now on")
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None):
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                         maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        self._flat_init()
+
+    def _eligible(self):
+        if not self._flat_params_ok():
+            return False
+        g = self.param_groups[0]
+        if g.get("differentiable") or g.get("fused") or g.get("foreach") is False:
+            return False
+        if any(isinstance(g[k], torch.Tensor) for k in ("lr", "momentum", "dampening", "weight_decay")):
+            return False
+        return not any(p.grad is not None and p.grad.is_sparse for p in g["params"])
+
+    def _state_fits(self, ps, active):
+        """momentum buffers for every active parameter or for none (torch would step the others per tensor)"""
+        if self.param_groups[0]["momentum"] == 0:
+            return True
+        have = [i for i in active if "momentum_buffer" in self.state.get(ps[i], {})]
+        return not have or len(have) == len(active)
+
+    def _adopt_state(self, ps, active, offs, n, dev):
+        if self.param_groups[0]["momentum"] == 0:
+            return {"b": None, "first": False}
+        have = [i for i in active if "momentum_buffer" in self.state.get(ps[i], {})]
+        flat_b = torch.zeros(n, dtype=torch.float32, device=dev)
+        for i in active:
+            p, o = ps[i], offs[i]
+            b = flat_b[o:o + p.numel()].view_as(p)
+            if have:
+                b.copy_(self.state[p]["momentum_buffer"])
+            self.state[p]["momentum_buffer"] = b
+        return {"b": flat_b, "first": not have}
+
+    def _flat_fits(self, f):
+        # momentum switched on or off after the layout was built: torch's path (it keeps or ignores the buffers by itself)
+        return (f["b"] is not None) == (self.param_groups[0]["momentum"] != 0)
+
+    def _launch(self, f, grp, gp, n):
+        b = f["b"]
+        _lib.check(_lib.load().mlsp_sgd_flat_f32(f["p"].data_ptr(), b.data_ptr() if b is not None else None, f["seg"][0], f["seg"][1], gp, n,
+                                                 float(grp["lr"]), float(grp["momentum"]), float(grp["dampening"]),
+                                                 float(grp["weight_decay"]), int(bool(grp["nesterov"])), int(bool(grp["maximize"])),
+                                                 int(f["first"]), f["tile_amax"].data_ptr(), _lib.stream()), "mlsp_sgd_flat_f32")
+        f["first"] = False
