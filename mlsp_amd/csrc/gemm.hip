@@ -842,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs p) {
 //     loaded (8-byte rows, no transposing 2-byte stores) and read with two ds_read_b64_tr_b16 per fragment; the 320-byte pitch puts the
 //     four k-rows of a transposed read in four different 64-byte bank windows;
 //   * per K-tile: all 24 fragments of tile t are read, barrier, then the 48 (24) MFMAs of tile t run with the split + image write of tile
-//     t+1 and the global loads of tile t+2 hand-placed between them (gen_split_body.py -> gemm_split_body_wm*.inc), barrier.
+//     t+1 and the global loads of tile t+2 hand-placed between them (gen_split_body.py -> build/gemm_split_body.inc), barrier.
 __device__ __forceinline__ uint32_t sx_cvt_pk(float lo, float hi) {       // one v_cvt_pk_bf16_f32 (RNE)
     const f32x2 v = {lo, hi};
     const bf16x2 b = __builtin_convertvector(v, bf16x2);
@@ -1186,106 +1186,9 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmArgs p) {
         uint32_t pkd[5][2][2];                                        // NPC == 2: the pieces of the quads staged before the barrier
         float r0, r1, a1;
         __builtin_amdgcn_sched_barrier(0);
-        // (one generated body per (tile height, transformed operand, dropout): gen_split_body.py spreads the vector work over the MFMA slots)
-        if constexpr (NPC == 2) {
-            if constexpr (DY && XF == 0) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_dy.inc"
-                } else {
-#include "gemm_split_body_h_wm1_dy.inc"
-                }
-            } else if constexpr (DY && !XD) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_dyxb.inc"
-                } else {
-#include "gemm_split_body_h_wm1_dyxb.inc"
-                }
-            } else if constexpr (DY) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_dyxbd.inc"
-                } else {
-#include "gemm_split_body_h_wm1_dyxbd.inc"
-                }
-            } else if constexpr (XF == 0) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2.inc"
-                } else {
-#include "gemm_split_body_h_wm1.inc"
-                }
-            } else if constexpr (XF == 1 && !XD) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_xa.inc"
-                } else {
-#include "gemm_split_body_h_wm1_xa.inc"
-                }
-            } else if constexpr (XF == 1 && XD) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_xad.inc"
-                } else {
-#include "gemm_split_body_h_wm1_xad.inc"
-                }
-            } else if constexpr (XF == 2 && !XD) {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_xb.inc"
-                } else {
-#include "gemm_split_body_h_wm1_xb.inc"
-                }
-            } else {
-                if (WM == 2) {
-#include "gemm_split_body_h_wm2_xbd.inc"
-                } else {
-#include "gemm_split_body_h_wm1_xbd.inc"
-                }
-            }
-        } else if constexpr (DY && XF == 0) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_dy.inc"
-            } else {
-#include "gemm_split_body_wm1_dy.inc"
-            }
-        } else if constexpr (DY && !XD) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_dyxb.inc"
-            } else {
-#include "gemm_split_body_wm1_dyxb.inc"
-            }
-        } else if constexpr (DY) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_dyxbd.inc"
-            } else {
-#include "gemm_split_body_wm1_dyxbd.inc"
-            }
-        } else if constexpr (XF == 0) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2.inc"
-            } else {
-#include "gemm_split_body_wm1.inc"
-            }
-        } else if constexpr (XF == 1 && !XD) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_xa.inc"
-            } else {
-#include "gemm_split_body_wm1_xa.inc"
-            }
-        } else if constexpr (XF == 1 && XD) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_xad.inc"
-            } else {
-#include "gemm_split_body_wm1_xad.inc"
-            }
-        } else if constexpr (XF == 2 && !XD) {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_xb.inc"
-            } else {
-#include "gemm_split_body_wm1_xb.inc"
-            }
-        } else {
-            if (WM == 2) {
-#include "gemm_split_body_wm2_xbd.inc"
-            } else {
-#include "gemm_split_body_wm1_xbd.inc"
-            }
-        }
+        // (one generated body per (piece count, tile height, transformed operand, dropout): gen_split_body.py's VARIANTS table; it spreads the
+        // vector work over the MFMA slots and writes the selection ladder with the bodies in place)
+#include "build/gemm_split_body.inc"
         SX_XF_NEXT(t + 2);
         SX_DY_NEXT(t + 2);
         __syncthreads();

@@ -115,7 +115,7 @@ def test_no_register_spills_in_hot_kernels():
 
 # kernel family -> ceiling of "SGPRs Spill" (the figures of the round-4 build plus a margin).  A scalar spill is a v_writelane / v_readlane
 # pair into a spare VGPR, never memory; what would hurt is a reload inside a K loop, so the ceilings are held where they were measured
-# harmless: gemm_split_kernel's K-tile body (gemm_split_body_wm*.inc) addresses everything through loop-invariant descriptors and
+# harmless: gemm_split_kernel's K-tile body (generated by gen_split_body.py) addresses everything through loop-invariant descriptors and
 # immediate offsets, and DESIGN.md section 10 lists the readlane count of the loop bodies.
 SGPR_SPILL_CEILING = {"gemm_split_kernel": 64, "gemm_f32_kernel": 64, "gemm_bf16_kernel": 64, "edge_reduce_lds_kernel": 180, "edge_reduce_wide_kernel": 180,
                       "knn_mfma5_kernel": 220, "knn_mfma4_kernel": 96, "knn_kernel": 300, "knn_query_kernel": 80,
