@@ -674,10 +674,6 @@ int launch_bn_bwd_finalize_coef_z(hipStream_t st, const double* part, int nparts
                        (const float*)nullptr, 1, 0, (float*)nullptr, zero_vec, 1);
     return mlsp_launch_status();
 }
-int launch_bn_bwd_finalize_coef(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
-                                float* dbeta, float* coef) {
-    return launch_bn_bwd_finalize_coef_z(st, part, nparts, count, C, bn_save, dgamma, dbeta, coef, nullptr);
-}
 int launch_bn_bwd_finalize_coef_groups(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
                                        float* dbeta, float* coef, const float* gys, int ppg, int rows, float* gout) {
     if (!gys || !gout || ppg <= 0 || nparts % ppg) return MLSP_ERR_ARG;
@@ -777,7 +773,7 @@ __global__ __launch_bounds__(256) void colsum_groups_fin_kernel(const float* __r
     }
 }
 
-int launch_colsum_groups(hipStream_t st, const float* X, int G, int rows_per_group, int C, float* out, float* scratch = nullptr) {
+int launch_colsum_groups(hipStream_t st, const float* X, int G, int rows_per_group, int C, float* out, float* scratch) {
     if (scratch && vec_ok(C, X) && 256 % (C / 4) == 0 && rows_per_group >= 256) {
         const int slabs = 16;                       // scratch: [G][16][C] floats
         hipLaunchKernelGGL((colsum_groups_vec_kernel<float>), dim3(slabs, G), dim3(256), 0, st, X, C, rows_per_group, slabs, scratch);

@@ -104,18 +104,9 @@ __global__ __launch_bounds__(64) void colmax_bwd_coef_kernel(const float* __rest
     }
 }
 
-// Wb[c][:] = rowscale[c] * W[c][:]
-__global__ void scale_rows_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ rowscale, int Cout, int Cin,
-                                  float* __restrict__ Wb) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Cout * Cin) return;
-    int c = t / Cin, i = t % Cin;
-    Wb[t] = rowscale[c] * W[(size_t)c * ldw + i];
-}
-
 // negr[i] = - sum_c v[c] * W[c][i]        block: 64 columns x 16 row groups (one wave each), LDS reduce in fixed order
-// (Wb != null: the workgroups past the first ceil(Cin / 64) are scale_rows_kernel's -- Wb[c][:] = rowscale[c] * W[c][:] -- so that the two
-// weight-sized preparations of the colmax backward's input-gradient half are one launch)
+// (the workgroups past the first ceil(Cin / 64) scale rows instead -- Wb[c][:] = rowscale[c] * W[c][:] -- so that the two weight-sized
+// preparations of the colmax backward's input-gradient half are one launch)
 __global__ __launch_bounds__(1024) void wt_vec_neg_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ v, int Cout,
                                                           int Cin, float* __restrict__ negr, const float* __restrict__ rowscale,
                                                           float* __restrict__ Wb) {
@@ -303,14 +294,6 @@ int launch_colmax_bwd_coef(hipStream_t st, const float* dOut, const float* out, 
                            double count, int act, float slope, int training, float* g, float* coef, float* dgamma, float* dbeta) {
     hipLaunchKernelGGL(colmax_bwd_coef_kernel, dim3(C), dim3(64), 0, st, dOut, out, ysel, bn, B, C, count, act, slope, training, g,
                        coef, dgamma, dbeta);
-    return mlsp_launch_status();
-}
-int launch_scale_rows(hipStream_t st, const float* W, int ldw, const float* rowscale, int Cout, int Cin, float* Wb) {
-    hipLaunchKernelGGL(scale_rows_kernel, dim3((Cout * Cin + 255) / 256), dim3(256), 0, st, W, ldw, rowscale, Cout, Cin, Wb);
-    return mlsp_launch_status();
-}
-int launch_wt_vec_neg(hipStream_t st, const float* W, int ldw, const float* v, int Cout, int Cin, float* negr) {
-    hipLaunchKernelGGL(wt_vec_neg_kernel, dim3((Cin + 63) / 64), dim3(1024), 0, st, W, ldw, v, Cout, Cin, negr, (const float*)nullptr, (float*)nullptr);
     return mlsp_launch_status();
 }
 // negr = -W^T v and Wb = diag(rowscale) W in one launch

@@ -20,11 +20,9 @@ static inline int mlsp_launch_status() {
     return e == hipSuccess ? MLSP_OK : (int)e;
 }
 
-// HIP-event profiling hook (gemm.hip; armed by mlsp_profile_begin, off otherwise): kernel classes of mlsp_profile_classes()
+// HIP-event profiling hook (gemm.hip prof_cls_begin / prof_cls_end; armed by mlsp_profile_begin, off otherwise): kernel classes of mlsp_profile_classes()
 enum { MLSP_PROF_GEMM = 0, MLSP_PROF_KNN_C3, MLSP_PROF_KNN_C64, MLSP_PROF_KNN_C128, MLSP_PROF_EDGE_REDUCE, MLSP_PROF_TNET_FWD,
        MLSP_PROF_TNET_BWD, MLSP_PROF_GEMM_SPLIT /* the subset of class 0 that ran on gemm_split_kernel */, MLSP_PROF_NCLS };
-int prof_cls_begin(hipStream_t st, int cls);              // -> token (< 0: not armed)
-void prof_cls_end(hipStream_t st, int token, double work);
 
 // Products of the GEMM family are a PER-CALL argument of every entry point that reaches it (include/mlsp_hip.h `precision`): 0 f32 MFMA,
 // 1 bf16-rounded operands, 2 fp32-accurate six-product bf16 split.  An entry point opens a GemmPrecisionScope from its argument; the
@@ -41,13 +39,7 @@ struct GemmPrecisionScope {
     GemmPrecisionScope(const GemmPrecisionScope&) = delete;
     GemmPrecisionScope& operator=(const GemmPrecisionScope&) = delete;
 };
-int gemm_precision_mode();
 #define PREC_SCOPE(mode_) if ((mode_) < 0 || (mode_) > 3) return MLSP_ERR_ARG; GemmPrecisionScope prec_scope_(mode_, ws, ws_bytes)
-
-// Raise a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) -- at most once per (device, kernel, size): the host call
-// costs tens of microseconds, a dozen of them per step put the enqueue thread behind the GPU on slower hosts.  (api.hip; a cache of
-// what was already asked of the runtime, not dispatch state: the same launches happen with or without it.)
-hipError_t mlsp_lds_limit(const void* fn, size_t lds);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -168,3 +160,6 @@ static inline XfDev xf_dev(const GemmXf& x) {
     d.xH = mix32_host((uint32_t)x.seed) ^ (uint32_t)(x.seed >> 32) * 0x9e3779b9U; d.ld = x.ld; d.col = x.col;
     return d;
 }
+
+// every host function that one translation unit defines and another calls (after the Gemm* structs its prototypes name)
+#include "launchers.h"

@@ -1540,7 +1540,7 @@ static void launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C
 }
 
 // How many K splits a launch will use (shared by the launcher and mlsp_workspace_bytes).
-int gemm_pick_split(int M, int N, int K) {
+static int gemm_pick_split(int M, int N, int K) {
     int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
     long tiles = (long)ntm * ntn;
     int ktiles = (K + BK - 1) / BK;
@@ -1573,7 +1573,6 @@ int gemm_stat_parts(int M, int N, int K) {
 }
 int gemm_panel_rows(int M, int N, int K) { return gemm_pick_bm(M, N, K); }
 
-size_t thin_tn_slab_floats(int M, int N, int K);
 // A 64 x 64 weight gradient over many rows (dW = dY^T X of a 64 -> 64 layer over the edges of a set-abstraction level): neither the 128-row
 // tile kernels (a quarter of the tile used, predicated path) nor the N = 64 kernel (M % 128) fit it.  With contiguous operands two
 // consecutive rows are ONE row of a [K/2][128] matrix, and  A2^T B2  (128 x 128, an interior-tile launch) holds the even-row sum in its
@@ -1720,13 +1719,6 @@ extern "C" int mlsp_profile_split_kinds(double* out) {
     return MLSP_OK;
 }
 
-int launch_skinny_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                       float* C, int ldc, const float* bias);
-int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                     int ldc, const float* bias, float* slab, size_t slab_floats, const GemmXf* xf, const GemmBs* bs = nullptr);
-int thin_bs_parts(int M, int N, int K);
-bool thin_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which);
-
 // Can this contraction stage `which` (1: A [M][K] row-major, 2: B [K][N] k-major) through the operand transform?  Interior tiles,
 // 16-byte loads, fp32 operands, the MFMA tile kernels (not the thin / skinny / N = 64 ones).
 // (mode 2: gemm_split_kernel<.., XF, XD> where the split kernel pays, the fp32 transform kernels on the short-K launches: exact fp32
@@ -1774,9 +1766,8 @@ bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which) {
 
 int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B,
                 int ldb, float* C, int ldc, const float* bias, const float* gbias, int rows_per_group, float* slab,
-                size_t slab_floats, double* stat_part = nullptr, const float* sel_gamma = nullptr, float* sel_val = nullptr,
-                int* sel_row = nullptr, bool accumulate = false, const GemmXf* xf = nullptr, int stat_ld = 0, const GemmGroups* grp = nullptr,
-                const GemmBs* bs = nullptr, const GemmDy* dy = nullptr) {
+                size_t slab_floats, double* stat_part, const float* sel_gamma, float* sel_val, int* sel_row, bool accumulate,
+                const GemmXf* xf, int stat_ld, const GemmGroups* grp, const GemmBs* bs, const GemmDy* dy) {
     // grp (nullable): block-diagonal product in one launch (GemmArgs groups; M / N are the LAUNCH's dimensions, K one group's).
     // Only on the interior-tile fp32 kernel: MLSP_ERR_UNSUPPORTED otherwise (nothing launched; the caller launches group by group).
     // stat_ld (0: N): C is a column slice of a [M][stat_ld] matrix whose BatchNorm statistics are taken as ONE vector (multi.hip):

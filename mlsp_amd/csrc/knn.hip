@@ -1327,15 +1327,6 @@ static int launch_knn_k(hipStream_t st, const float* x, int ld, const float* xx,
     return mlsp_launch_status();
 }
 
-bool knn6_supported(int B, int N, int C, int k);                       // knn6.hip
-size_t knn6_plane_bytes(int P, int C);
-int launch_knn6(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes);
-bool knn6_vex_supported(int B, int N, int C, int k);
-size_t knn6_vex_bytes(int P);
-int launch_knn6_vex(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* cand);
-bool knn6w_supported(int B, int N, int C, int k);
-int launch_knn6w(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes, int** flags_out);
-
 // xx_ws: [B*N] floats of workspace; planes (nullable): knn6_plane_bytes(B*N, C) bytes of workspace for the v6 kernel's bf16 images
 int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx_ws, void* planes, size_t plane_bytes) {
     if (!x || !idx || !xx_ws || B <= 0 || N <= 0 || C <= 0 || k <= 0 || k > N || ld < C) return MLSP_ERR_ARG;

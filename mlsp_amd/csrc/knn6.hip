@@ -1355,7 +1355,7 @@ __global__ __launch_bounds__(512) void knn6w_kernel(const float* __restrict__ x,
     }
 }
 
-size_t knn6_lds_bytes(int N) { return (size_t)512 * K6_LSTR + (size_t)N * 4 + 128 * 4 + 512 * 4 + 64 + (size_t)8 * 512 * 4 + 512 * 4; }
+static size_t knn6_lds_bytes(int N) { return (size_t)512 * K6_LSTR + (size_t)N * 4 + 128 * 4 + 512 * 4 + 64 + (size_t)8 * 512 * 4 + 512 * 4; }
 
 // shapes v6 takes (the rest stays on knn.hip's kernels)
 // the vector-exact mode of the kernel: C <= 3 on whole 128-query chunks, the cloud's {x, xx} image in the 16 KB work-list area
@@ -1378,7 +1378,7 @@ bool knn6_supported(int B, int N, int C, int k) {
     return B > 0 && N >= 128 && N % 128 == 0 && N <= 4096 && C >= 1 && C <= 128 && k >= 1 && k <= K6_KMAX && k <= N &&
            knn6_lds_bytes(N) <= 160 * 1024;
 }
-int knn6_padded_channels(int C) { return C <= 16 ? 16 : C <= 64 ? 64 : 128; }
+static int knn6_padded_channels(int C) { return C <= 16 ? 16 : C <= 64 ? 64 : 128; }
 // image + centred norms + the wide kernel's cloud flags (B <= P / 128 ints)
 size_t knn6_plane_bytes(int P, int C) { return (size_t)P * 2 * knn6_padded_channels(C) * sizeof(__bf16) + (size_t)P * sizeof(float) + ((size_t)P / 128 + 4) * sizeof(int); }
 bool knn6w_supported(int B, int N, int C, int k) {

@@ -14,35 +14,6 @@
 #include "../../include/mlsp_hip.h"
 #include <cstdlib>
 
-int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                float* C, int ldc, const float* bias, const float* gbias, int rows_per_group, float* slab, size_t slab_floats,
-                double* stat_part, const float* sel_gamma, float* sel_val, int* sel_row, bool accumulate, const GemmXf* xf, int stat_ld,
-                const GemmGroups* grp = nullptr, const GemmBs* bs = nullptr, const GemmDy* dy = nullptr);
-int gemm_bs_parts(int M, int N, int K, int lda, int ldb, int ldc);
-int gemm_panel_rows(int M, int N, int K);
-bool gemm_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which);
-bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which);
-int gemm_precision_mode();
-int gemm_stat_parts(int M, int N, int K);
-size_t gemm_slab_floats(int M, int N, int K);
-int bn_vec_parts(int M);
-int launch_colstats_n(hipStream_t st, const float* Y, int M, int C, int ld, double* part, int* nparts_out);
-int launch_bn_finalize(hipStream_t st, const double* part, int nparts, double count, int C, const float* gamma,
-                       const float* beta, float* run_mean, float* run_var, float momentum, float eps, float* scale,
-                       float* shift, float* save_mean, float* save_invstd);
-int launch_bn_eval_prepare(hipStream_t st, int C, const float* gamma, const float* beta, const float* run_mean,
-                           const float* run_var, float eps, float* scale, float* shift, float* save_mean, float* save_invstd);
-int launch_bn_bwd_finalize_coef(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
-                                float* dbeta, float* coef);
-bool gemm_dy_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb);
-int launch_bn_bwd_finalize(hipStream_t st, const double* part, int nparts, double count, int C, float* dgamma, float* dbeta,
-                           float* mean_dz, float* mean_dzy);
-int launch_bn_bwd_finalize_z(hipStream_t st, const double* part, int nparts, double count, int C, float* dgamma, float* dbeta,
-                             float* mean_dz, float* mean_dzy, float* zero_vec);
-int launch_bn_bwd_finalize_coef_z(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
-                                  float* dbeta, float* coef, float* zero_vec);
-int launch_colsum(hipStream_t st, const float* X, int M, int C, double* part, float* out);
-
 #define MROWS 64          // rows per workgroup of the streaming passes (== VROWS of bn.hip: bn_vec_parts)
 
 // ---- streaming passes with per-channel activation parameters: a thread owns 4 consecutive channels and walks rows -------------------
@@ -221,7 +192,7 @@ __global__ __launch_bounds__(256) void xf_materialize_kernel(const float* __rest
         }
     }
 }
-int launch_xf_materialize_ld(hipStream_t st, const float* X, int ldx, int M, int C, const GemmXf& xf, float* out, int ldo) {
+static int launch_xf_materialize_ld(hipStream_t st, const float* X, int ldx, int M, int C, const GemmXf& xf, float* out, int ldo) {
     if (!X || !out || M <= 0 || C <= 0 || ldo < C || (double)M * xf.ld >= 17179869184.0) return MLSP_ERR_ARG;
     const int vec = (C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && xf.ld % 4 == 0 && xf.col % 4 == 0 &&
                      (((uintptr_t)X | (uintptr_t)out | (uintptr_t)xf.scale | (uintptr_t)xf.shift) & 15) == 0) ? 1 : 0;

@@ -582,14 +582,6 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_point_kernel(const float* __r
     if (en == 0) *(f32x4*)(du + (size_t)j * C + c) = acc;
 }
 
-int launch_bn_finalize(hipStream_t st, const double* part, int nparts, double count, int C, const float* gamma, const float* beta,
-                       float* run_mean, float* run_var, float momentum, float eps, float* scale, float* shift, float* save_mean,
-                       float* save_invstd);
-int launch_bn_eval_prepare(hipStream_t st, int C, const float* gamma, const float* beta, const float* run_mean, const float* run_var,
-                           float eps, float* scale, float* shift, float* save_mean, float* save_invstd);
-int launch_bn_bwd_finalize(hipStream_t st, const double* part, int nparts, double count, int C, float* dgamma, float* dbeta, float* mean_dz,
-                           float* mean_dzy);
-
 static bool saf_shape_ok(int C, int ns) { return (C == 16 || C == 32 || C == 64 || C == 128 || C == 256) && ns <= 256; }
 int sa_fold_parts(long E) { return (int)((E + SAF_EPB - 1) / SAF_EPB); }
 

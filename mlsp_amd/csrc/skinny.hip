@@ -334,11 +334,6 @@ int launch_skinny_bn_bwd_z(hipStream_t st, const float* dZ, const float* Y, floa
                        sk_drop_thresh(pd), dropout_inv_keep8(pd), seed, dgamma, dbeta, zero_vec);
     return mlsp_launch_status();
 }
-int launch_skinny_bn_bwd(hipStream_t st, const float* dZ, const float* Y, float* dY, int M, int C, const float* bn_save, int training,
-                         int act, float slope, float p_drop, uint64_t seed, float* dgamma, float* dbeta) {
-    return launch_skinny_bn_bwd_z(st, dZ, Y, dY, M, C, bn_save, training, act, slope, p_drop, seed, dgamma, dbeta, nullptr);
-}
-
 
 // ---- composition of two linear maps (PointSegDA's conv pairs without an activation in between: include/mlsp_hip.h mlsp_compose_linear_*) ----
 // forward: workgroup = output row o; thread c < Ci: W[o][c] = sum_m Wb[o][m] Wa[m][c]; thread Ci: b[o] = sum_m Wb[o][m] ba[m] + bb[o]

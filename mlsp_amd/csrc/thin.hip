@@ -291,7 +291,6 @@ __global__ __launch_bounds__(256) void thin_tn_kernel(const float* __restrict__ 
     }
 }
 
-int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit);
 #define THIN_SN_BLOCKS 1024  // workgroups of the small-N kernel at most (512: 24.9 / 8.1 us, 1024: 21.2 / 7.2 us for the 16- / 3-channel layers)
 #define THIN_TN_ROWS 64      // rows of the K dimension per workgroup (one partial slab each)
 

@@ -1742,7 +1742,6 @@ __global__ __launch_bounds__(256) void tnet_edge_bwd2_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-int gemm_precision_mode();        // gemm.hip
 int tnet_grid(int ntiles) { return ntiles < 512 ? ((ntiles + 7) / 8) * 8 : 512; }
 int tnet_points_per_tile(int k) { return k > 0 && k <= TN_ROWS ? (TN_ROWS / k > 8 ? 8 : TN_ROWS / k) : 0; }
 
@@ -1817,8 +1816,7 @@ int launch_tnet_bwd_g(hipStream_t st, const float* dT, const float* T, const flo
     return mlsp_launch_status();
 }
 
-int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit);
-int tnet_bwd_grid(int ntiles) { return ntiles < 256 ? ((ntiles + 7) / 8) * 8 : 256; }
+static int tnet_bwd_grid(int ntiles) { return ntiles < 256 ? ((ntiles + 7) / 8) * 8 : 256; }
 // floats of scratch the backward needs: workgroup partial slabs + M/cv + the reduced slab (Gram path), or the round-1 kernel's dW2 slabs
 size_t tnet_bwd_scratch_floats(int ntiles) {
     const size_t a = (size_t)tnet_bwd_grid(ntiles) * TG_SLAB + TN_C1 * TN_C1 + TN_C1 + TG_SLAB;

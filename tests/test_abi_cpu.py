@@ -148,6 +148,72 @@ def test_sgpr_spills_stay_bounded():
     assert {"gemm_split_kernel", "edge_reduce_lds_kernel"} <= seen
 
 
+CSRC = os.path.join(ROOT, "mlsp_amd", "csrc")
+
+
+def _file_scope_functions(path):
+    """(name, has_body) of every non-template, non-kernel function head at file scope of a C++ source; the second value is the source with
+    comments, literals and preprocessor lines blanked (to look for uses in)."""
+    def blank(m):
+        return re.sub(r"[^\n]", " ", m.group(0))
+    src = open(path).read().replace('extern "C"', "extern_C  ")
+    src = re.sub(r"//[^\n]*|/\*.*?\*/|\"(?:\\.|[^\"\\\n])*\"|'(?:\\.|[^'\\\n])*'", blank, src, flags=re.S)
+    src = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", blank, src, flags=re.M)
+    # keep file scope only: every braced body becomes "{}"; extern "C" { and namespace { are transparent
+    scope, stack, last = [], [], 0
+    for m in re.finditer(r"[{}]", src):
+        inside = sum(stack)
+        if m.group() == "{":
+            opens_body = inside or not re.search(r"(extern_C|\bnamespace(\s+\w+)?)\s*$", src[last:m.start()])
+            if not inside:
+                scope.append(src[last:m.start()] + ("{" if opens_body else ";"))
+            stack.append(1 if opens_body else 0)
+        else:
+            if stack.pop() and inside == 1:
+                scope.append("}")
+        if not sum(stack):
+            last = m.end()
+    assert not stack, path
+    scope.append(src[last:])
+    out = []
+    for head, end in re.findall(r"([^;{}]+)(;|\{)", "".join(scope)):
+        head = re.sub(r"^\s*extern_C\s*", "", head)
+        before, paren, _ = head.partition("(")                 # "<return type> <name>" "(" "<parameters>)"
+        m = re.fullmatch(r"\s*([\w\s\*&:<>,]*[\w\*&>])\s*\b(\w+)\s*", before)
+        if (m and paren and head.rstrip().endswith(")")
+                and not re.search(r"\b(template|__global__|__device__|typedef|struct|class|enum|using|operator)\b", m.group(1))):
+            out.append((m.group(2), end == "{"))
+    return out, src
+
+
+def test_cross_file_host_functions_are_declared_once_in_launchers_h():
+    """csrc/launchers.h is the cross-file surface of the kernel library, exactly: a .hip file declares nothing that another file defines
+    (the compiler cannot check such a copy against the definition), every function the header declares is defined in exactly one .hip
+    file, and each one is used by some other file (a function only its own file uses is static there, one nobody uses is deleted)."""
+    import glob
+    funcs, text = {}, {}
+    for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        funcs[os.path.basename(f)], text[os.path.basename(f)] = _file_scope_functions(f)
+    assert len(funcs) >= 17
+    defined_in = {}
+    for f, items in funcs.items():
+        for name, has_body in items:
+            if has_body:
+                defined_in.setdefault(name, []).append(f)
+    # what a .hip file declares without a body, it defines itself further down
+    strays = [(f, name) for f, items in funcs.items() for name, has_body in items if not has_body and f not in defined_in.get(name, [])]
+    assert not strays, strays
+    header, _ = _file_scope_functions(os.path.join(CSRC, "launchers.h"))
+    assert len(header) >= 100 and not any(has_body for _, has_body in header)
+    names = [name for name, _ in header]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    wrong = {n: defined_in.get(n, []) for n in names if len(defined_in.get(n, [])) != 1}
+    assert not wrong, wrong
+    words = {f: set(re.findall(r"\w+", t)) for f, t in text.items()}
+    unused = [n for n in names if not any(n in w for f, w in words.items() if f != defined_in[n][0])]
+    assert not unused, unused
+
+
 def test_forward_bookkeeping_is_per_thread():
     """nn.DataParallel runs one replica per Python thread (PointDA/trainer.py:251-252): the queue of num_batches_tracked
     increments and the forward nesting depth are thread-local, so interleaved forwards of two replicas lose no increment."""
