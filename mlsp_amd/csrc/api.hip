@@ -50,10 +50,10 @@ int mlsp_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda, 
                   const float* bias, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
     PREC_SCOPE(precision);
     Workspace w(ws, ws_bytes);
-    size_t sf = gemm_slab_floats(M, N, K);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
-    if (sf && !slab) sf = 0;   // launcher falls back to a single pass
-    return launch_gemm(st, ta != 0, tb != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, nullptr, 0, slab, sf);
+    GemmOpts o; o.bias = bias;
+    take_slab(w, o, gemm_slab_floats(M, N, K));
+    if (!o.slab) o.slab_floats = 0;   // launcher falls back to a single pass
+    return launch_gemm(st, ta != 0, tb != 0, M, N, K, A, lda, B, ldb, C, ldc, o);
 }
 
 int mlsp_knn_f32(const float* x, int ldx, int B, int N, int C, int k, int32_t* idx, int32_t* rev_off, int32_t* rev_ent,
@@ -191,15 +191,14 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
     float* Wd = Wd_out ? Wd_out : w.take<float>((size_t)2 * Cout * C);     // Wd_out: kept by the caller for the backward pass
     int nparts = edge_reduce_parts(P);
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
-    size_t sf = gemm_slab_floats(P, 2 * Cout, C);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, gemm_slab_floats(P, 2 * Cout, C));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
     if (!training) {                  // eval mode: the BatchNorm vectors do not depend on the batch -- prepared by the weight-fold launch
         if (!run_mean || !run_var) return MLSP_ERR_ARG;
         CHECK(launch_build_wd_eval(st, W, Cout, C, Wd, Cout, gamma, beta, run_mean, run_var, bn_save, 0, nullptr, nullptr, nullptr, nullptr, nullptr, eps));
     } else CHECK(launch_build_wd(st, W, Cout, C, Wd, (C >= 128 && C % 32 == 0 && build_wd_leaves_bound(Cout, C)) ? amax_reserve(Wd, 2 * Cout, C, C) : nullptr));   // (mode 3: the fold leaves the bound of what it writes)
-    CHECK(launch_gemm(st, false, true, P, 2 * Cout, C, x, ldx, Wd, C, uv, 2 * Cout, nullptr, nullptr, 0, slab, sf));
+    CHECK(launch_gemm(st, false, true, P, 2 * Cout, C, x, ldx, Wd, C, uv, 2 * Cout, so));
     {   // the neighbour gather + max/min + BN sums: compulsory bytes = u half + indices in, msel + s1 + arg slot out
         const int tok = prof_cls_begin(st, MLSP_PROF_EDGE_REDUCE);
         const int rc = launch_edge_reduce(st, uv, idx, gamma, P, N, Cout, k, msel, argsel, s1, part, &nparts);
@@ -209,9 +208,8 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
     if (training) {
         // (mode 3, the caller offered bounds for `out`: the finalizer leaves |gamma| sqrt(P k) + |beta| per channel -- a bound of the layer's
         // output for the GEMMs that read it, instead of a streaming pass over it)
-        bn_bound_request(amax_offered_output(out, P, Cout, ldo, Cout));
         CHECK(launch_bn_finalize(st, part, nparts, (double)P * k, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale,
-                                 shift, mean, invstd));
+                                 shift, mean, invstd, amax_offered_output(out, P, Cout, ldo, Cout)));
     }
     CHECK(launch_edge_select_act(st, msel, uv, P, Cout, scale, shift, act, slope, out, ldo));
     return MLSP_OK;
@@ -237,9 +235,7 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
     float* mean_dz = w.take<float>(Cout);
     float* mean_dzy = w.take<float>(Cout);
-    size_t sf1 = gemm_slab_floats(P, C, 2 * Cout), sf2 = gemm_slab_floats(2 * Cout, C, P);
-    size_t sf = sf1 > sf2 ? sf1 : sf2;
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, gemm_slab_floats(P, C, 2 * Cout), gemm_slab_floats(2 * Cout, C, P));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     const float* scale = bn_save, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
     // f16x3: the passes that write duv leave its bound (256 partial maxima in a slot of the workspace tail, found again by both products
@@ -256,12 +252,11 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
     // (the forward's [Wa ; Wb - Wa] is reused when the caller kept it; beta = 1: dx is added into a slice of a wider gradient)
     const float* Wdc = Wd_in;
     if (!Wdc && dx) { CHECK(launch_build_wd(st, W, Cout, C, Wd)); Wdc = Wd; }
-    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * Cout, duv, 2 * Cout, Wdc, C, dx, lddx, nullptr, nullptr, 0, slab, sf, nullptr,
-                              nullptr, nullptr, nullptr, dx_accumulate != 0));
-    gemm_unfold_request(dW);          // a split-K launch sums its slabs straight into the reference layout (gemm.hip splitk_reduce_unfold_kernel)
-    const int rcw = launch_gemm(st, true, false, 2 * Cout, C, P, duv, 2 * Cout, x, ldx, dWd, C, nullptr, nullptr, 0, slab, sf);
-    const bool unfolded = gemm_unfold_take();
-    if (rcw != MLSP_OK) return rcw;
+    GemmOpts od = so; od.accumulate = dx_accumulate != 0;
+    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * Cout, duv, 2 * Cout, Wdc, C, dx, lddx, od));
+    bool unfolded = false;            // a split-K launch sums its slabs straight into the reference layout (gemm.hip splitk_reduce_unfold_kernel)
+    GemmOpts ow = so; ow.unfold_dw = dW; ow.unfolded = &unfolded;
+    CHECK(launch_gemm(st, true, false, 2 * Cout, C, P, duv, 2 * Cout, x, ldx, dWd, C, ow));
     if (!unfolded) CHECK(launch_unbuild_wd(st, dWd, Cout, C, dW));
     return MLSP_OK;
 }
@@ -284,14 +279,13 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
     uint8_t* arg1 = w.take<uint8_t>((size_t)P * C1);
     int np1 = edge_reduce_parts(P), np2 = tnet_fwd_parts(B, N, k);
     double* part = w.take<double>((size_t)(np1 > np2 ? np1 : np2) * 2 * C2);
-    size_t sf = gemm_slab_floats(P, 2 * C1, C);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, gemm_slab_floats(P, 2 * C1, C));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     if (!training) {                  // eval mode: both BatchNorm stages' vectors ride in the weight-fold launch
         if (!run_mean1 || !run_var1 || !run_mean2 || !run_var2) return MLSP_ERR_ARG;
         CHECK(launch_build_wd_eval(st, W1, C1, C, Wd, C1, gamma1, beta1, run_mean1, run_var1, bn1_save, C2, gamma2, beta2, run_mean2, run_var2, bn2_save, eps));
     } else CHECK(launch_build_wd(st, W1, C1, C, Wd));
-    CHECK(launch_gemm(st, false, true, P, 2 * C1, C, x, ldx, Wd, C, uv, 2 * C1, nullptr, nullptr, 0, slab, sf));
+    CHECK(launch_gemm(st, false, true, P, 2 * C1, C, x, ldx, Wd, C, uv, 2 * C1, so));
     CHECK(launch_edge_reduce(st, uv, idx, gamma1, P, N, C1, k, msel, arg1, s1, part, &np1));
     if (training) {
         CHECK(launch_bn_finalize(st, part, np1, (double)P * k, C1, gamma1, beta1, run_mean1, run_var1, momentum, eps, bn1_save,
@@ -304,9 +298,9 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
         if (rc != MLSP_OK) return rc;
     }
     if (training) {
-        bn_bound_request(amax_offered_output(out, P, C2, C2, C2));     // (mode 3: the analytic bound of the stage's output, as mlsp_edgeconv_fwd_f32)
+        // (mode 3: the analytic bound of the stage's output, as mlsp_edgeconv_fwd_f32)
         CHECK(launch_bn_finalize(st, part, np2, (double)P * k, C2, gamma2, beta2, run_mean2, run_var2, momentum, eps, bn2_save,
-                                 bn2_save + C2, bn2_save + 2 * C2, bn2_save + 3 * C2));
+                                 bn2_save + C2, bn2_save + 2 * C2, bn2_save + 3 * C2, amax_offered_output(out, P, C2, C2, C2)));
     }
     CHECK(launch_tnet_out(st, zsel, bn2_save, P, slope, out));
     return MLSP_OK;
@@ -345,9 +339,7 @@ int mlsp_tnet_edge_bwd_f32(const float* dOut, const float* x, int ldx, const int
     float* m1 = w.take<float>(C1);
     float* m2 = w.take<float>(C1);
     float* duv = w.take<float>((size_t)P * 2 * C1);
-    size_t sf1 = gemm_slab_floats(P, C, 2 * C1), sf2 = gemm_slab_floats(2 * C1, C, P);
-    size_t sf = sf1 > sf2 ? sf1 : sf2;
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, gemm_slab_floats(P, C, 2 * C1), gemm_slab_floats(2 * C1, C, P));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     // BN2 backward sums of dz = dOut * act'(out): the same computation as the first pass of the generic BN backward (out > 0 <=>
     // scale2*zsel + shift2 > 0), so the vectorised column-stationary kernel is used when the operands allow it
@@ -377,8 +369,8 @@ int mlsp_tnet_edge_bwd_f32(const float* dOut, const float* x, int ldx, const int
     }
     CHECK(launch_tnet_edge_bwd2(st, dhp, uv, s1, bn1_save, training ? m1 : nullptr, m2, rev_off, rev_ent, P, N, k, duv));
     CHECK(launch_build_wd(st, W1, C1, C, Wd));
-    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * C1, duv, 2 * C1, Wd, C, dx, C, nullptr, nullptr, 0, slab, sf));
-    CHECK(launch_gemm(st, true, false, 2 * C1, C, P, duv, 2 * C1, x, ldx, dWd, C, nullptr, nullptr, 0, slab, sf));
+    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * C1, duv, 2 * C1, Wd, C, dx, C, so));
+    CHECK(launch_gemm(st, true, false, 2 * C1, C, P, duv, 2 * C1, x, ldx, dWd, C, so));
     CHECK(launch_unbuild_wd(st, dWd, C1, C, dW1));
     return MLSP_OK;
 }
@@ -422,12 +414,12 @@ static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const floa
     const int fused_parts = (gamma && training) ? gemm_stat_parts(M, Cout, Cin) : 0;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(M);
     double* part = gamma ? w.take<double>((size_t)nparts * 2 * Cout) : nullptr;
-    size_t sf = gemm_slab_floats(M, Cout, Cin);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
-    GemmXf xf_s; const GemmXf* xf = nullptr;
+    GemmOpts o; o.bias = bias; o.gbias = gbias; o.rows_per_group = rows_per_group;
+    take_slab(w, o, gemm_slab_floats(M, Cout, Cin));
+    GemmXf xf_s;
     if (in) {
         xf_s = chain_xf(*in, 1, training);
-        if (defer_fusable(*in) && gemm_xf_supported(false, true, M, Cout, Cin, X, ldx, W, ldw, 1)) xf = &xf_s;
+        if (defer_fusable(*in) && gemm_xf_supported(false, true, M, Cout, Cin, X, ldx, W, ldw, 1)) o.xf = &xf_s;
         else {                                             // shape outside the fused path: materialise the activated input once
             float* Xa = w.take<float>((size_t)M * Cin);
             if (!w.ok()) return MLSP_ERR_WORKSPACE;
@@ -439,12 +431,11 @@ static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const floa
     if (!gamma) {
         // plain Linear: the GEMM writes Z directly.  Every activated layer of the hot path has a BN.
         if (act || p_drop > 0.f) return MLSP_ERR_UNSUPPORTED;
-        return launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Z, Cout, bias, gbias, rows_per_group, slab, sf, nullptr, nullptr,
-                           nullptr, nullptr, false, xf);
+        return launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Z, Cout, o);
     }
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
-    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, bias, gbias, rows_per_group, slab, sf,
-                      fused_parts ? part : nullptr, nullptr, nullptr, nullptr, false, xf));
+    o.stat_part = fused_parts ? part : nullptr;
+    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     const int prow = fused_parts ? M / fused_parts : 0;                    // rows per statistics panel
     const bool gsum_fin = group_ysum && training && fused_parts && M % fused_parts == 0 && rows_per_group % prow == 0;
     if (training) {
@@ -510,9 +501,7 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
     double* part = (has_bn || dbias) ? w.take<double>((size_t)nparts * 2 * Cout) : nullptr;
     float* mean_dz = has_bn ? w.take<float>(Cout) : nullptr;
     float* mean_dzy = has_bn ? w.take<float>(Cout) : nullptr;
-    size_t sf1 = dX ? gemm_slab_floats(M, Cin, Cout) : 0, sf2 = gemm_slab_floats(Cout, Cin, M);
-    size_t sf = sf1 > sf2 ? sf1 : sf2;
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, dX ? gemm_slab_floats(M, Cin, Cout) : 0, gemm_slab_floats(Cout, Cin, M));
     float* gscratch = dgbias ? w.take<float>((size_t)n_groups * 16 * Cout) : nullptr;
     float* coef = has_bn ? w.take<float>((size_t)4 * Cout) : nullptr;      // c0 | nk2 | sc | max |d'| (bn.hip bn_bwd_finalize_coef_kernel)
     const float* Xorig = X; const int ldx_orig = ldx;   // the previous layer's pre-BN output (fused statistics read it as it is)
@@ -555,12 +544,9 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
     } else if (has_bn) {
         const float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
         // (the per-cloud bias gradient -- column sums of dY per cloud -- comes out of the same pass when the shape allows)
-        bn_zero_vec_request(zb);
-        const int rcb = launch_bn_act_bwd(st, dZ, Y, dY, M, Cout, scale, shift, mean, invstd, training, act, slope,
-                                          training ? p_drop : 0.f, seed, part, dgamma, dbeta, mean_dz, mean_dzy, dgbias ? gscratch : nullptr,
-                                          rows_per_group, &g_slabs, pre_stats, pre_parts);
-        dbias_zeroed = bn_zero_vec_take();
-        if (rcb != MLSP_OK) return rcb;
+        CHECK(launch_bn_act_bwd(st, dZ, Y, dY, M, Cout, scale, shift, mean, invstd, training, act, slope, training ? p_drop : 0.f, seed, part,
+                                dgamma, dbeta, mean_dz, mean_dzy, zb, dgbias ? gscratch : nullptr, rows_per_group, &g_slabs, pre_stats, pre_parts));
+        dbias_zeroed = zb != nullptr;
         g = dY;
     }
     GemmBs bs_s; const GemmBs* bs = nullptr;
@@ -575,10 +561,10 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
         // gradient buffer) and weight gradient in one launch (skinny.hip)
         CHECK(launch_skinny_bwd_pair(st, g, Cout, W, ldw, X, ldx, dX, lddx, dW, M, Cin, Cout, dx_accumulate));
     } else {
-    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, g, Cout, W, ldw, dX, lddx, nullptr, nullptr, 0, slab, sf, nullptr, nullptr,
-                              nullptr, nullptr, dx_accumulate != 0, nullptr, 0, nullptr, bs, dy));
-    CHECK(launch_gemm(st, true, false, Cout, Cin, M, g, Cout, X, ldx, dW, Cin, nullptr, nullptr, 0, slab, sf, nullptr, nullptr, nullptr,
-                      nullptr, false, xf, 0, nullptr, nullptr, dy));
+    GemmOpts od = so; od.accumulate = dx_accumulate != 0; od.bs = bs; od.dy = dy;
+    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, g, Cout, W, ldw, dX, lddx, od));
+    GemmOpts ow = so; ow.xf = xf; ow.dy = dy;
+    CHECK(launch_gemm(st, true, false, Cout, Cin, M, g, Cout, X, ldx, dW, Cin, ow));
     }
     if (dbias) {
         if (has_bn && training) {
@@ -646,11 +632,11 @@ int mlsp_pointmlp_segmax_fwd_f32(const float* X, int ldx, int M, int Cin, const 
     const int fused_parts = training ? gemm_stat_parts(M, Cout, Cin) : 0;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(M);
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
-    size_t sf = gemm_slab_floats(M, Cout, Cin);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts o; o.bias = bias; o.stat_part = fused_parts ? part : nullptr;
+    take_slab(w, o, gemm_slab_floats(M, Cout, Cin));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
-    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, bias, nullptr, 0, slab, sf, fused_parts ? part : nullptr));
+    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     if (training) {
         if (!fused_parts) CHECK(launch_colstats(st, Y, M, Cout, Cout, part));
         CHECK(launch_bn_finalize(st, part, nparts, (double)M, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale, shift, mean, invstd));
@@ -676,9 +662,7 @@ int mlsp_pointmlp_segmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     double* part = w.take<double>((size_t)npr * 2 * Cout);
     float* mean_dz = w.take<float>(Cout);
     float* mean_dzy = w.take<float>(Cout);
-    size_t sf1 = dX ? gemm_slab_floats(M, Cin, Cout) : 0, sf2 = gemm_slab_floats(Cout, Cin, M);
-    size_t sf = sf1 > sf2 ? sf1 : sf2;
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, dX ? gemm_slab_floats(M, Cin, Cout) : 0, gemm_slab_floats(Cout, Cin, M));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     const float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
     // sums of dz' and dz'*yhat over ALL M rows == over the G x Cout selected entries (every other row's dz is zero)
@@ -688,8 +672,8 @@ int mlsp_pointmlp_segmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     }
     CHECK(launch_bn_bwd_finalize(st, part, npr, (double)M, Cout, dgamma, dbeta, mean_dz, mean_dzy));
     CHECK(launch_segsel_bwd_apply(st, dOut, Y, ysel, argk, (size_t)M, k, Cout, bn_save, training ? mean_dz : nullptr, mean_dzy, act, slope, dY));
-    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, dY, Cout, W, ldw, dX, lddx, nullptr, nullptr, 0, slab, sf));
-    CHECK(launch_gemm(st, true, false, Cout, Cin, M, dY, Cout, X, ldx, dW, Cin, nullptr, nullptr, 0, slab, sf));
+    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, dY, Cout, W, ldw, dX, lddx, so));
+    CHECK(launch_gemm(st, true, false, Cout, Cin, M, dY, Cout, X, ldx, dW, Cin, so));
     if (dbias) {
         if (training) {                                        // a bias in front of a batch-statistics BatchNorm: analytically zero gradient
             hipError_t e = hipMemsetAsync(dbias, 0, (size_t)Cout * sizeof(float), st);
@@ -730,8 +714,8 @@ int mlsp_pointmlp_fwd_mx(const void* X, int x_bf16, int ldx, int M, int Cin, con
     double* part = w.take<double>((size_t)(fused_parts ? fused_parts : 1) * 2 * Cout);
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
-    CHECK(launch_gemm_mx(st, false, true, M, Cout, Cin, X, x_bf16, ldx, W, 0, ldw, Y, out_bf16, Cout, bias, gbias, rows_per_group, nullptr, 0,
-                         fused_parts ? part : nullptr, false));
+    GemmOpts o; o.bias = bias; o.gbias = gbias; o.rows_per_group = rows_per_group; o.stat_part = fused_parts ? part : nullptr;
+    CHECK(launch_gemm_mx(st, false, true, M, Cout, Cin, X, x_bf16, ldx, W, 0, ldw, Y, out_bf16, Cout, o));
     if (training) {
         CHECK(launch_bn_finalize(st, part, fused_parts, (double)M, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale, shift,
                                  mean, invstd));
@@ -758,25 +742,19 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
     float* mean_dz = w.take<float>(Cout);
     float* mean_dzy = w.take<float>(Cout);
-    const size_t sf = gemm_slab_floats(Cout, Cin, M);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts ow; take_slab(w, ow, gemm_slab_floats(Cout, Cin, M));
     float* gscratch = dgbias ? w.take<float>((size_t)n_groups * 16 * Cout) : nullptr;
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     const float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
-    bn_zero_vec_request(dbias);       // (a bias in front of a batch-stat BN: zero gradient, written by the finalizer of the pass below)
-    const int rcb = out_bf16 ? launch_bn_act_bwd_b16(st, dZ, Y, dY, M, Cout, scale, shift, mean, invstd, training, act, slope, training ? p_drop : 0.f, seed,
-                                                     part, dgamma, dbeta, mean_dz, mean_dzy)
-                             : launch_bn_act_bwd(st, (const float*)dZ, (const float*)Y, (float*)dY, M, Cout, scale, shift, mean, invstd, training, act, slope,
-                                                 training ? p_drop : 0.f, seed, part, dgamma, dbeta, mean_dz, mean_dzy);
-    const bool dbias_zeroed = bn_zero_vec_take();
-    if (rcb != MLSP_OK) return rcb;
-    if (dX) CHECK(launch_gemm_mx(st, false, false, M, Cin, Cout, dY, out_bf16, Cout, W, 0, ldw, dX, x_bf16, lddx, nullptr, nullptr, 0, nullptr, 0,
-                                 nullptr, dx_accumulate != 0));
-    CHECK(launch_gemm_mx(st, true, false, Cout, Cin, M, dY, out_bf16, Cout, X, x_bf16, ldx, dW, 0, Cin, nullptr, nullptr, 0, slab, sf, nullptr, false));
-    if (dbias && !dbias_zeroed) {     // a bias in front of a batch-stat BN has an analytically zero gradient (sum_rows dY == 0)
-        hipError_t e = hipMemsetAsync(dbias, 0, (size_t)Cout * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
-    }
+    // (dbias -- training mode only, see above: a bias in front of a batch-stat BN has an analytically zero gradient, sum_rows dY == 0 --
+    // is written by the finalizer of either pass)
+    if (out_bf16) CHECK(launch_bn_act_bwd_b16(st, dZ, Y, dY, M, Cout, scale, shift, mean, invstd, training, act, slope, training ? p_drop : 0.f, seed,
+                                              part, dgamma, dbeta, mean_dz, mean_dzy, dbias));
+    else CHECK(launch_bn_act_bwd(st, (const float*)dZ, (const float*)Y, (float*)dY, M, Cout, scale, shift, mean, invstd, training, act, slope,
+                                 training ? p_drop : 0.f, seed, part, dgamma, dbeta, mean_dz, mean_dzy, dbias));
+    GemmOpts od; od.accumulate = dx_accumulate != 0;
+    if (dX) CHECK(launch_gemm_mx(st, false, false, M, Cin, Cout, dY, out_bf16, Cout, W, 0, ldw, dX, x_bf16, lddx, od));
+    CHECK(launch_gemm_mx(st, true, false, Cout, Cin, M, dY, out_bf16, Cout, X, x_bf16, ldx, dW, 0, Cin, ow));
     if (dgbias) {
         if (out_bf16) CHECK(launch_colsum_groups_b16(st, dY, n_groups, rows_per_group, Cout, dgbias, gscratch));
         else CHECK(launch_colsum_groups(st, (const float*)dY, n_groups, rows_per_group, Cout, dgbias, gscratch));
@@ -803,11 +781,10 @@ int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin,
     int* pr = fuse_sel ? w.take<int>((size_t)ntm * Cout) : nullptr;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(P);
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
-    size_t sf = gemm_slab_floats(P, Cout, Cin);
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts o; o.stat_part = fused_parts ? part : nullptr; o.sel_gamma = fuse_sel ? gamma : nullptr; o.sel_val = pv; o.sel_row = pr;
+    take_slab(w, o, gemm_slab_floats(P, Cout, Cin));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
-    CHECK(launch_gemm(st, false, true, P, Cout, Cin, X, ldx, W, ldw, Y, Cout, nullptr, nullptr, 0, slab, sf,
-                      fused_parts ? part : nullptr, fuse_sel ? gamma : nullptr, pv, pr));
+    CHECK(launch_gemm(st, false, true, P, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     if (training) {
         if (!fused_parts) CHECK(launch_colstats(st, Y, P, Cout, Cout, part));
         CHECK(launch_bn_finalize(st, part, nparts, (double)P, Cout, gamma, beta, run_mean, run_var, momentum, eps, bn_save,
@@ -844,19 +821,16 @@ int mlsp_pointmlp_colmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     float* Wb = w.take<float>((size_t)Cout * Cin);
     float* Mneg = w.take<float>((size_t)Cin * Cin);
     float* negr = w.take<float>(Cin);
-    size_t sf = gemm_slab_floats(Cin, Cin, P), s2 = gemm_slab_floats(Cout, Cin, Cin), s3 = gemm_slab_floats(Cin, Cin, Cout),
-           s4 = gemm_slab_floats(P, Cin, Cin);
-    if (s2 > sf) sf = s2;
-    if (s3 > sf) sf = s3;
-    if (s4 > sf) sf = s4;
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    const size_t s1 = gemm_slab_floats(Cin, Cin, P), s2 = gemm_slab_floats(Cout, Cin, Cin), s3 = gemm_slab_floats(Cin, Cin, Cout),
+                 s4 = gemm_slab_floats(P, Cin, Cin);
+    GemmOpts so; take_slab(w, so, s1 > s2 ? s1 : s2, s3 > s4 ? s3 : s4);
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     CHECK(launch_colmax_bwd_coef(st, dOut, out, ysel, bn_save, B, Cout, (double)P, act, slope, training, g, coef, dgamma, dbeta));
     CHECK(launch_colmax_gather_rows(st, g, arg, X, ldx, B, N, Cout, Cin, S));
     if (training) {
         CHECK(launch_colsum(st, X, P, Cin, part, sx));
-        CHECK(launch_gemm(st, true, false, Cin, Cin, P, X, ldx, X, ldx, G, Cin, nullptr, nullptr, 0, slab, sf));
-        CHECK(launch_gemm(st, false, false, Cout, Cin, Cin, W, ldw, G, Cin, WG, Cin, nullptr, nullptr, 0, slab, sf));
+        CHECK(launch_gemm(st, true, false, Cin, Cin, P, X, ldx, X, ldx, G, Cin, so));
+        CHECK(launch_gemm(st, false, false, Cout, Cin, Cin, W, ldw, G, Cin, WG, Cin, so));
         CHECK(launch_colmax_dw(st, S, WG, sx, coef, bn_save, Cout, Cin, dW));
     } else {
         hipError_t e = hipMemcpyAsync(dW, S, (size_t)Cout * Cin * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -865,9 +839,9 @@ int mlsp_pointmlp_colmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     if (dX) {
         if (training) {
             CHECK(launch_wt_vec_neg_scale_rows(st, W, ldw, coef + 2 * Cout, coef + 3 * Cout, Cout, Cin, negr, Wb));    // negr; Wb = -Bc * W
-            CHECK(launch_gemm(st, true, false, Cin, Cin, Cout, Wb, Cin, W, ldw, Mneg, Cin, nullptr, nullptr, 0, slab, sf));
-            CHECK(launch_gemm(st, false, false, P, Cin, Cin, X, ldx, Mneg, Cin, dX, Cin, negr, nullptr, 0, slab, sf, nullptr, nullptr,
-                              nullptr, nullptr, dx_accumulate != 0));
+            CHECK(launch_gemm(st, true, false, Cin, Cin, Cout, Wb, Cin, W, ldw, Mneg, Cin, so));
+            GemmOpts od = so; od.bias = negr; od.accumulate = dx_accumulate != 0;
+            CHECK(launch_gemm(st, false, false, P, Cin, Cin, X, ldx, Mneg, Cin, dX, Cin, od));
         } else if (!dx_accumulate) {
             hipError_t e = hipMemsetAsync(dX, 0, (size_t)P * Cin * sizeof(float), st);
             if (e != hipSuccess) return (int)e;

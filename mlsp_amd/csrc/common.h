@@ -101,6 +101,25 @@ struct GemmDy { const float* y; const float* coef; int cld; int amax = 0; };    
 // B = Bg[g] = W_g; dgrad alike); mode 2: output ROWS are grouped (wgrad: B = X + g * b_gs; A and C take the launch-wide row index).
 struct GemmGroups { int G, mode; long a_gs, b_gs; const float* Bg[4]; };
 
+// What launch_gemm / launch_gemm_mx take behind C, ldc: a call site fills a local by field name, every field defaults to "absent".
+struct GemmOpts {
+    const float* bias = nullptr;                        // C[r][c] += bias[c]
+    const float* gbias = nullptr; int rows_per_group = 0;       // C[r][c] += gbias[r / rows_per_group][c] (per-cloud bias rows)
+    float* slab = nullptr; size_t slab_floats = 0;      // split-K partial sums (gemm_slab_floats); absent / too small: one pass
+    double* stat_part = nullptr; int stat_ld = 0;       // BatchNorm column sums per row panel from the epilogue (gemm_stat_parts); stat_ld: see launch_gemm
+    const float* sel_gamma = nullptr; float* sel_val = nullptr; int* sel_row = nullptr;   // per-panel column extremes instead of C (colmax.hip)
+    bool accumulate = false;                            // C += product (beta = 1; one pass)
+    const GemmXf* xf = nullptr; const GemmGroups* grp = nullptr; const GemmBs* bs = nullptr; const GemmDy* dy = nullptr;
+    // an EdgeConv weight gradient (C = dWd [2 Cout][N]): a split-K reduce may sum its slabs straight into the reference layout unfold_dw
+    // [Cout][2 N] and leave C unwritten (gemm.hip splitk_reduce_unfold_kernel); *unfolded (nullable) <- whether it did
+    float* unfold_dw = nullptr; bool* unfolded = nullptr;
+};
+// carve the split-K slab that a call's launches share, sized for the larger of two shapes' gemm_slab_floats; a failed take shows in w.ok()
+static inline void take_slab(Workspace& w, GemmOpts& o, size_t a, size_t b = 0) {
+    o.slab_floats = a > b ? a : b;
+    o.slab = o.slab_floats ? w.take<float>(o.slab_floats) : nullptr;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1390,14 +1390,6 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __re
     }
 }
 
-static void launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int ns, const float* bias,
-                                     const float* gbias, int rows_per_group);
-
-int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit) {
-    launch_splitk_reduce_any(st, slab, C, M, N, ldc, nsplit, nullptr, nullptr, 0);
-    return mlsp_launch_status();
-}
-
 // vectorised slab reduce (contiguous C only): 16 bytes per lane.  A workgroup covers 256/ZG consecutive float4 outputs;
 // its ZG thread groups each sum the slabs z = g, g+ZG, ... (8 loads in flight), then the groups are added in order through
 // LDS.  The order is fixed by (nsplit, ZG) alone -> bitwise reproducible.
@@ -1497,20 +1489,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_unfold_kernel(const float* 
     out[0] = su - sv;
     out[C4] = sv;
 }
-// request of the NEXT split-K reduction on this thread (launch_gemm of an EdgeConv weight gradient): consumed by launch_splitk_reduce_any,
-// which clears it; gemm_unfold_take() tells the caller whether the reduce did the unfold (a launch without K splits did not)
-static thread_local float* tl_unfold_dw = nullptr;
-static thread_local bool tl_unfold_done = false;
-void gemm_unfold_request(float* dW) { tl_unfold_dw = dW; tl_unfold_done = false; }
-bool gemm_unfold_take() { const bool d = tl_unfold_done; tl_unfold_dw = nullptr; tl_unfold_done = false; return d; }
-
-static void launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int ns, const float* bias,
-                                     const float* gbias, int rows_per_group) {
+// dW (nullable; common.h GemmOpts): where the shape allows, the sums go there through the kernel above and C stays unwritten.
+// -> whether they did
+static bool launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int ns, const float* bias,
+                                     const float* gbias, int rows_per_group, float* dW = nullptr) {
     size_t total = (size_t)M * N;
     const bool vec = (N % 4 == 0) && ldc == N && ((((uintptr_t)slab | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)gbias) & 15) == 0);
-    if (tl_unfold_dw && vec && !bias && !gbias && M % 2 == 0 && (((uintptr_t)tl_unfold_dw) & 15) == 0) {
-        float* dW = tl_unfold_dw;
-        tl_unfold_dw = nullptr; tl_unfold_done = true;
+    if (dW && vec && !bias && !gbias && M % 2 == 0 && (((uintptr_t)dW) & 15) == 0) {
         const size_t h4 = total / 8;
         if (ns >= 32 && 2 * h4 <= 64 * 1024)
             hipLaunchKernelGGL((splitk_reduce_unfold_kernel<8>), dim3((unsigned)((h4 + 31) / 32)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
@@ -1518,9 +1503,8 @@ static void launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C
             hipLaunchKernelGGL((splitk_reduce_unfold_kernel<4>), dim3((unsigned)((h4 + 63) / 64)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
         else
             hipLaunchKernelGGL((splitk_reduce_unfold_kernel<1>), dim3((unsigned)((h4 + 255) / 256)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
-        return;
+        return true;
     }
-    tl_unfold_dw = nullptr;
     if (vec) {
         size_t t4 = total / 4;
         // enough workgroups to fill the chip: more slab groups per workgroup when the output is small
@@ -1537,6 +1521,12 @@ static void launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C
         int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group);
     }
+    return false;
+}
+int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit, float* unfold_dw, bool* unfolded) {
+    const bool u = launch_splitk_reduce_any(st, slab, C, M, N, ldc, nsplit, nullptr, nullptr, 0, unfold_dw);
+    if (unfolded) *unfolded = u;
+    return mlsp_launch_status();
 }
 
 // How many K splits a launch will use (shared by the launcher and mlsp_workspace_bytes).
@@ -1765,9 +1755,12 @@ bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which) {
 }
 
 int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B,
-                int ldb, float* C, int ldc, const float* bias, const float* gbias, int rows_per_group, float* slab,
-                size_t slab_floats, double* stat_part, const float* sel_gamma, float* sel_val, int* sel_row, bool accumulate,
-                const GemmXf* xf, int stat_ld, const GemmGroups* grp, const GemmBs* bs, const GemmDy* dy) {
+                int ldb, float* C, int ldc, const GemmOpts& o) {
+    const float* const bias = o.bias; const float* const gbias = o.gbias; const int rows_per_group = o.rows_per_group;
+    float* const slab = o.slab; const size_t slab_floats = o.slab_floats; double* const stat_part = o.stat_part; const int stat_ld = o.stat_ld;
+    const float* const sel_gamma = o.sel_gamma; float* const sel_val = o.sel_val; int* const sel_row = o.sel_row; const bool accumulate = o.accumulate;
+    const GemmXf* const xf = o.xf; const GemmGroups* const grp = o.grp; const GemmBs* const bs = o.bs; const GemmDy* const dy = o.dy;
+    if (o.unfolded) *o.unfolded = false;
     // grp (nullable): block-diagonal product in one launch (GemmArgs groups; M / N are the LAUNCH's dimensions, K one group's).
     // Only on the interior-tile fp32 kernel: MLSP_ERR_UNSUPPORTED otherwise (nothing launched; the caller launches group by group).
     // stat_ld (0: N): C is a column slice of a [M][stat_ld] matrix whose BatchNorm statistics are taken as ONE vector (multi.hip):
@@ -1782,7 +1775,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
                (xf && xf->which != 2) || !gemm_dy_supported(ta, tb, M, N, K, A, lda, B, ldb)))
         return MLSP_ERR_UNSUPPORTED;                                         // nothing launched: the caller runs the streaming apply pass
     if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && (!xf || tl_call_precision != 1)) {
-        const int rc = launch_thin_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, slab, slab_floats, xf, bs);
+        const int rc = launch_thin_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, o);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
     if (xf && !gemm_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, xf->which)) return MLSP_ERR_UNSUPPORTED;   // nothing launched: caller materialises
@@ -1792,7 +1785,8 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         if (slab && slab_floats >= inner + 128 * 128) {
             float* C2 = slab + inner;
             const size_t used0 = g_prof.used;
-            const int rc = launch_gemm(st, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, nullptr, nullptr, 0, slab, inner);
+            GemmOpts oi; oi.slab = slab; oi.slab_floats = inner;      // (C2 is not the caller's C: no unfold_dw)
+            const int rc = launch_gemm(st, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, oi);
             if (rc != MLSP_OK) return rc;
             if (g_prof.used == used0 + 1) {              // the profiler prices the ALGORITHMIC contraction (64 x 64 x K), not the folded one
                 auto& r = g_prof.rec[used0];
@@ -2005,7 +1999,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         g_prof.flop += 2.0 * M * (double)N * K;
         g_prof.bytes += 4.0 * ((double)M * K + (double)K * N + (C ? (double)M * N : 0.0));
     }
-    if (ns > 1) launch_splitk_reduce_any(st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group);
+    if (ns > 1 && launch_splitk_reduce_any(st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group, o.unfold_dw) && o.unfolded) *o.unfolded = true;
     return mlsp_launch_status();
 }
 
@@ -2017,23 +2011,23 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
 // Only interior-tile shapes (M % tile, N % 128, K % 32 == 0, 16-byte aligned rows): MLSP_ERR_UNSUPPORTED otherwise, and the caller keeps
 // that layer in fp32.  Same BN-statistics / bias / per-cloud-bias / beta = 1 epilogues; the statistics come from the fp32 accumulators.
 int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16,
-                   int ldb, void* C, int c_bf16, int ldc, const float* bias, const float* gbias, int rows_per_group, float* slab,
-                   size_t slab_floats, double* stat_part, bool accumulate) {
-    if (!a_bf16 && !b_bf16 && !c_bf16)
-        return launch_gemm(st, ta, tb, M, N, K, (const float*)A, lda, (const float*)B, ldb, (float*)C, ldc, bias, gbias, rows_per_group,
-                           slab, slab_floats, stat_part, nullptr, nullptr, nullptr, accumulate);
+                   int ldb, void* C, int c_bf16, int ldc, const GemmOpts& o) {
+    if (!a_bf16 && !b_bf16 && !c_bf16) return launch_gemm(st, ta, tb, M, N, K, (const float*)A, lda, (const float*)B, ldb, (float*)C, ldc, o);
+    // what the bf16 path does not implement (nothing launched)
+    if (o.sel_gamma || o.sel_val || o.sel_row || o.xf || o.grp || o.bs || o.dy || o.unfold_dw || o.stat_ld) return MLSP_ERR_UNSUPPORTED;
+    if (o.unfolded) *o.unfolded = false;
     if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return MLSP_ERR_ARG;
-    if (gbias && rows_per_group <= 0) return MLSP_ERR_ARG;
+    if (o.gbias && o.rows_per_group <= 0) return MLSP_ERR_ARG;
     GemmArgs p;
-    p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.bias = bias; p.gbias = gbias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.rows_per_group = rows_per_group;
+    p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.bias = o.bias; p.gbias = o.gbias;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.rows_per_group = o.rows_per_group;
     int ns = gemm_pick_split(M, N, K);
-    if (ns > 1 && (!slab || slab_floats < (size_t)ns * M * N)) ns = 1;
-    if (accumulate) ns = 1;
+    if (ns > 1 && (!o.slab || o.slab_floats < (size_t)ns * M * N)) ns = 1;
+    if (o.accumulate) ns = 1;
     if (ns > 1 && c_bf16) return MLSP_ERR_UNSUPPORTED;                   // a split result is reduced in fp32
-    if (stat_part && ns != 1) return MLSP_ERR_ARG;
-    p.accumulate = accumulate ? 1 : 0; p.c_bf16 = c_bf16; p.fast_out = 0;
-    p.stat_part = stat_part; p.stat_ld = N; p.sel_gamma = nullptr; p.sel_val = nullptr; p.sel_row = nullptr;
+    if (o.stat_part && ns != 1) return MLSP_ERR_ARG;
+    p.accumulate = o.accumulate ? 1 : 0; p.c_bf16 = c_bf16; p.fast_out = 0;
+    p.stat_part = o.stat_part; p.stat_ld = N; p.sel_gamma = nullptr; p.sel_val = nullptr; p.sel_row = nullptr;
     const int ktiles = (K + BK - 1) / BK;
     const int kts = (ktiles + ns - 1) / ns;
     ns = (ktiles + kts - 1) / kts;
@@ -2044,9 +2038,9 @@ int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const 
     p.a_vec = a_ok && (((uintptr_t)A & 15) == 0);
     p.b_vec = b_ok && (((uintptr_t)B & 15) == 0);
     const bool nedge = (N % BN != 0);
-    if (nedge && !(!tb && !b_bf16 && N % 4 == 0 && !stat_part && !(c_bf16 && ns > 1))) return MLSP_ERR_UNSUPPORTED;   // k-major fp32 B only
+    if (nedge && !(!tb && !b_bf16 && N % 4 == 0 && !o.stat_part && !(c_bf16 && ns > 1))) return MLSP_ERR_UNSUPPORTED;   // k-major fp32 B only
     if (!(p.a_vec && p.b_vec && M % bm == 0 && K % BK == 0)) return MLSP_ERR_UNSUPPORTED;
-    if (ns > 1) { p.C = slab; p.ldc = N; }
+    if (ns > 1) { p.C = o.slab; p.ldc = N; }
     p.xcd_map = p.ntm >= 16 && p.ntn > 1;
     dim3 grid(p.xcd_map ? ((p.ntm + 7) / 8) * 8 * p.ntn : p.ntm * p.ntn, ns);
     const bool prof = g_prof.on && g_prof.used < PROF_MAX_PAIRS;
@@ -2081,11 +2075,11 @@ int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const 
 #undef MX_GO
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
-        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (stat_part ? 1 : 0) + 4, 0, 0};
+        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (o.stat_part ? 1 : 0) + 4, 0, 0};
         g_prof.used++;
         g_prof.flop += 2.0 * M * (double)N * K;
         g_prof.bytes += (a_bf16 ? 2.0 : 4.0) * M * K + (b_bf16 ? 2.0 : 4.0) * K * N + (c_bf16 ? 2.0 : 4.0) * M * N;
     }
-    if (ns > 1) launch_splitk_reduce_any(st, slab, (float*)C, M, N, ldc, ns, bias, gbias, rows_per_group);
+    if (ns > 1) launch_splitk_reduce_any(st, o.slab, (float*)C, M, N, ldc, ns, o.bias, o.gbias, o.rows_per_group);
     return mlsp_launch_status();
 }

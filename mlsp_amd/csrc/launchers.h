@@ -15,9 +15,9 @@ int gemm_precision_mode();   // the product mode of the entry point this thread 
 // of an output of this call with room for `need` floats.  null: nothing to fill
 float* amax_reserve(const float* X, long rows, int cols, int ld);
 float* amax_offered_output(const float* out, long rows, int cols, int ld, int need);
-int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit);
-void gemm_unfold_request(float* dW);   // for the NEXT split-K reduction on this thread; take(): did that reduction do the unfold?
-bool gemm_unfold_take();
+// unfold_dw / unfolded (nullable): common.h GemmOpts
+int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit, float* unfold_dw = nullptr,
+                       bool* unfolded = nullptr);
 int gemm_stat_parts(int M, int N, int K);
 int gemm_panel_rows(int M, int N, int K);
 size_t gemm_slab_floats(int M, int N, int K);
@@ -29,13 +29,9 @@ int gemm_bs_parts(int M, int N, int K, int lda, int ldb, int ldc);
 bool gemm_dy_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb);
 bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which);
 int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                const float* bias, const float* gbias, int rows_per_group, float* slab, size_t slab_floats, double* stat_part = nullptr,
-                const float* sel_gamma = nullptr, float* sel_val = nullptr, int* sel_row = nullptr, bool accumulate = false,
-                const GemmXf* xf = nullptr, int stat_ld = 0, const GemmGroups* grp = nullptr, const GemmBs* bs = nullptr,
-                const GemmDy* dy = nullptr);
+                const GemmOpts& o = GemmOpts());
 int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16, int ldb,
-                   void* C, int c_bf16, int ldc, const float* bias, const float* gbias, int rows_per_group, float* slab, size_t slab_floats,
-                   double* stat_part, bool accumulate);
+                   void* C, int c_bf16, int ldc, const GemmOpts& o = GemmOpts());
 
 // knn.hip
 // xx_ws: [B*N] floats of workspace; planes (nullable): knn6_plane_bytes(B*N, C) bytes of workspace for the v6 kernel's bf16 images
@@ -62,9 +58,10 @@ int bn_stat_parts(int M);
 int bn_parts_max(int M);
 int launch_colstats_n(hipStream_t st, const float* Y, int M, int C, int ld, double* part, int* nparts_out);
 int launch_colstats(hipStream_t st, const float* Y, int M, int C, int ld, double* part);
-void bn_bound_request(float* out);
+// bound_out (nullable, [C]): also write the channels' output bounds |gamma| sqrt(count) + |beta| (a slot of amax_offered_output)
 int launch_bn_finalize(hipStream_t st, const double* part, int nparts, double count, int C, const float* gamma, const float* beta, float* run_mean,
-                       float* run_var, float momentum, float eps, float* scale, float* shift, float* save_mean, float* save_invstd);
+                       float* run_var, float momentum, float eps, float* scale, float* shift, float* save_mean, float* save_invstd,
+                       float* bound_out = nullptr);
 int launch_bn_finalize_groups(hipStream_t st, const double* part, int nparts, double count, int C, const float* gamma, const float* beta,
                               float* run_mean, float* run_var, float momentum, float eps, float* scale, float* shift, float* save_mean,
                               float* save_invstd, float* gsum, int ppg);
@@ -72,10 +69,12 @@ int launch_bn_eval_prepare(hipStream_t st, int C, const float* gamma, const floa
                            float* scale, float* shift, float* save_mean, float* save_invstd);
 int launch_bn_act_fwd(hipStream_t st, const float* Y, float* Z, size_t rows, int C, const float* scale, const float* shift, int act, float slope,
                       float p_drop, uint64_t seed);
+// zero_vec (nullable, [C]; also launch_bn_act_bwd_b16, launch_skinny_bn_bwd_z and the *_z finalizers): the gradient of a bias in front of a
+// batch-statistics BatchNorm, zero-filled by the pass's finalizer -- every MLSP_OK return has written it
 int launch_bn_act_bwd(hipStream_t st, const float* dZ, const float* Y, float* dY, int M, int C, const float* scale, const float* shift,
                       const float* mean, const float* invstd, int training, int act, float slope, float p_drop, uint64_t seed, double* part,
-                      float* dgamma, float* dbeta, float* mean_dz, float* mean_dzy, float* gpart = nullptr, int rows_per_group = 0,
-                      int* gpart_slabs = nullptr, const double* pre_stats = nullptr, int pre_parts = 0);
+                      float* dgamma, float* dbeta, float* mean_dz, float* mean_dzy, float* zero_vec, float* gpart = nullptr,
+                      int rows_per_group = 0, int* gpart_slabs = nullptr, const double* pre_stats = nullptr, int pre_parts = 0);
 int launch_bn_bwd_finalize_coef_z(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
                                   float* dbeta, float* coef, float* zero_vec);
 int launch_bn_bwd_finalize_coef_groups(hipStream_t st, const double* part, int nparts, double count, int C, const float* bn_save, float* dgamma,
@@ -101,11 +100,9 @@ int launch_segsel_bwd_apply(hipStream_t st, const float* dOut, const float* Y, c
 int launch_segmax_bwd(hipStream_t st, const float* dOut, const uint8_t* argk, int P, int k, int C, float* dZ);
 int launch_bn_act_fwd_b16(hipStream_t st, const void* Y, void* Z, int rows, int C, const float* scale, const float* shift, int act, float slope,
                           float p_drop, uint64_t seed);
-void bn_zero_vec_request(float* v);
-bool bn_zero_vec_take();
 int launch_bn_act_bwd_b16(hipStream_t st, const void* dZ, const void* Y, void* dY, int M, int C, const float* scale, const float* shift,
                           const float* mean, const float* invstd, int training, int act, float slope, float p_drop, uint64_t seed, double* part,
-                          float* dgamma, float* dbeta, float* mean_dz, float* mean_dzy);
+                          float* dgamma, float* dbeta, float* mean_dz, float* mean_dzy, float* zero_vec);
 int launch_colsum_groups_b16(hipStream_t st, const void* X, int G, int rows_per_group, int C, float* out, float* scratch);
 
 // edge.hip
@@ -241,8 +238,9 @@ int launch_transform3_bwd(hipStream_t st, const float* x, const float* T, const 
 // thin.hip
 size_t thin_tn_slab_floats(int M, int N, int K);
 int thin_bs_parts(int M, int N, int K);
+// reads o.bias, slab, slab_floats, xf, bs, unfold_dw, unfolded; launch_gemm keeps a launch with any other field set away from it
 int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                     const float* bias, float* slab, size_t slab_floats, const GemmXf* xf, const GemmBs* bs = nullptr);
+                     const GemmOpts& o);
 bool thin_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which);
 
 // multi.hip

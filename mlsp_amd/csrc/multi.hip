@@ -313,7 +313,7 @@ int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs
     double* part = w.take<double>((size_t)(npmax > (M + 255) / 256 ? npmax : (M + 255) / 256) * 2 * Ctot);
     size_t sf = 0;                                             // (small M: a segment's GEMM may split K; then the statistics are a separate pass)
     for (int s = 0; s < nseg; s += run[s]) { const size_t f = gemm_slab_floats(M, run[s] * segs[s].Cout, segs[s].Cin); sf = f > sf ? f : sf; }
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, sf);
     float* Xa = any_mat ? w.take<float>((size_t)M * ldx) : nullptr;     // activated copies of the slices whose GEMM cannot transform (same layout as X)
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     int ycol = 0;
@@ -334,8 +334,8 @@ int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs
                 Xs = Xa;
             }
         }
-        MCHECK(launch_gemm(st, false, true, M, run[s] * g.Cout, g.Cin, Xs + g.x_col, ldx, g.W, g.ldw, Y + ycol, Ctot, g.bias, nullptr, 0, slab, sf,
-                           fused ? part + ycol : nullptr, nullptr, nullptr, nullptr, false, xf, Ctot, run[s] > 1 ? &grp : nullptr));
+        GemmOpts o = so; o.bias = g.bias; o.stat_part = fused ? part + ycol : nullptr; o.stat_ld = Ctot; o.xf = xf; o.grp = run[s] > 1 ? &grp : nullptr;
+        MCHECK(launch_gemm(st, false, true, M, run[s] * g.Cout, g.Cin, Xs + g.x_col, ldx, g.W, g.ldw, Y + ycol, Ctot, o));
         ycol += run[s] * g.Cout;
     }
     float* scale = bn_save, *shift = bn_save + Ctot, *mean = bn_save + 2 * Ctot, *invstd = bn_save + 3 * Ctot;
@@ -418,7 +418,7 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
         const size_t f = gemm_slab_floats(run[s] * segs[s].Cout, segs[s].Cin, M), f2 = dX ? gemm_slab_floats(M, run[s] * segs[s].Cin, segs[s].Cout) : 0;
         sf = f > sf ? f : sf; sf = f2 > sf ? f2 : sf;
     }
-    float* slab = sf ? w.take<float>(sf) : nullptr;
+    GemmOpts so; take_slab(w, so, sf);
     float* Xa = any_mat ? w.take<float>((size_t)M * ldx) : nullptr;
     float* coef = w.take<float>((size_t)4 * Ctot);           // c0 | nk2 | sc | max |d'| (bn.hip bn_bwd_finalize_coef_kernel)
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
@@ -475,8 +475,8 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
                 bs = &bs_s;
                 for (int t = 1; t < G; ++t) if (!multi_defer_same(in[s], in[s + t])) return MLSP_ERR_UNSUPPORTED;     // (one producer description per launch)
             }
-            MCHECK(launch_gemm(st, false, false, M, G * g.Cin, g.Cout, gY + ycol, Ctot, g.W, g.ldw, dX + g.x_col, lddx, nullptr, nullptr, 0, slab, sf,
-                               nullptr, nullptr, nullptr, nullptr, acc, nullptr, 0, G > 1 ? &grp : nullptr, bs, use_dy ? &dy_s : nullptr));
+            GemmOpts od = so; od.accumulate = acc; od.grp = G > 1 ? &grp : nullptr; od.bs = bs; od.dy = use_dy ? &dy_s : nullptr;
+            MCHECK(launch_gemm(st, false, false, M, G * g.Cin, g.Cout, gY + ycol, Ctot, g.W, g.ldw, dX + g.x_col, lddx, od));
         }
         const float* Xs = X;
         GemmXf xf_s; const GemmXf* xf = nullptr;
@@ -492,8 +492,8 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
             }
         }
         GemmGroups grw = {G, 2, 0, g.Cin, {nullptr, nullptr, nullptr, nullptr}};
-        MCHECK(launch_gemm(st, true, false, G * g.Cout, g.Cin, M, gY + ycol, Ctot, Xs + g.x_col, ldx, dW[s], g.Cin, nullptr, nullptr, 0, slab, sf,
-                           nullptr, nullptr, nullptr, nullptr, false, xf, 0, G > 1 ? &grw : nullptr, nullptr, use_dy ? &dy_s : nullptr));
+        GemmOpts ow = so; ow.xf = xf; ow.grp = G > 1 ? &grw : nullptr; ow.dy = use_dy ? &dy_s : nullptr;
+        MCHECK(launch_gemm(st, true, false, G * g.Cout, g.Cin, M, gY + ycol, Ctot, Xs + g.x_col, ldx, dW[s], g.Cin, ow));
         ycol += G * g.Cout;
     }
     if (dbias && !training) MCHECK(launch_colsum(st, dY, M, Ctot, part, dbias));      // (training: zeroed by the finalizer above)

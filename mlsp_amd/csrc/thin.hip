@@ -315,7 +315,8 @@ int thin_bs_parts(int M, int N, int K) {
     return (K <= 16 && N % 4 == 0 && N >= 64 && N <= 512 && M >= 1024 && 256 % (N / 4) == 0 && M % 128 == 0) ? M / 128 : 0;
 }
 int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                     int ldc, const float* bias, float* slab, size_t slab_floats, const GemmXf* xf, const GemmBs* bs) {
+                     int ldc, const GemmOpts& o) {
+    const float* const bias = o.bias; float* const slab = o.slab; const size_t slab_floats = o.slab_floats; const GemmXf* const xf = o.xf; const GemmBs* const bs = o.bs;
     auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     XfDev xd = {nullptr, nullptr, 1.f, 1.f, 0u, 0u, 0, 0};
     if (xf) {
@@ -385,7 +386,7 @@ int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, cons
 #undef THIN_TN
         int rc = mlsp_launch_status();
         if (rc != MLSP_OK) return rc;
-        return launch_slab_reduce(st, slab, C, M, N, ldc, chunks);
+        return launch_slab_reduce(st, slab, C, M, N, ldc, chunks, o.unfold_dw, o.unfolded);      // (an EdgeConv weight gradient with C <= 16 is unfolded here)
     }
     return MLSP_ERR_UNSUPPORTED;
 }

@@ -214,6 +214,28 @@ def test_cross_file_host_functions_are_declared_once_in_launchers_h():
     assert not unused, unused
 
 
+def test_launch_arguments_travel_as_arguments():
+    """The only per-thread state of the kernel library is the per-call context that GemmPrecisionScope guards (product mode, f16x3 flag,
+    operand-bound slots).  What one launch needs -- the EdgeConv weight-gradient unfold, a BatchNorm finalizer's output bounds or zero
+    vector -- is an argument of that launch (common.h GemmOpts), never a thread-local "request" that the next launch on the thread picks
+    up and a "take" reads back."""
+    import glob
+    declared = []
+    for f in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
+        _, src = _file_scope_functions(f)
+        for m in re.finditer(r"\bthread_local\b", src):
+            i, depth, decl = m.end(), 0, ""              # up to the declarator's "=" or ";", over the body of a struct defined in place
+            while depth or src[i] not in ";=":
+                depth += {"{": 1, "}": -1}.get(src[i], 0)
+                decl += src[i] if not depth and src[i] != "}" else " "
+                i += 1
+            declared.append((os.path.basename(f), re.findall(r"\w+", decl)[-1]))
+    assert sorted(declared) == [("gemm.hip", "tl_amax"), ("gemm.hip", "tl_call_precision"), ("gemm.hip", "tl_split_half")], declared
+    header, _ = _file_scope_functions(os.path.join(CSRC, "launchers.h"))
+    channels = [name for name, _ in header if re.search(r"_(request|take)$", name)]
+    assert len(header) >= 100 and not channels, channels
+
+
 def test_forward_bookkeeping_is_per_thread():
     """nn.DataParallel runs one replica per Python thread (PointDA/trainer.py:251-252): the queue of num_batches_tracked
     increments and the forward nesting depth are thread-local, so interleaved forwards of two replicas lose no increment."""
