@@ -497,6 +497,36 @@ int mlsp_sgd_flat_f32(float* P, float* B, const uint32_t* off, const uint32_t* n
                       double momentum, double dampening, double weight_decay, int nesterov, int maximize, int first, float* tile_amax,
                       mlsp_stream_t stream);
 
+/* The edge stages of the vector-attention block (PointDA/hengshuang_transformer/transformer.py:28-44) between its GEMMs (csrc/vecattn.hip).
+ * P = B N points, k slots per point (1 <= k <= 64), E = P k edges, e = (i, s), j = idx[i][s] (int32 [B][N][k], local to the cloud; an
+ * entry may repeat inside a row).  Every [E][d] / [P][d] matrix is fp32, channels contiguous; d % 4 == 0, pointers and row pitches
+ * 16-byte aligned (xyz: any pitch ldx >= 3) -- anything else returns MLSP_ERR_UNSUPPORTED.  No entry reaches a matrix core.
+ * delta_fwd (transformer.py:37, first layer of fc_delta): H1[e][c] = relu(sum_a Wd1[c][a] (xyz_i[a] - xyz_j[a]) + bd1[c]), Wd1 [d][3]. */
+int mlsp_vecattn_delta_fwd_f32(const float* xyz, int ldx, const int32_t* idx, const float* Wd1, const float* bd1, int B, int N, int k, int d,
+                               float* H1, mlsp_stream_t stream);
+/* transformer.py:37 backward: dWd1 [d][3] and dbd1 [d] from dH1 and H1 (mask H1 > 0), summed in a fixed order through the workspace.
+ * No gradient to xyz. */
+int mlsp_vecattn_delta_bwd_f32(const float* dH1, const float* H1, const float* xyz, int ldx, const int32_t* idx, int B, int N, int k, int d,
+                               float* dWd1, float* dbd1, void* ws, size_t ws_bytes, mlsp_stream_t stream);
+/* transformer.py:39, the input of fc_gamma: T[e] = q_i - kk_j + pos[e]; q / kk [P][d] with row pitches ldq / ldk. */
+int mlsp_vecattn_mix_fwd_f32(const float* q, int ldq, const float* kk, int ldk, const float* pos, const int32_t* idx, int B, int N, int k, int d,
+                             float* T, mlsp_stream_t stream);
+/* transformer.py:39 backward: dq_i = sum_s dT[i][s].  (dpos = dT; dkk_j = -(reverse-index sum of dT): mlsp_group_reverse +
+ * mlsp_sa_group_bwd_f32.) */
+int mlsp_vecattn_mix_bwd_f32(const float* dT, int B, int N, int k, int d, float* dq, mlsp_stream_t stream);
+/* transformer.py:40-42: attn [E][d] = softmax over the k slots of A / sqrt(d) per channel (maximum subtracted), res [P][d] =
+ * sum_s attn[i][s] * (v_j + pos[i][s]); v [P][d] with row pitch ldv. */
+int mlsp_vecattn_aggregate_fwd_f32(const float* A, const float* v, int ldv, const float* pos, const int32_t* idx, int B, int N, int k, int d,
+                                   float* attn, float* res, mlsp_stream_t stream);
+/* transformer.py:40-42 backward from dres: dVP[e] = attn[e] * dres_i (the gradient of v_j + pos[e]: add to dpos, reverse-index sum -> dv)
+ * and dA[e] = attn[e] * (g[e] - sum_s attn[i][s] g[i][s]) / sqrt(d), g[e] = dres_i * (v_j + pos[e]).  attn itself takes no gradient. */
+int mlsp_vecattn_aggregate_bwd_f32(const float* dres, const float* attn, const float* v, int ldv, const float* pos, const int32_t* idx, int B,
+                                   int N, int k, int d, float* dVP, float* dA, mlsp_stream_t stream);
+/* transformer.py:39, the ReLU inside fc_gamma on [rows][d] (the GEMM family activates only behind a BatchNorm): y = max(x, 0), y may be x;
+ * backward dx = dy where y > 0. */
+int mlsp_vecattn_relu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t stream);
+int mlsp_vecattn_relu_bwd_f32(const float* dy, const float* y, int64_t rows, int d, float* dx, mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

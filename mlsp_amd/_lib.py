@@ -75,6 +75,14 @@ SIGNATURES = {
     "mlsp_def_density_loss_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
     "mlsp_gather_rows_u32": [_P, _P, _I, _I, _I, _P, _P],
     "mlsp_gather_rows_bwd_f32": [_P, _P, _I, _I, _I, _P, _P],
+    "mlsp_vecattn_delta_fwd_f32": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "mlsp_vecattn_delta_bwd_f32": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mlsp_vecattn_mix_fwd_f32": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P],
+    "mlsp_vecattn_mix_bwd_f32": [_P, _I, _I, _I, _I, _P, _P],
+    "mlsp_vecattn_aggregate_fwd_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "mlsp_vecattn_aggregate_bwd_f32": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "mlsp_vecattn_relu_fwd_f32": [_P, _I64, _I, _P, _P],
+    "mlsp_vecattn_relu_bwd_f32": [_P, _P, _I64, _I, _P, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],

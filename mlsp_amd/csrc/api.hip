@@ -991,4 +991,46 @@ int mlsp_gather_rows_bwd_f32(const float* dout, const int64_t* index, int B, int
     return launch_def_gather_bwd(st, dout, index, B, N, C, dx);
 }
 
+int mlsp_vecattn_delta_fwd_f32(const float* xyz, int ldx, const int32_t* idx, const float* Wd1, const float* bd1, int B, int N, int k, int d,
+                               float* H1, mlsp_stream_t st) {
+    if (!xyz || !idx || !Wd1 || !bd1 || !H1 || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_vecattn_delta_fwd(st, xyz, ldx, idx, Wd1, bd1, B, N, k, d, H1);
+}
+int mlsp_vecattn_delta_bwd_f32(const float* dH1, const float* H1, const float* xyz, int ldx, const int32_t* idx, int B, int N, int k, int d,
+                               float* dWd1, float* dbd1, void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    if (!dH1 || !H1 || !xyz || !idx || !dWd1 || !dbd1 || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    if (d % 4 || k > 64) return MLSP_ERR_UNSUPPORTED;
+    Workspace w(ws, ws_bytes);
+    float* part = w.take<float>(vecattn_delta_bwd_ws_floats(B, N, k, d));
+    if (!w.ok()) return MLSP_ERR_WORKSPACE;
+    return launch_vecattn_delta_bwd(st, dH1, H1, xyz, ldx, idx, B, N, k, d, part, dWd1, dbd1);
+}
+int mlsp_vecattn_mix_fwd_f32(const float* q, int ldq, const float* kk, int ldk, const float* pos, const int32_t* idx, int B, int N, int k, int d,
+                             float* T, mlsp_stream_t st) {
+    if (!q || !kk || !pos || !idx || !T || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_vecattn_mix_fwd(st, q, ldq, kk, ldk, pos, idx, B, N, k, d, T);
+}
+int mlsp_vecattn_mix_bwd_f32(const float* dT, int B, int N, int k, int d, float* dq, mlsp_stream_t st) {
+    if (!dT || !dq || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_vecattn_mix_bwd(st, dT, B, N, k, d, dq);
+}
+int mlsp_vecattn_aggregate_fwd_f32(const float* A, const float* v, int ldv, const float* pos, const int32_t* idx, int B, int N, int k, int d,
+                                   float* attn, float* res, mlsp_stream_t st) {
+    if (!A || !v || !pos || !idx || !attn || !res || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_vecattn_aggregate_fwd(st, A, v, ldv, pos, idx, B, N, k, d, attn, res);
+}
+int mlsp_vecattn_aggregate_bwd_f32(const float* dres, const float* attn, const float* v, int ldv, const float* pos, const int32_t* idx, int B,
+                                   int N, int k, int d, float* dVP, float* dA, mlsp_stream_t st) {
+    if (!dres || !attn || !v || !pos || !idx || !dVP || !dA || B <= 0 || N <= 0 || k <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_vecattn_aggregate_bwd(st, dres, attn, v, ldv, pos, idx, B, N, k, d, dVP, dA);
+}
+int mlsp_vecattn_relu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t st) {
+    if (!x || !y) return MLSP_ERR_ARG;
+    return launch_vecattn_relu_fwd(st, x, rows, d, y);
+}
+int mlsp_vecattn_relu_bwd_f32(const float* dy, const float* y, int64_t rows, int d, float* dx, mlsp_stream_t st) {
+    if (!dy || !y || !dx) return MLSP_ERR_ARG;
+    return launch_vecattn_relu_bwd(st, dy, y, rows, d, dx);
+}
+
 }  // extern "C"

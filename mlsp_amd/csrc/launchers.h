@@ -260,3 +260,19 @@ int launch_def_density_bwd(hipStream_t st, const float* pvec, const float* dens,
 int launch_def_gather(hipStream_t st, const uint32_t* x, const int64_t* index, int B, int N, int W, uint32_t* out);
 int launch_def_gather_bwd(hipStream_t st, const float* dout, const int64_t* index, int B, int N, int C, float* dx);
 
+// vecattn.hip
+size_t vecattn_delta_bwd_ws_floats(int B, int N, int k, int d);       // floats of `part` that launch_vecattn_delta_bwd writes
+int launch_vecattn_delta_fwd(hipStream_t st, const float* xyz, int ldx, const int* idx, const float* Wd1, const float* bd1, int B, int N, int k,
+                             int d, float* H1);
+int launch_vecattn_delta_bwd(hipStream_t st, const float* dH1, const float* H1, const float* xyz, int ldx, const int* idx, int B, int N, int k,
+                             int d, float* part, float* dWd1, float* dbd1);
+int launch_vecattn_mix_fwd(hipStream_t st, const float* q, int ldq, const float* kk, int ldk, const float* pos, const int* idx, int B, int N, int k,
+                           int d, float* T);
+int launch_vecattn_mix_bwd(hipStream_t st, const float* dT, int B, int N, int k, int d, float* dq);
+int launch_vecattn_aggregate_fwd(hipStream_t st, const float* A, const float* v, int ldv, const float* pos, const int* idx, int B, int N, int k,
+                                 int d, float* attn, float* res);
+int launch_vecattn_aggregate_bwd(hipStream_t st, const float* dres, const float* attn, const float* v, int ldv, const float* pos, const int* idx,
+                                 int B, int N, int k, int d, float* dVP, float* dA);
+int launch_vecattn_relu_fwd(hipStream_t st, const float* x, long long rows, int d, float* y);
+int launch_vecattn_relu_bwd(hipStream_t st, const float* dy, const float* y, long long rows, int d, float* dx);
+

@@ -1883,6 +1883,186 @@ def gather_rows(x, index):
     return _GatherRows.apply(x, index)
 
 
+def _va_check(rc, what):
+    """MLSP_ERR_UNSUPPORTED of the vector-attention kernels (d % 4, k > 64, alignment) is a MlspLibraryError: there is no other path"""
+    if rc == -3:
+        raise _lib.MlspLibraryError("%s: %s (needs d %% 4 == 0, 1 <= k <= 64, 16-byte-aligned rows)"
+                                    % (what, _lib.load().mlsp_strerror(rc).decode()))
+    _lib.check(rc, what)
+
+
+class _EdgeIndex:
+    """idx int32 [B,N,k] of a vector-attention call and, from the first backward that needs it, its reverse index (every edge that names
+    point j, in a fixed order: mlsp_group_reverse) -- shared by the two scatters of the call."""
+    __slots__ = ("idx", "B", "N", "k", "rev")
+
+    def __init__(self, idx32):
+        self.idx, (self.B, self.N, self.k), self.rev = idx32, idx32.shape, None
+
+    def scatter(self, dG):
+        """[E][d] edge rows -> [P][d]: out[j] = sum of the rows of the edges (i, s) with idx[i][s] == j"""
+        lib = _lib.load()
+        B, N, k, dev = self.B, self.N, self.k, dG.device
+        if self.rev is None:
+            rev_off = torch.empty((B * N + 1,), dtype=torch.int32, device=dev)
+            rev_ent = torch.empty((B * N * k,), dtype=torch.int32, device=dev)
+            _lib.check(lib.mlsp_group_reverse(self.idx.data_ptr(), B, N, N, k, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
+                       "mlsp_group_reverse")
+            self.rev = (rev_off, rev_ent)
+        d = dG.shape[1]
+        out = torch.empty((B * N, d), dtype=torch.float32, device=dev)
+        _lib.check(lib.mlsp_sa_group_bwd_f32(dG.data_ptr(), d, 0, d, self.rev[0].data_ptr(), self.rev[1].data_ptr(), B, N, N, k,
+                                             out.data_ptr(), _lib.stream()), "mlsp_sa_group_bwd_f32")
+        return out
+
+
+class _VaDelta(Function):
+    """first layer of fc_delta on the edges: H1 = relu(Wd1 (xyz_i - xyz_j) + bd1)  (mlsp_vecattn_delta_*_f32); no gradient to xyz"""
+
+    @staticmethod
+    def forward(ctx, xyz, Wd1, bd1, eidx):
+        lib = _lib.load()
+        B, N, k = eidx.B, eidx.N, eidx.k
+        Wd1, bd1 = Wd1.contiguous(), bd1.contiguous()
+        d = Wd1.shape[0]
+        assert xyz.shape[0] == B * N and Wd1.shape == (d, 3) and bd1.shape == (d,), (xyz.shape, Wd1.shape, bd1.shape)
+        H1 = torch.empty((B * N * k, d), dtype=torch.float32, device=xyz.device)
+        _va_check(lib.mlsp_vecattn_delta_fwd_f32(xyz.data_ptr(), xyz.stride(0), eidx.idx.data_ptr(), Wd1.data_ptr(), bd1.data_ptr(), B, N, k,
+                                                 d, H1.data_ptr(), _lib.stream()), "mlsp_vecattn_delta_fwd_f32")
+        ctx.save_for_backward(xyz, H1)
+        ctx.eidx = eidx
+        return H1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dH1):
+        lib = _lib.load()
+        xyz, H1 = ctx.saved_tensors
+        e = ctx.eidx
+        d = H1.shape[1]
+        dH1 = dH1.contiguous()
+        dW = torch.empty((d, 3), dtype=torch.float32, device=dH1.device)
+        db = torch.empty((d,), dtype=torch.float32, device=dH1.device)
+        ws, wsn = _lib.workspace(dH1.device, 4096, d, 4)
+        _va_check(lib.mlsp_vecattn_delta_bwd_f32(dH1.data_ptr(), H1.data_ptr(), xyz.data_ptr(), xyz.stride(0), e.idx.data_ptr(), e.B, e.N,
+                                                 e.k, d, dW.data_ptr(), db.data_ptr(), ws, wsn, _lib.stream()), "mlsp_vecattn_delta_bwd_f32")
+        return None, dW, db, None
+
+
+class _VaMix(Function):
+    """T[(i,s)] = q_i - kk_j + pos[(i,s)]  (mlsp_vecattn_mix_*_f32); dkk through the reverse index, dpos is dT itself"""
+
+    @staticmethod
+    def forward(ctx, q, kk, pos, eidx):
+        lib = _lib.load()
+        q, kk, pos = _rows(q), _rows(kk), pos.contiguous()
+        B, N, k = eidx.B, eidx.N, eidx.k
+        d = q.shape[1]
+        assert q.shape == (B * N, d) and kk.shape == (B * N, d) and pos.shape == (B * N * k, d), (q.shape, kk.shape, pos.shape)
+        T = torch.empty_like(pos)
+        _va_check(lib.mlsp_vecattn_mix_fwd_f32(q.data_ptr(), q.stride(0), kk.data_ptr(), kk.stride(0), pos.data_ptr(), eidx.idx.data_ptr(),
+                                               B, N, k, d, T.data_ptr(), _lib.stream()), "mlsp_vecattn_mix_fwd_f32")
+        ctx.eidx = eidx
+        return T
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dT):
+        lib = _lib.load()
+        e = ctx.eidx
+        dT = dT.contiguous()
+        d = dT.shape[1]
+        dq = dkk = None
+        if ctx.needs_input_grad[0]:
+            dq = torch.empty((e.B * e.N, d), dtype=torch.float32, device=dT.device)
+            _va_check(lib.mlsp_vecattn_mix_bwd_f32(dT.data_ptr(), e.B, e.N, e.k, d, dq.data_ptr(), _lib.stream()), "mlsp_vecattn_mix_bwd_f32")
+        if ctx.needs_input_grad[1]:
+            dkk = e.scatter(dT).neg_()
+        return dq, dkk, dT, None
+
+
+class _VaRelu(Function):
+    """the ReLU between the layers of fc_gamma on [E][d] rows (mlsp_vecattn_relu_*_f32: pointmlp activates only behind a BatchNorm)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        _va_check(lib.mlsp_vecattn_relu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()), "mlsp_vecattn_relu_fwd_f32")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        lib = _lib.load()
+        y, = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        _va_check(lib.mlsp_vecattn_relu_bwd_f32(dy.data_ptr(), y.data_ptr(), y.shape[0], y.shape[1], dx.data_ptr(), _lib.stream()),
+                  "mlsp_vecattn_relu_bwd_f32")
+        return dx
+
+
+class _VaAggregate(Function):
+    """attn = softmax over the slots of A / sqrt(d), res_i = sum_s attn * (v_j + pos)  (mlsp_vecattn_aggregate_*_f32); attn is returned
+    non-differentiable"""
+
+    @staticmethod
+    def forward(ctx, A, v, pos, eidx):
+        lib = _lib.load()
+        A, v, pos = A.contiguous(), _rows(v), pos.contiguous()
+        B, N, k = eidx.B, eidx.N, eidx.k
+        d = v.shape[1]
+        assert A.shape == (B * N * k, d) and pos.shape == A.shape and v.shape[0] == B * N, (A.shape, v.shape, pos.shape)
+        attn = torch.empty_like(A)
+        res = torch.empty((B * N, d), dtype=torch.float32, device=A.device)
+        _va_check(lib.mlsp_vecattn_aggregate_fwd_f32(A.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(), eidx.idx.data_ptr(), B, N, k, d,
+                                                     attn.data_ptr(), res.data_ptr(), _lib.stream()), "mlsp_vecattn_aggregate_fwd_f32")
+        ctx.save_for_backward(attn, v, pos)
+        ctx.eidx = eidx
+        ctx.mark_non_differentiable(attn)
+        return res, attn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dres, _dattn=None):
+        lib = _lib.load()
+        attn, v, pos = ctx.saved_tensors
+        e = ctx.eidx
+        d = v.shape[1]
+        dres = dres.contiguous()
+        dVP, dA = torch.empty_like(attn), torch.empty_like(attn)
+        _va_check(lib.mlsp_vecattn_aggregate_bwd_f32(dres.data_ptr(), attn.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(),
+                                                     e.idx.data_ptr(), e.B, e.N, e.k, d, dVP.data_ptr(), dA.data_ptr(), _lib.stream()),
+                  "mlsp_vecattn_aggregate_bwd_f32")
+        dv = e.scatter(dVP) if ctx.needs_input_grad[1] else None
+        return dA, dv, dVP, None
+
+
+def vector_attention(xyz_rows, idx32, q, kk, v, delta_w1, delta_b1, delta_w2, delta_b2, gamma_w1, gamma_b1, gamma_w2, gamma_b2):
+    """The edge part of the vector-attention block (PointDA/hengshuang_transformer/transformer.py:37-42): xyz_rows [B*N,3] (no gradient),
+    idx32 int32 [B,N,k] neighbour indices local to the cloud (k <= 64; an entry may repeat inside a row), q / kk / v [B*N,d] per point,
+    the four (weight, bias) pairs of fc_delta and fc_gamma in nn.Linear layout -> (res [B*N,d], attn [B*N*k,d]).
+    pos = fc_delta(xyz_i - xyz_j), attn = softmax_s(fc_gamma(q_i - kk_j + pos) / sqrt(d)), res_i = sum_s attn * (v_j + pos).
+    The three d x d layers on the edges are pointmlp GEMMs (they take the product mode of gemm_precision); everything between them is one
+    HIP kernel each.  `attn` is returned NON-differentiable (ctx.mark_non_differentiable): every caller in the reference takes [0] of the
+    block; gradients reach q, kk, v and the eight parameters through `res` only."""
+    _lib.require_gpu(xyz_rows, idx32, q, kk, v)
+    assert idx32.dtype == torch.int32 and idx32.dim() == 3 and xyz_rows.dim() == 2 and xyz_rows.shape[1] >= 3, (idx32.dtype, idx32.shape, xyz_rows.shape)
+    xyz_rows = xyz_rows.detach()
+    if xyz_rows.stride(1) != 1:
+        xyz_rows = xyz_rows.contiguous()
+    eidx = _EdgeIndex(idx32.contiguous())
+    H1 = _VaDelta.apply(xyz_rows, delta_w1, delta_b1, eidx)
+    pos = pointmlp(H1, delta_w2, bias=delta_b2)
+    T = _VaMix.apply(q, kk, pos, eidx)
+    G = _VaRelu.apply(pointmlp(T, gamma_w1, bias=gamma_b1))
+    A = pointmlp(G, gamma_w2, bias=gamma_b2)
+    return _VaAggregate.apply(A, v, pos, eidx)
+
+
 def gemm(A, B, ta=False, tb=False, bias=None):
     """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests."""
     lib = _lib.load()
