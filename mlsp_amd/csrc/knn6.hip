@@ -37,7 +37,7 @@
 // Measured on MI355X (B = 32, N = 1024, k = 20, one call incl. the prep kernel; uniform random clouds): C = 64 71 us (v5 113), C = 128 103 us
 // (v5 176), N = 2048 C = 64 95 us (v5 176); C = 3 54 us (v5 49: the selection phases dominate when the sweeps are trivial, so C <= 16 stays
 // on v5).  Inside the DGCNN step (features of a 3-D manifold: small gaps between neighbours relative to the norms, 2-3x more ambiguous
-// pairs): 89 / 129 us against 118 / 165.  Phase cycles per wave at C = 64, two waves per SIMD (tools/knn6_stamps.py): sweeps 17 k + 27 k,
+// pairs): 89 / 129 us against 118 / 165.  Phase cycles per wave at C = 64, two waves per SIMD (clock stamps between the phases): sweeps 17 k + 27 k,
 // tau 5.5 k, list conversion 5 k, sort / flag / settle 26 k, exact distances 16 k (bound by cache-line transactions: every 16-byte piece
 // of a gathered row is its own transaction; a cooperative fetch through LDS lost to its chain of dependent steps as written here).
 #include "common.h"
@@ -49,11 +49,11 @@ typedef unsigned int k6u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int k6u32x4 __attribute__((ext_vector_type(4)));
 typedef int k6i32x4 __attribute__((ext_vector_type(4)));
 
-#define K6_KMAX 24          // largest k
-#define K6_CAP 24           // survivors one (query, quarter) list keeps
+#define K6_KMAX 24          // largest k of knn6_kernel
+#define K6W_KMAX 40         // ... of knn6w_kernel
+#define K6_CAP 24           // survivors one list (a query's candidates of one part and half-wave) keeps
 #define K6_LENT 28          // entries of a list: the cursor is clamped every 4 appends
 #define K6_LSTR 232         // bytes between lists (58 dwords: 16 consecutive lists start in 16 different even banks)
-#define K6_XS 68            // floats per query of the tau exchange image (16-byte aligned rows, 4-bank skew)
 #define K6_EPS 1.220703125e-04f      // 2^-13 (error budget in the header)
 
 // byte offset of the 16-byte piece (point row of its tile, half h) of block kb, plane p (0 hi, 1 lo) of tile T
@@ -137,11 +137,557 @@ __device__ __forceinline__ void k6_static_for(F&& f) {
 // candidate beats list entry (value desc, index asc); false for a NaN candidate
 __device__ __forceinline__ bool k6_beats(float d, int j, float pv, int pi) { return d > pv || (d == pv && j < pi); }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The cut of a workgroup: 8 waves = QG groups of 32 queries x PARTS contiguous parts of the cloud's candidates; wave w carries group
+// w % QG against part w / QG.  Everything else about the two kernels' geometry follows from QG:
+//                                          knn6_kernel (k <= 24)     knn6w_kernel (24 < k <= 40)
+//   QG     query groups                    4                         2
+//   QWG    queries per workgroup           128                       64
+//   PARTS  candidate parts per group       2 halves                  4 quarters
+//   NL     lists per query (part x h)      4                         8
+//   NMAX   pass-A maxima per query         64                        128
+//   FL     lanes per query, fast final     4 (32 rank positions)     8 (64 rank positions)
+//   KMAX   largest k                       K6_KMAX = 24              K6W_KMAX = 40
+template <int QG_>
+struct K6Cut {
+    static constexpr int QG = QG_, QGS = __builtin_ctz(QG), QWG = 32 * QG, PARTS = 8 / QG, NL = 2 * PARTS, NMAX = 16 * NL;     // (QGS = log2 QG)
+    static constexpr int KMAX = QG == 4 ? K6_KMAX : K6W_KMAX; // largest k the kernel is dispatched for
+    static constexpr int XS = NMAX + 4;                       // floats per query of the tau exchange image (16-byte aligned rows, 4-bank skew)
+    static constexpr int FL = NL, FQ = 64 / FL, FCAP = 8 * FL;       // fast final: lanes per query, queries per wave, survivors it holds
+    // index of list t = 2 part + h of query qlc of group qg among the workgroup's 512 lists
+    static __device__ __forceinline__ int list_at(int qg, int qlc, int t) { return (qg * NL + t) * 32 + qlc; }
+};
+typedef K6Cut<4> K6Narrow;
+typedef K6Cut<2> K6Wide;
+
+// prologue, norm bounds: nxx[j] = -xc_j / 2 (what the sweeps' accumulators start from) and this thread's share of the two maxima
+// (fmaxf drops a NaN operand: a NaN norm -- a NaN coordinate, or an infinite first point of the cloud, the origin of the centred
+// image -- becomes an infinite bound here, and an infinite bound sends the workgroup through the exact path / to the v5 kernel)
+__device__ __forceinline__ void k6_fill_nxx(int tid, int N, const float* xcb, const float* xxb, float* nxx, float& m, float& mr) {
+    for (int j = tid; j < N; j += 512) {
+        const float v = xcb[j], w = xxb[j];
+        nxx[j] = -0.5f * v; m = fmaxf(m, v == v ? v : INFINITY); mr = fmaxf(mr, w == w ? w : INFINITY);
+    }
+}
+// ... and their reduction over the workgroup (one __syncthreads: nxx is complete behind it): xcmax = largest centred, xxmax = largest raw norm
+__device__ __forceinline__ void k6_reduce_bounds(int lane, int wave, float m, float mr, float* red, float& xcmax, float& xxmax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); mr = fmaxf(mr, __shfl_xor(mr, o, 64)); }
+    if (lane == 0) { red[wave] = m; red[8 + wave] = mr; }
+    __syncthreads();
+    xcmax = red[0]; xxmax = red[8];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) { xcmax = fmaxf(xcmax, red[w]); xxmax = fmaxf(xxmax, red[8 + w]); }
+}
+
+// MFMA operand of 16-channel block kb of the 32-point tile at `tile` (uniform address): row l31, channels 16 kb + 8 h .. + 7 of the hi and the
+// lo plane; voff = h * 512 + l31 * 16, this lane's 16 bytes of a fragment: the wave reads one contiguous KiB per piece (k6_piece)
+__device__ __forceinline__ void k6_frag_load(const char* tile, int kb, unsigned voff, k6bf16x8& fh, k6bf16x8& fl) {
+    const char* p = tile + kb * 2048;
+    fh = *(const k6bf16x8*)(p + voff);
+    fl = *(const k6bf16x8*)(p + 1024 + voff);
+}
+// B operand: the wave's 32 queries = tile T of the image
+template <int NKB>
+__device__ __forceinline__ void k6_load_query(const char* planes, size_t T, unsigned voff, k6bf16x8 (&qh)[NKB], k6bf16x8 (&ql)[NKB]) {
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) k6_frag_load(planes + T * (NKB * 2048), kb, voff, qh[kb], ql[kb]);
+}
+
+// One sweep of a wave over its part of the candidates: nt 32-candidate tiles from cand0 (uniform: the part's first tile in the image),
+// part * nt the part's first tile in the cloud.  sel(acc, tl) sees the finished 32 x 32 tile:
+// acc[r] = a(query l31, candidate (r & 3) + 8 (r >> 2) + 4 h of the tile), a = dot' - xc_j / 2.
+// Fragment ring: slot (tile % PF, block) is refilled right after its use with the tile PF ahead; a scheduling barrier after every
+// refill keeps the loads where they are written (the scheduler otherwise sinks them next to their use: prefetch distance zero).
+// The compiler drains the memory counter once per loop trip (its wait-count analysis merges pessimistically at the back edge), so a
+// trip covers UNR tiles: the drain exposes one L2 latency per UNR tiles of MFMA work.
+template <int NKB, class Sel>
+__device__ __forceinline__ void k6_sweep(const char* cand0, unsigned voff, const float* nxx, int part, int h, int nt,
+                                         const k6bf16x8 (&qh)[NKB], const k6bf16x8 (&ql)[NKB], Sel&& sel) {
+    constexpr int PF = NKB >= 8 ? 1 : NKB >= 4 ? 2 : 4;      // tiles of fragments in flight (the ring holds PF * NKB blocks of 2 x 4 registers)
+    constexpr int NR = PF * NKB;
+    constexpr int UNR = NKB >= 8 ? 2 : 8;                     // tiles per loop trip (4 at C = 128 costs two spilled registers)
+    auto frag_load = [&](int tl, int kb, k6bf16x8& ah, k6bf16x8& al) {       // A operand: candidate row l31 of tile tl of this part
+        k6_frag_load(cand0 + (size_t)tl * (NKB * 2048), kb, voff, ah, al);
+    };
+    k6bf16x8 fh[NR], fl[NR];
+    auto tile = [&](auto SLOT, auto RING, int tl, int tn) {   // tn: the tile that refills this ring slot (always loaded: no branch)
+        constexpr int s0 = decltype(SLOT)::value * NKB;
+        constexpr bool ring = decltype(RING)::value;
+        f32x16 acc;
+        const float* p = nxx + (part * nt + tl) * 32 + 4 * h;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const f32x4 v = *(const f32x4*)(p + 8 * g4);
+            acc[4 * g4] = v[0]; acc[4 * g4 + 1] = v[1]; acc[4 * g4 + 2] = v[2]; acc[4 * g4 + 3] = v[3];
+        }
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], qh[kb], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[s0 + kb], qh[kb], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], ql[kb], acc, 0, 0, 0);
+            if (ring) {
+                frag_load(tn, kb, fh[s0 + kb], fl[s0 + kb]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        sel(acc, tl);
+    };
+    const int nmain = (nt / UNR) * UNR;
+    if (nmain > 0) {                                          // (so nt >= UNR >= PF: the ring's first PF tiles exist, no clamp)
+#pragma unroll
+        for (int tu = 0; tu < PF; ++tu)
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) frag_load(tu, kb, fh[tu * NKB + kb], fl[tu * NKB + kb]);
+        for (int t0 = 0; t0 < nmain; t0 += UNR) {
+            k6_static_for<0, UNR>([&](auto TU) {
+                constexpr int tu = decltype(TU)::value;
+                const int tl = t0 + tu;
+                const int tn = min(tl + PF, nt - 1);          // (past the end the last tile is fetched again: harmless, and no branch in the body)
+                tile(std::integral_constant<int, tu % PF>{}, std::true_type{}, tl, tn);
+            });
+        }
+    }
+    for (int tl = nmain; tl < nt; ++tl) {                     // ragged tail (nt not a multiple of UNR): one tile at a time through slot 0
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) frag_load(tl, kb, fh[kb], fl[kb]);
+        tile(std::integral_constant<int, 0>{}, std::false_type{}, tl, tl);
+    }
+}
+
+// pass A: a lane's 16 running maxima -> its 16 floats of the query's row of the tau exchange image (slot = 2 part + h)
+__device__ __forceinline__ void k6_store_maxima(float* dst, const float (&cm)[16]) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) { const f32x4 v = {cm[4 * g4], cm[4 * g4 + 1], cm[4 * g4 + 2], cm[4 * g4 + 3]}; *(f32x4*)(dst + 4 * g4) = v; }
+}
+
+// 64 floats sorted descending in registers (bitonic network, one lane)
+__device__ __forceinline__ void k6_sort64(float (&v)[64]) {
+#pragma unroll
+    for (int k2 = 2; k2 <= 64; k2 <<= 1)
+#pragma unroll
+        for (int j = k2 >> 1; j > 0; j >>= 1)
+#pragma unroll
+            for (int i = 0; i < 64; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const float lo = fminf(v[i], v[l]), hi = fmaxf(v[i], v[l]);
+                    if ((i & k2) == 0) { v[i] = hi; v[l] = lo; }           // descending overall
+                    else { v[i] = lo; v[l] = hi; }
+                }
+            }
+}
+
+// pass B, one tile: the survivors (acc[r] >= thr) of the 16 candidates jb + (r & 3) + 8 (r >> 2) go to the list at LDS byte address `base`.
+// per pair: v_cmpx (exec = survivors) / ds_write2_b32 {value, index} at the cursor / cursor += 8 under that mask / exec back to all lanes:
+// three vector instructions and no branch; the cursor `ad` is clamped every 4 appends (lists have 4 entries of slack), `top` keeps the
+// farthest it got (overflow: top > base + K6_CAP * 8).
+#define K6_APPEND(ad_, val_, thr_, j_, gate_) asm volatile("v_cmpx_ge_f32_e32 vcc, %1, %2\n\tds_write2_b32 %0, %1, %3 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, -1" \
+                                                           : "+v"(ad_) : "v"(val_), "v"(thr_), "v"(j_), "v"(gate_) : "vcc", "memory")
+__device__ __forceinline__ void k6_append16(unsigned& ad, unsigned& top, unsigned base, const f32x16& acc, float thr, int jb) {
+    int jv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) jv[r] = jb + (r & 3) + 8 * (r >> 2);
+    // The compiler does not place the MFMA -> VALU / LDS read wait states for instructions INSIDE an asm statement: a visible VALU read of
+    // the accumulator (gate) comes first -- the hazard recognizer pads in front of it -- and every append depends on the gate.
+    const float gate = fmaxf(acc[0], acc[15]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        K6_APPEND(ad, acc[r], thr, jv[r], gate);
+        if ((r & 3) == 3) { top = max(top, ad); ad = min(ad, base + K6_CAP * 8); }
+    }
+}
+
+// F0: a lane moves ITS list to the pd domain (pd' = 2 a - xc_q; `exact`: the list holds pd itself) and fills it to the end with {-inf, 0}
+// (never ahead of, never close to a real entry: the counting loops of the slow final read whole blocks unmasked); the list's length and
+// the largest centred norm among its survivors go to slot t = 2 part + h of query qs of the workgroup.
+template <class Cut, bool VEX>
+__device__ __forceinline__ void k6_f0(char* LB, int cnt, bool exact, float xcq, const float* nxx, int* cnts, float* lmn, int qs, int t) {
+    float mn = 0.f;                                            // min of -xc_j / 2 = -(largest centred squared norm among this list's survivors) / 2
+#pragma unroll
+    for (int p0 = 0; p0 < K6_LENT; p0 += 4) {
+        k6u32x2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *(const k6u32x2*)(LB + (p0 + u) * 8);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float a = __int_as_float((int)v[u][0]);
+            const float p = (exact || VEX) ? a : fmaf(2.0f, a, -xcq);
+            const bool live = p0 + u < cnt;
+            const k6u32x2 w = {(unsigned)__float_as_int(live ? p : -INFINITY), live ? v[u][1] : 0u};
+            *(k6u32x2*)(LB + (p0 + u) * 8) = w;
+            if (!VEX && live) mn = fminf(mn, nxx[v[u][1] & 4095u]);
+        }
+    }
+    cnts[qs * Cut::NL + t] = cnt;
+    lmn[qs * Cut::NL + t] = mn;
+}
+
+// The canonical distance of (query row q, candidate row j) of the cloud at xb: dot = fmaf chain over the channels ascending from +0,
+// t = fl(2 dot - xx_j), pd = fl(t - xx_q) (oracle/knn_canon.c) -- this arithmetic is what makes the indices bit-exact.  xvec (16-byte
+// aligned rows, C % 4 == 0): both rows fetched CHV float4 pieces at a time (2 x CHV x 16 bytes in flight per lane).
+template <int CHV>
+__device__ __forceinline__ float k6_canon_pd(const float* xb, int ld, int C, bool xvec, const float* xxb, int q, int j) {
+    const float* rq = xb + (size_t)q * ld;
+    const float* rj = xb + (size_t)j * ld;
+    float acc = 0.f;
+    if (!xvec) {
+        for (int c = 0; c < C; ++c) acc = fmaf(rq[c], rj[c], acc);
+    } else {
+        for (int c = 0; c < C; c += 4 * CHV) {
+            f32x4 a4[CHV], b4[CHV];
+#pragma unroll
+            for (int u = 0; u < CHV; ++u)
+                if (c + 4 * u < C) { a4[u] = *(const f32x4*)(rq + c + 4 * u); b4[u] = *(const f32x4*)(rj + c + 4 * u); }
+#pragma unroll
+            for (int u = 0; u < CHV; ++u)
+                if (c + 4 * u < C) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = fmaf(a4[u][e], b4[u][e], acc);
+                }
+        }
+    }
+    const float t2 = fmaf(2.0f, acc, -xxb[j]);
+    return t2 - xxb[q];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The finals: exact ranks of a query's survivors.  What a wave needs for them:
+struct K6Fin {
+    const float *xb, *xxb, *xcb;        // the cloud: fp32 rows, canonical (raw) and centred squared norms
+    int ld, C, k;
+    bool xvec;                          // rows can be fetched as float4
+    float xxmax, canon;                 // the cloud's largest raw norm; K6_CANON
+    char* lists;                        // [512][K6_LSTR], pd domain (k6_f0)
+    const int* cnts;                    // [queries of the workgroup][NL] list lengths
+    const float* lmn;                   // [queries of the workgroup][NL] min of -xc_j / 2 over each list's survivors
+    unsigned* wl;                       // this wave's 512 words of work space
+    int* out;                           // idx rows of the cloud
+    int lane, qg, part, qwg0;           // qwg0: first query of the workgroup, local to the cloud
+};
+// address of list t of query qlc of the wave's group
+template <class Cut>
+__device__ __forceinline__ char* k6_list(const K6Fin& f, int qlc, int t) { return f.lists + (size_t)(Cut::list_at(f.qg, qlc, t) * K6_LSTR); }
+// query qq of the workgroup: pp[t] = survivors ahead of list t (pp[NL] = all of them), cmx = its longest list, and
+// 2 E = the width of the window inside which the approximate values do not decide (error budget: file header; 0 for exact values)
+template <class Cut>
+__device__ __forceinline__ void k6_query_lists(const K6Fin& f, int qq, bool exact, int (&pp)[Cut::NL + 1], int& cmx, float& E2) {
+    float mn = 0.f;
+    pp[0] = 0;
+#pragma unroll
+    for (int t4 = 0; t4 < Cut::NL; t4 += 4) {
+        const k6i32x4 c4 = *(const k6i32x4*)(f.cnts + qq * Cut::NL + t4);
+        const f32x4 m4 = *(const f32x4*)(f.lmn + qq * Cut::NL + t4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) pp[t4 + u + 1] = pp[t4 + u] + c4[u];
+        const int cm4 = max(max(c4[0], c4[1]), max(c4[2], c4[3]));
+        const float mn4 = fminf(fminf(m4[0], m4[1]), fminf(m4[2], m4[3]));
+        cmx = t4 ? max(cmx, cm4) : cm4;
+        mn = t4 ? fminf(mn, mn4) : mn4;
+    }
+    const float xm = -2.0f * mn;                               // largest centred squared norm among the query's survivors
+    const int qrow = f.qwg0 + qq;
+    E2 = exact ? 0.0f : 2.0f * (K6_EPS * (f.xcb[qrow] + xm) + f.canon * (f.xxb[qrow] + f.xxmax));
+}
+// entry e of a query's concatenated lists: list t, position e - pb
+template <int NL>
+__device__ __forceinline__ void k6_locate(const int (&pp)[NL + 1], int e, int& t, int& pb) {
+    t = 0; pb = 0;
+#pragma unroll
+    for (int u = 1; u < NL; ++u) { const bool ge = e >= pp[u]; t = ge ? u : t; pb = ge ? pp[u] : pb; }
+}
+
+// value of the same register in lane ^ D: DPP row_ror at 8, the permlane swaps at 16 / 32 (no LDS)
+template <int D>
+__device__ __forceinline__ unsigned k6_xlane(unsigned v, int lane) {
+    if constexpr (D == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true);
+    else if constexpr (D == 16) { const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); return (lane & 16) ? r[0] : r[1]; }
+    else { const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false); return (lane & 32) ? r[0] : r[1]; }
+}
+// compare-exchange of a lane's positions a, a ^ jj; desc: the larger value to the lower position
+__device__ __forceinline__ void k6_cex_local(float (&pv)[8], int (&jv)[8], int jj, bool desc) {
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const int c = a ^ jj;
+        if (c > a) {
+            const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
+            const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
+            const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
+            pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
+        }
+    }
+}
+// ... of position i of this lane and of lane ^ D: the lane without bit D holds the lower position
+template <int D>
+__device__ __forceinline__ void k6_cex_cross(float (&pv)[8], int (&jv)[8], int lane, bool desc) {
+    const bool low = (lane & D) == 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float ov = __uint_as_float(k6_xlane<D>(__float_as_uint(pv[i]), lane));
+        const int oj = (int)k6_xlane<D>((unsigned)jv[i], lane);
+        const bool sw = low ? (desc ? pv[i] < ov : pv[i] > ov) : (desc ? ov < pv[i] : ov > pv[i]);
+        pv[i] = sw ? ov : pv[i]; jv[i] = sw ? oj : jv[i];
+    }
+}
+
+// ---- fast final (every query of the wave has at most FCAP = 8 FL survivors -- the normal case): FL LANES PER QUERY.  Wave (qg, part) finishes
+// queries part * FQ .. + FQ - 1 of its group; lane l serves query l % FQ and holds rank positions 8 m .. 8 m + 7 of its FCAP (m = l / FQ).  The FL lanes
+// pull the query's survivors into registers and sort them by pd' with a bitonic network whose exchanges at distance >= 8 cross lanes (k6_xlane):
+// with four lanes 72 compare-exchanges per lane instead of the 240 of one lane per query.  Then: the ones whose gap to a neighbour in rank is
+// within 2 E are flagged, get their canonical distances (all flagged pairs of the wave packed densely over its lanes: fmaf chains over the fp32
+// rows), and the flagged runs are settled with odd-even passes under the full order (value desc, index asc); the pair across a lane boundary goes
+// through two shuffles.  An unflagged survivor never moves: its gaps exceed 2 E.  VEX: the lists hold exact values, only exact ties are flagged.
+// Returns false, with nothing written, when a query of the wave has more survivors than that: the counting final takes the wave.
+template <class Cut, int CT, bool VEX>
+__device__ __forceinline__ bool k6_fast_final(const K6Fin& f) {
+    constexpr int FL = Cut::FL, FQ = Cut::FQ, FCAP = Cut::FCAP, NL = Cut::NL;
+    const int lane = f.lane, ql = lane & (FQ - 1), m = lane / FQ;
+    const int qlc = f.part * FQ + ql;
+    const int qq = f.qg * 32 + qlc, qrow = f.qwg0 + qq;
+    int pp[NL + 1], cmx;
+    float E2;
+    k6_query_lists<Cut>(f, qq, VEX, pp, cmx, E2);
+    const int n = pp[NL];
+    int nmaxw = n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nmaxw = max(nmaxw, __shfl_xor(nmaxw, o, 64));
+    if (nmaxw > FCAP) return false;
+    float pv[8];
+    int jv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = 8 * m + i;
+        int t, pb;
+        k6_locate<NL>(pp, e, t, pb);
+        const k6u32x2 v = *(const k6u32x2*)(k6_list<Cut>(f, qlc, e < n ? t : 0) + (e < n ? e - pb : 0) * 8);
+        pv[i] = e < n ? __int_as_float((int)v[0]) : -INFINITY;
+        jv[i] = e < n ? (int)v[1] : 0x7fffffff;
+    }
+    // bitonic network over positions a = 8 m + i; a pair keeps the larger value at the lower position iff (a & k2) == 0
+#pragma unroll
+    for (int a = 0; a < 8; a += 2) {                            // k2 = 2
+        const bool desc = (a & 2) == 0;
+        const bool sw = desc ? pv[a] < pv[a + 1] : pv[a] > pv[a + 1];
+        const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
+        const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
+        pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
+    }
+#pragma unroll
+    for (int jj = 2; jj > 0; jj >>= 1)                          // k2 = 4: direction by bit 2 of the position
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const int c = a ^ jj;
+            if (c > a) {
+                const bool desc = (a & 4) == 0;
+                const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
+                const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
+                const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
+                pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
+            }
+        }
+    // k2 = 8 s, s = 1 .. FL: direction by bit s of m (the last stage: descending), exchanges with lanes m ^ (s / 2) .. m ^ 1, i.e. at lane
+    // distances FQ, 2 FQ, 4 FQ = 16, 32 for four lanes per query, 8, 16, 32 for eight, then inside the lane
+    auto cex_lane = [&](bool d) { k6_cex_local(pv, jv, 4, d); k6_cex_local(pv, jv, 2, d); k6_cex_local(pv, jv, 1, d); };
+    { const bool d = (m & 1) == 0; cex_lane(d); }                                                                                   // k2 = 8
+    { const bool d = (m & 2) == 0; k6_cex_cross<FQ>(pv, jv, lane, d); cex_lane(d); }                                                // k2 = 16
+    { const bool d = (m & 4) == 0; k6_cex_cross<2 * FQ>(pv, jv, lane, d); k6_cex_cross<FQ>(pv, jv, lane, d); cex_lane(d); }         // k2 = 32
+    if constexpr (FL == 8) { k6_cex_cross<4 * FQ>(pv, jv, lane, true); k6_cex_cross<2 * FQ>(pv, jv, lane, true); k6_cex_cross<FQ>(pv, jv, lane, true); cex_lane(true); }   // k2 = 64
+    // flag: gap to the next survivor in rank not provably larger than 2 E (dead tail entries: -inf, never flagged)
+    const float nxt0 = __shfl(pv[0], lane + FQ, 64), prv7 = __shfl(pv[7], lane - FQ, 64);
+    unsigned amb = 0u;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) amb |= (8 * m + i + 1 < n && !(pv[i] - pv[i + 1] > E2)) ? (3u << i) : 0u;
+    amb |= (m < FL - 1 && 8 * m + 8 < n && !(pv[7] - nxt0 > E2)) ? 0x80u : 0u;
+    amb |= (m > 0 && 8 * m < n && !(prv7 - pv[0] > E2)) ? 1u : 0u;
+    const int nfl = __builtin_popcount(amb);                   // this lane's flagged entries; the query's: the FL lanes' sum
+    int nflag = 0, foff = 0;
+#pragma unroll
+    for (int t = 0; t < FL; ++t) { const int fl = __shfl(nfl, ql + FQ * t, 64); nflag += fl; foff += t < m ? fl : 0; }
+    unsigned* slots = f.wl + ql * FCAP + foff;                 // this lane's part of the query's [FCAP]: candidate index in, canonical distance out
+    {
+        int c = 0;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            if ((amb >> a) & 1u) { slots[c] = (unsigned)jv[a]; ++c; }
+        }
+    }
+    int fmaxw = nflag;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fmaxw = max(fmaxw, __shfl_xor(fmaxw, o, 64));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // Canonical distances of the flagged pairs, DENSELY packed over the wave's lanes: pair i of the wave = (query, slot) by a prefix sum of
+    // the FQ queries' flag counts (the counts differ a lot from query to query: slot-by-slot rounds ran at a third of the lanes).  Both rows
+    // fetched whole (2 x 16 x 16 bytes in flight per lane at C = 64; 8 pieces at C = 128: register budget), fmaf chain channels ascending.
+    // (Staging the rows through LDS with cooperative, fully coalesced fetches was built and measured: 2x slower -- the phase is bound by its
+    // chain of dependent steps, not by cache-line transactions.)
+    if (fmaxw > 0) {
+        int offs[FQ + 1];
+        offs[0] = 0;
+#pragma unroll
+        for (int q = 0; q < FQ; ++q) offs[q + 1] = offs[q] + __builtin_amdgcn_readlane(nflag, q);      // (scalar)
+        const int total = offs[FQ];
+        const int qbase = f.qwg0 + f.qg * 32 + f.part * FQ;
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane;
+            if (i < total) {
+                int q = 0, ob = 0;
+#pragma unroll
+                for (int t = 1; t < FQ; ++t) { const bool ge = i >= offs[t]; q = ge ? t : q; ob = ge ? offs[t] : ob; }
+                unsigned* sp = f.wl + q * FCAP + (i - ob);
+                const int j = (int)*sp;
+                *sp = (unsigned)__float_as_int(k6_canon_pd<CT >= 128 ? 8 : 16>(f.xb, f.ld, f.C, f.xvec, f.xxb, qbase + q, j));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    {
+        int c = 0;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            if ((amb >> a) & 1u) { pv[a] = __int_as_float((int)slots[c]); ++c; }
+        }
+    }
+    // settle the flagged runs: odd-even transposition passes under the full order until nothing moves (a run of r entries needs <= r passes)
+    if (fmaxw > 0) {
+        for (int pass = 0; pass < FCAP; ++pass) {
+            bool moved = false;
+#pragma unroll
+            for (int par = 0; par < 2; ++par)                   // positions (8 m + a, + 1) inside the lane: a even, then a odd
+#pragma unroll
+                for (int a = par; a < 7; a += 2) {
+                    const bool sw = k6_beats(pv[a + 1], jv[a + 1], pv[a], jv[a]);
+                    const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
+                    const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
+                    pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
+                    moved |= sw;
+                }
+            {                                                    // the odd pair across the lane boundary: (8 m + 7, 8 (m + 1))
+                const float nv = __shfl(pv[0], lane + FQ, 64), pvv = __shfl(pv[7], lane - FQ, 64);
+                const int nj = __shfl(jv[0], lane + FQ, 64), pj = __shfl(jv[7], lane - FQ, 64);
+                const bool swh = m < FL - 1 && k6_beats(nv, nj, pv[7], jv[7]);      // the next lane's first entry beats my last one
+                const bool swl = m > 0 && k6_beats(pv[0], jv[0], pvv, pj);          // my first entry beats the previous lane's last one
+                pv[7] = swh ? nv : pv[7]; jv[7] = swh ? nj : jv[7];
+                pv[0] = swl ? pvv : pv[0]; jv[0] = swl ? pj : jv[0];
+                moved |= swh | swl;
+            }
+            if (!__any(moved)) break;
+        }
+    }
+    int* out = f.out + (size_t)qrow * f.k;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const int pos = 8 * m + a;
+        if (pos < f.k && pos < n) out[pos] = jv[a];
+    }
+    return true;
+}
+
+// flush of the counting final: canonical distance of every pair on the wave's work list (items: entry offset / 8 | query of the
+// workgroup << 16) back into the lists, then a recount of those entries under the full order (value desc, index asc)
+template <class Cut>
+__device__ __forceinline__ void k6_flush(const K6Fin& f, int wcnt) {
+    constexpr int RU = Cut::NL == 4 ? 4 : 1;                   // lists per trip of the recount (eight lists stay a loop: 192 unrolled comparisons are only code size)
+    const int lane = f.lane;
+    for (int i0 = 0; i0 < wcnt; i0 += 64) {
+        const int i = i0 + lane;
+        if (i < wcnt) {
+            const unsigned item = f.wl[i];
+            char* ent = f.lists + (size_t)(item & 0xffffu) * 8;
+            const int j = *(const int*)(ent + 4);
+            *(float*)ent = k6_canon_pd<8>(f.xb, f.ld, f.C, f.xvec, f.xxb, f.qwg0 + (int)(item >> 16), j);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int i0 = 0; i0 < wcnt; i0 += 64) {
+        const int i = i0 + lane;
+        const bool on = i < wcnt;
+        const unsigned item = on ? f.wl[i] : 0u;
+        const int qq_ = (int)(item >> 16), qlc_ = qq_ & 31;
+        const k6u32x2 me = *(const k6u32x2*)(f.lists + (size_t)(item & 0xffffu) * 8);
+        const float pm = __int_as_float((int)me[0]);
+        const int jm = (int)me[1];
+        int rank = 0;
+#pragma unroll RU
+        for (int t = 0; t < Cut::NL; ++t) {
+            const char* L = k6_list<Cut>(f, qlc_, t);
+#pragma unroll
+            for (int p0 = 0; p0 < K6_CAP; p0 += 8) {
+                k6u32x2 ke[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) ke[u] = *(const k6u32x2*)(L + (p0 + u) * 8);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) rank += k6_beats(__int_as_float((int)ke[u][0]), (int)ke[u][1], pm, jm) ? 1 : 0;
+            }
+        }
+        if (on && rank < f.k) f.out[(size_t)(f.qwg0 + qq_) * f.k + rank] = jm;
+    }
+}
+
+// ---- counting final (a query of the wave has more than FCAP survivors, or the lists are exact): rank by counting, two queries per trip (one
+// per half-wave); lane l31 owns entries l31 + 32 s of the query's NL concatenated lists.  Per entry of the query: rank += (pd'_e > mine),
+// near += (|pd'_e - mine| <= 2 E).  near > 1 (I count myself): AMBIGUOUS -> the wave's work list; everyone else is written out at once.
+// `exact` values: 2 E = 0, only exact ties go through the flush's full-order recount.
+template <class Cut>
+__device__ __forceinline__ void k6_counting_final(const K6Fin& f, bool exact) {
+    constexpr int NL = Cut::NL, FQ = Cut::FQ;
+    constexpr int PU = NL == 4 ? 4 : 1;                        // list positions per trip of the counting loop: 4 x 4 lists, 1 x 8 lists
+    const int lane = f.lane, l31 = lane & 31, h = lane >> 5;
+    int wcnt = 0;                                              // wave-uniform
+    for (int it = 0; it < FQ / 2; ++it) {
+        const int qlc = f.part * FQ + it * 2 + h;              // query of the group
+        const int qq = f.qg * 32 + qlc;                        // query of the workgroup
+        int pp[NL + 1], cmx;
+        float E2;
+        k6_query_lists<Cut>(f, qq, exact, pp, cmx, E2);
+        const int n = pp[NL];
+        const int nmax = max(__builtin_amdgcn_readlane(n, 0), __builtin_amdgcn_readlane(n, 32));
+        cmx = max(__builtin_amdgcn_readlane(cmx, 0), __builtin_amdgcn_readlane(cmx, 32));
+        for (int s0 = 0; s0 < nmax; s0 += 32) {                // one trip unless a query has more than 32 survivors
+            const int e = s0 + l31;
+            const bool valid = e < n;
+            int t, pb;
+            k6_locate<NL>(pp, e, t, pb);
+            const char* mine = k6_list<Cut>(f, qlc, valid ? t : 0) + (valid ? e - pb : 0) * 8;
+            const k6u32x2 me = *(const k6u32x2*)mine;
+            const float pm = __int_as_float((int)me[0]);
+            const int j = (int)me[1];
+            int rank = 0, near = 0;
+            for (int p0 = 0; p0 < cmx; p0 += PU) {             // (the lists are filled to K6_LENT with -inf: whole trips, unmasked)
+#pragma unroll
+                for (int u = 0; u < PU; ++u)
+#pragma unroll
+                    for (int lt = 0; lt < NL; ++lt) {
+                        const float a = *(const float*)(k6_list<Cut>(f, qlc, lt) + (p0 + u) * 8);
+                        rank += a > pm ? 1 : 0;
+                        near += fabsf(a - pm) <= E2 ? 1 : 0;
+                    }
+            }
+            const bool amb = valid && !(near <= 1);            // another survivor inside my 2 E window (I count once myself)
+            if (valid && !amb && rank < f.k) f.out[(size_t)(f.qwg0 + qq) * f.k + rank] = j;
+            const unsigned long long mk = __ballot(amb);
+            if (mk) {
+                const int before = __builtin_popcountll(mk & ((1ull << lane) - 1ull));
+                if (amb) f.wl[wcnt + before] = (unsigned)((mine - f.lists) >> 3) | ((unsigned)qq << 16);
+                wcnt += __builtin_popcountll(mk);
+            }
+        }
+        if (wcnt > 512 - 2 * NL * K6_CAP || (it == FQ / 2 - 1 && wcnt > 0)) {       // (a trip adds at most 2 x NL x K6_CAP items)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            k6_flush<Cut>(f, wcnt);
+            wcnt = 0;
+        }
+    }
+}
+
 // Workgroup = 8 waves = 128 queries x all N candidates of their cloud.  Wave w: qg = w & 3 picks a group of 32 queries, ch = w >> 2 the
 // half of the candidates it sweeps: two waves per SIMD (the selection phases are vector-issue bound, and a lone wave issues at half rate),
 // no barrier inside a sweep.  (Two query groups per wave against the same fragments -- half the fragment traffic -- was built and measured:
 // the sweeps gain 10 %, every selection phase loses 2x at one wave per SIMD.)
-// Measured (B = 32, N = 1024, k = 20): 37.7 us per call against 41.5 on knn_mfma5_kernel<4>; stamps (tools/knn6_stamps.py, clocks per
+// Measured (B = 32, N = 1024, k = 20): 37.7 us per call against 41.5 on knn_mfma5_kernel<4>; clock stamps between the phases (clocks per
 // workgroup): pass A 11.7 k, pass B 24.7 k, tau 5.5 k, final 11.4 k of 64 k -- the sweeps are LDS-issue bound, not vector bound: every
 // ds_read_b128 of a candidate row serves 64 (query, candidate) pairs whatever the arithmetic (16 reads per tile and wave, 8 waves), and
 // the masked survivor append doubles that in pass B.  Going below needs several queries per lane against one candidate read (another
@@ -153,86 +699,56 @@ template <int CT, bool VEX = false>
 __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, int ld, const float* __restrict__ xx_all, const float* __restrict__ xc_all,
                                                    const char* __restrict__ planes, int N, int C, int k, int* __restrict__ idx, int B) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    typedef K6Narrow Cut;
     constexpr int NKB = CT / 16;                              // 16-channel blocks = bf16 MFMA K steps per tile
-    constexpr int PF = NKB >= 8 ? 1 : NKB >= 4 ? 2 : 4;      // tiles of fragments in flight (the ring holds PF * NKB blocks of 2 x 4 registers)
-    constexpr int NR = PF * NKB;
-    constexpr int UNR = NKB >= 8 ? 2 : 8;                     // tiles per loop trip (see `sweep`; 4 at C = 128 costs two spilled registers)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);         // (scalar: addresses below stay in SGPRs)
-    const int l31 = lane & 31, h = lane >> 5, qg = wave & 3, ch = wave >> 2;
+    const int l31 = lane & 31, h = lane >> 5, qg = wave & (Cut::QG - 1), ch = wave >> Cut::QGS;
     int b, chunk;
-    xcd_cloud_map(blockIdx.x, N / 128, B, b, chunk);
+    xcd_cloud_map(blockIdx.x, N / Cut::QWG, B, b, chunk);
     const float* xxb = xx_all + (size_t)b * N;                // canonical squared norms (raw coordinates)
     const float* xcb = xc_all + (size_t)b * N;                // squared norms relative to the cloud's first point (the sweeps' coordinates)
     const size_t T0 = (size_t)b * (N / 32);                  // first 32-point tile of this cloud in the fragment-major image
     const float* xb = x + (size_t)b * N * ld;
-    const int nt2 = N / 64;                                   // 32-candidate tiles of this wave's half
+    const int nt2 = N / (32 * Cut::PARTS);                    // 32-candidate tiles of this wave's half
 
-    char* lists = (char*)sm;                                  // [512 lists][K6_LSTR]; list = ((qg*2 + ch)*2 + h)*32 + query of the group
-    float* xch = sm;                                          // tau exchange image [128 queries][K6_XS], dead before pass B
+    char* lists = (char*)sm;                                  // [512 lists][K6_LSTR]; list = Cut::list_at(qg, query of the group, 2 ch + h)
+    float* xch = sm;                                          // tau exchange image [128 queries][Cut::XS], dead before pass B
     float* nxx = (float*)(lists + 512 * K6_LSTR);             // [N]  -xc_j / 2
     float* tauv = nxx + N;                                    // [128]
-    int* cnts = (int*)(tauv + 128);                           // [128 queries][4 quarters]
+    int* cnts = (int*)(tauv + 128);                           // [128 queries][4 lists]
     float* red = (float*)(cnts + 512);                        // [16]
     unsigned* wlbase = (unsigned*)(red + 16);                 // [8 waves][512 words]: fast final: [16 queries][32] candidate / exact value of the ambiguous; slow final: work list
-    float* lmn = (float*)(wlbase + 8 * 512);                  // [128 queries][4 quarters] min of -xc_j / 2 over the list's survivors
+    float* lmn = (float*)(wlbase + 8 * 512);                  // [128 queries][4 lists] min of -xc_j / 2 over the list's survivors
     const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)sm);       // LDS byte address of `lists`
 
     float xcmax, xxmax;
     {
         float m = 0.f, mr = 0.f;
-        // (fmaxf drops a NaN operand: a NaN norm -- a NaN coordinate, or an infinite first point of the cloud, the origin of the centred
-        // image -- becomes an infinite bound here, and an infinite bound sends the workgroup through the exact path below)
-        if (VEX) {
+        if (VEX) {                                            // (a NaN norm becomes an infinite bound: k6_fill_nxx)
             const f32x4* cg = (const f32x4*)planes + (size_t)b * N;
             f32x4* cl = (f32x4*)wlbase;                       // the cloud {x, xx}: the final's work lists live here later
             for (int j = tid; j < N; j += 512) { const f32x4 v = cg[j]; cl[j] = v; mr = fmaxf(mr, v[3] == v[3] ? v[3] : INFINITY); }
         } else
-        for (int j = tid; j < N; j += 512) {
-            const float v = xcb[j], w = xxb[j];
-            nxx[j] = -0.5f * v; m = fmaxf(m, v == v ? v : INFINITY); mr = fmaxf(mr, w == w ? w : INFINITY);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); mr = fmaxf(mr, __shfl_xor(mr, o, 64)); }
-        if (lane == 0) { red[wave] = m; red[8 + wave] = mr; }
-        __syncthreads();
-        xcmax = red[0]; xxmax = red[8];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) { xcmax = fmaxf(xcmax, red[w]); xxmax = fmaxf(xxmax, red[8 + w]); }
+            k6_fill_nxx(tid, N, xcb, xxb, nxx, m, mr);
+        k6_reduce_bounds(lane, wave, m, mr, red, xcmax, xxmax);
     }
     // |pd' - pd_canonical| <= K6_EPS (xc_q + xc_j)  [split products on the centred coordinates, header]
     //                        + K6_CANON (xx_q + xx_j)  [the canonical value's own distance from -|x_q - x_j|^2: an fmaf chain of C terms, the two
     //                          norms and two more roundings on the RAW coordinates: < (C + 4) 2^-23 (xx_q + xx_j)]
     const float K6_CANON = (float)(C + 4) * 1.1920929e-07f;
-    const int q0 = chunk * 128 + qg * 32;                     // first query of this wave's group, local to the cloud
+    const int q0 = chunk * Cut::QWG + qg * 32;                // first query of this wave's group, local to the cloud
     const float xxq = xxb[q0 + l31];                          // raw (exact path, canonical bound)
     const float xcq = VEX ? 0.f : xcb[q0 + l31];              // centred (sweeps)
     // VEX: the lists hold the canonical values themselves -- no error to budget; a non-finite norm still asks for the exact path
     const float Eq = VEX ? (xxmax < INFINITY ? 0.f : INFINITY) : K6_EPS * (xcq + xcmax) + K6_CANON * (xxq + xxmax);
 
     // ---------------------------------------------------------------------------------------------------------------- approximate sweeps
-    k6bf16x8 qh[NKB], ql[NKB];                                // B operand: query row l31 of the group, channels 16 kb + 8 h .. + 7
+    k6bf16x8 qh[NKB], ql[NKB];
     f32x4 qv = {0.f, 0.f, 0.f, 0.f};                          // VEX: this lane's query {x0, x1, x2, xx}
-    if constexpr (VEX) {
-        qv = ((const f32x4*)wlbase)[q0 + l31];
-    } else {
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            qh[kb] = *(const k6bf16x8*)(planes + k6_piece(T0 + (q0 >> 5), NKB, kb, 0, h, l31));
-            ql[kb] = *(const k6bf16x8*)(planes + k6_piece(T0 + (q0 >> 5), NKB, kb, 1, h, l31));
-        }
-    }
+    if constexpr (VEX) qv = ((const f32x4*)wlbase)[q0 + l31];
     const unsigned voff = (unsigned)(h * 512 + l31 * 16);     // this lane's 16 bytes inside a fragment KiB
+    if constexpr (!VEX) k6_load_query<NKB>(planes, T0 + (q0 >> 5), voff, qh, ql);
     const char* cand0 = planes + (T0 + (size_t)ch * nt2) * (NKB * 2048);     // (uniform) first tile of this wave's half
-    auto frag_load = [&](int tl, int kb, k6bf16x8& ah, k6bf16x8& al) {       // A operand: candidate row l31 of tile tl of this half
-        const char* p = cand0 + (size_t)tl * (NKB * 2048) + kb * 2048;                       // uniform; one contiguous KiB per wave and piece
-        ah = *(const k6bf16x8*)(p + voff);
-        al = *(const k6bf16x8*)(p + 1024 + voff);
-    };
-    // one sweep over the half: sel(acc, tl) sees the finished 32 x 32 tile: acc[r] = a(query l31, candidate (r & 3) + 8 (r >> 2) + 4 h of the tile).
-    // Fragment ring: slot (tile % PF, block) is refilled right after its use with the tile PF ahead; a scheduling barrier after every
-    // refill keeps the loads where they are written (the scheduler otherwise sinks them next to their use: prefetch distance zero).
-    // The compiler drains the memory counter once per loop trip (its wait-count analysis merges pessimistically at the back edge), so a
-    // trip covers UNR tiles: the drain exposes one L2 latency per UNR tiles of MFMA work.
     auto sweep = [&](auto&& sel) {
         if constexpr (VEX) {
             // vector sweep: acc[r] = the CANONICAL distance of (query l31, candidate (r & 3) + 8 (r >> 2) + 4 h of the tile): dot = fmaf chain
@@ -252,51 +768,8 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
                 }
                 sel(acc, tl);
             }
-            return;
-        }
-        k6bf16x8 fh[NR], fl[NR];
-        auto tile = [&](auto SLOT, auto RING, int tl, int tn, auto&& sel_) {  // tn: the tile that refills this ring slot (always loaded: no branch)
-            constexpr int s0 = decltype(SLOT)::value * NKB;
-            constexpr bool ring = decltype(RING)::value;
-            f32x16 acc;
-            const float* p = nxx + (ch * nt2 + tl) * 32 + 4 * h;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const f32x4 v = *(const f32x4*)(p + 8 * g4);
-                acc[4 * g4] = v[0]; acc[4 * g4 + 1] = v[1]; acc[4 * g4 + 2] = v[2]; acc[4 * g4 + 3] = v[3];
-            }
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], qh[kb], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[s0 + kb], qh[kb], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], ql[kb], acc, 0, 0, 0);
-                if (ring) {
-                    frag_load(tn, kb, fh[s0 + kb], fl[s0 + kb]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            sel_(acc, tl);
-        };
-        const int nmain = (nt2 / UNR) * UNR;
-        if (nmain > 0) {
-#pragma unroll
-            for (int tu = 0; tu < PF; ++tu)
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) frag_load(tu, kb, fh[tu * NKB + kb], fl[tu * NKB + kb]);
-            for (int t0 = 0; t0 < nmain; t0 += UNR) {
-                k6_static_for<0, UNR>([&](auto TU) {
-                    constexpr int tu = decltype(TU)::value;
-                    const int tl = t0 + tu;
-                    const int tn = min(tl + PF, nt2 - 1);      // (past the end the last tile is fetched again: harmless, and no branch in the body)
-                    tile(std::integral_constant<int, tu % PF>{}, std::true_type{}, tl, tn, sel);
-                });
-            }
-        }
-        for (int tl = nmain; tl < nt2; ++tl) {                // ragged tail (N / 64 not a multiple of UNR): one tile at a time through slot 0
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) frag_load(tl, kb, fh[kb], fl[kb]);
-            tile(std::integral_constant<int, 0>{}, std::false_type{}, tl, tl, sel);
-        }
+        } else
+            k6_sweep<NKB>(cand0, voff, nxx, ch, h, nt2, qh, ql, sel);
     };
 
     // ---- pass A: 16 running maxima per lane (acc domain: a = dot' - xc_j / 2 is monotone in the distance for a fixed query)
@@ -308,9 +781,7 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) cm[r] = fmaxf(cm[r], acc[r]);
         });
-        float* dst = xch + (qg * 32 + l31) * K6_XS + (ch * 2 + h) * 16;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) { const f32x4 v = {cm[4 * g4], cm[4 * g4 + 1], cm[4 * g4 + 2], cm[4 * g4 + 3]}; *(f32x4*)(dst + 4 * g4) = v; }
+        k6_store_maxima(xch + (qg * 32 + l31) * Cut::XS + (ch * 2 + h) * 16, cm);
     }
     __syncthreads();
     // tau = k-th largest of a query's 64 maxima: one lane per query (the ch = 0 wave of a group: one wave per SIMD; lanes 32-63 mirror), bitonic
@@ -318,57 +789,28 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
     if (ch == 0) {
         const int qs = qg * 32 + l31;
         float v[64];
-        const float* src = xch + qs * K6_XS;
+        const float* src = xch + qs * Cut::XS;
 #pragma unroll
         for (int i4 = 0; i4 < 16; ++i4) {
             const f32x4 t = *(const f32x4*)(src + 4 * i4);
             v[4 * i4] = t[0]; v[4 * i4 + 1] = t[1]; v[4 * i4 + 2] = t[2]; v[4 * i4 + 3] = t[3];
         }
-#pragma unroll
-        for (int k2 = 2; k2 <= 64; k2 <<= 1)
-#pragma unroll
-            for (int j = k2 >> 1; j > 0; j >>= 1)
-#pragma unroll
-                for (int i = 0; i < 64; ++i) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const float lo = fminf(v[i], v[l]), hi = fmaxf(v[i], v[l]);
-                        if ((i & k2) == 0) { v[i] = hi; v[l] = lo; }           // descending overall
-                        else { v[i] = lo; v[l] = hi; }
-                    }
-                }
+        k6_sort64(v);
         float t = v[0];
 #pragma unroll
-        for (int i = 1; i < K6_KMAX; ++i) t = (i == k - 1) ? v[i] : t;
+        for (int i = 1; i < Cut::KMAX; ++i) t = (i == k - 1) ? v[i] : t;
         if (lane < 32) tauv[qs] = t;
     }
     __syncthreads();                                          // tau complete; the exchange image (aliases the lists) is dead from here on
     float thr = tauv[qg * 32 + l31] - Eq;                     // acc domain: pd' >= tau_pd - 2 E  <=>  a >= a_tau - E
     thr = thr == thr ? thr : -INFINITY;                       // (a non-finite bound Eq sends the workgroup through the exact path: `ovf` below)
 
-    // ---- pass B: survivors -> this lane's private list (acc-domain value, candidate index)
-    // per pair: v_cmpx (exec = survivors) / ds_write2_b32 {value, index} at the cursor / cursor += 8 under that mask / exec back to all lanes:
-    // three vector instructions and no branch; the cursor is clamped every 4 appends (lists have 4 entries of slack).
-    char* LB = lists + (size_t)((((qg * 2 + ch) * 2 + h) * 32 + l31) * K6_LSTR);
-    const unsigned base = lds0 + (unsigned)((((qg * 2 + ch) * 2 + h) * 32 + l31) * K6_LSTR);
+    // ---- pass B: survivors -> this lane's private list (acc-domain value, candidate index): k6_append16
+    const int lid = Cut::list_at(qg, l31, ch * 2 + h);
+    char* LB = lists + (size_t)(lid * K6_LSTR);
+    const unsigned base = lds0 + (unsigned)(lid * K6_LSTR);
     unsigned ad = base, top = base;
-    sweep([&](const f32x16& acc, int tl) {
-        const int jb = (ch * nt2 + tl) * 32 + 4 * h;
-        int jv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) jv[r] = jb + (r & 3) + 8 * (r >> 2);
-        // The compiler does not place the MFMA -> VALU / LDS read wait states for instructions INSIDE an asm statement: a visible VALU read of
-        // the accumulator (gate) comes first -- the hazard recognizer pads in front of it -- and every append depends on the gate.
-        const float gate = fmaxf(acc[0], acc[15]);
-#define K6_APPEND(ad_, val_, thr_, j_, gate_) asm volatile("v_cmpx_ge_f32_e32 vcc, %1, %2\n\tds_write2_b32 %0, %1, %3 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, -1" \
-                                                           : "+v"(ad_) : "v"(val_), "v"(thr_), "v"(j_), "v"(gate_) : "vcc", "memory")
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            K6_APPEND(ad, acc[r], thr, jv[r], gate);
-            if ((r & 3) == 3) { top = max(top, ad); ad = min(ad, base + K6_CAP * 8); }
-        }
-#undef K6_APPEND
-    });
+    sweep([&](const f32x16& acc, int tl) { k6_append16(ad, top, base, acc, thr, (ch * nt2 + tl) * 32 + 4 * h); });
     int cnt = (int)(ad - base) >> 3;
     // overflow (massive ties), or no usable bound: a non-finite norm in the cloud (the approximate values of a NaN row are NaN and survive
     // no comparison, so they would not overflow anything: ask for the exact path outright)
@@ -442,530 +884,99 @@ __global__ __launch_bounds__(512) void knn6_kernel(const float* __restrict__ x, 
         }
         exact_lists = true;
     }
-    // ---- F0: every lane moves ITS list to the pd domain (pd' = 2 a - xc_q; the exact path stored pd itself) and fills it to the end with
-    //      {-inf, 0} (never ahead of, never close to a real entry: the counting loops of the slow final read whole blocks unmasked)
-    {
-        float mn = 0.f;                                        // min of -xc_j / 2 = -(largest centred squared norm among this list's survivors) / 2
-#pragma unroll
-        for (int p0 = 0; p0 < K6_LENT; p0 += 4) {
-            k6u32x2 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *(const k6u32x2*)(LB + (p0 + u) * 8);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float a = __int_as_float((int)v[u][0]);
-                const float p = (exact_lists || VEX) ? a : fmaf(2.0f, a, -xcq);
-                const bool live = p0 + u < cnt;
-                const k6u32x2 w = {(unsigned)__float_as_int(live ? p : -INFINITY), live ? v[u][1] : 0u};
-                *(k6u32x2*)(LB + (p0 + u) * 8) = w;
-                if (!VEX && live) mn = fminf(mn, nxx[v[u][1] & 4095u]);
-            }
-        }
-        cnts[(qg * 32 + l31) * 4 + ch * 2 + h] = cnt;
-        lmn[(qg * 32 + l31) * 4 + ch * 2 + h] = mn;
-    }
+    k6_f0<Cut, VEX>(LB, cnt, exact_lists, xcq, nxx, cnts, lmn, qg * 32 + l31, ch * 2 + h);          // lists -> pd domain
     __syncthreads();
 
     // ---------------------------------------------------------------------------------------------------------------- final: exact ranks
     const bool xvec = (ld & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (C & 3) == 0;
-    auto list_at = [&](int qlc_, int t) -> char* { return lists + (size_t)((((qg * 2 + (t >> 1)) * 2 + (t & 1)) * 32 + qlc_) * K6_LSTR); };
-    // ---- fast final (every query of the group has at most 32 survivors -- the normal case): FOUR LANES PER QUERY.  Wave (qg, ch) finishes queries
-    // ch * 16 .. + 15 of its group; lane l serves query l & 15 and holds rank positions 8 m .. 8 m + 7 of its 32 (m = l >> 4).  The four lanes pull the
-    // query's survivors into registers and sort them by pd' with a bitonic network whose exchanges at distance 8 / 16 cross lanes (v_permlane16 /
-    // 32_swap, no LDS): 72 compare-exchanges per lane instead of the 240 of one lane per query.  Then as before: the ones whose gap to a neighbour in
-    // rank is within 2 E are flagged, get their canonical distances (all flagged pairs of the wave packed densely over its lanes: fmaf chains over
-    // the fp32 rows), and the flagged runs are settled with odd-even passes under the full order (value desc, index asc); the pair across a lane
-    // boundary goes through two shuffles.  An unflagged survivor never moves: its gaps exceed 2 E.
-    {
-        const int ql = lane & 15, m = lane >> 4;
-        const int qlc = ch * 16 + ql;
-        const int qq = qg * 32 + qlc, qrow = chunk * 128 + qq;
-        const k6i32x4 c4 = *(const k6i32x4*)(cnts + qq * 4);
-        const int p1 = c4[0], p2 = p1 + c4[1], p3 = p2 + c4[2], n = p3 + c4[3];
-        int nmaxw = n;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nmaxw = max(nmaxw, __shfl_xor(nmaxw, o, 64));
-        if (!exact_lists && nmaxw <= 32) {
-            const f32x4 m4 = *(const f32x4*)(lmn + qq * 4);
-            const float xm = -2.0f * fminf(fminf(m4[0], m4[1]), fminf(m4[2], m4[3]));
-            const float xqr = xxb[qrow], xqc = VEX ? 0.f : xcb[qrow];
-            const float E2 = VEX ? 0.0f : 2.0f * (K6_EPS * (xqc + xm) + K6_CANON * (xqr + xxmax));     // (VEX: exact values, only exact ties are flagged)
-            const char* Lb0 = list_at(qlc, 0);
-            const char* Lb1 = list_at(qlc, 1);
-            const char* Lb2 = list_at(qlc, 2);
-            const char* Lb3 = list_at(qlc, 3);
-            float pv[8];
-            int jv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = 8 * m + i;
-                const int t = (e >= p1) + (e >= p2) + (e >= p3);
-                const char* Lt = t == 0 ? Lb0 : t == 1 ? Lb1 : t == 2 ? Lb2 : Lb3;
-                const int pos = e - (t == 0 ? 0 : t == 1 ? p1 : t == 2 ? p2 : p3);
-                const k6u32x2 v = *(const k6u32x2*)(Lt + (e < n ? pos : 0) * 8);
-                pv[i] = e < n ? __int_as_float((int)v[0]) : -INFINITY;
-                jv[i] = e < n ? (int)v[1] : 0x7fffffff;
-            }
-            // value of the same register in lane ^ 16 / lane ^ 32
-            auto x16 = [&](unsigned v) -> unsigned { const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); return (m & 1) ? r[0] : r[1]; };
-            auto x32 = [&](unsigned v) -> unsigned { const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false); return (m & 2) ? r[0] : r[1]; };
-            auto cex_local = [&](int jj, bool desc) {          // positions a, a ^ jj inside the lane; desc: the larger value to the lower position
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const int c = a ^ jj;
-                    if (c > a) {
-                        const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
-                        const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
-                        const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
-                        pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
-                    }
-                }
-            };
-            auto cex_cross = [&](bool by32, bool desc) {       // positions 8 m + i and 8 (m ^ 1 | m ^ 2) + i: the lane with the lower m is the lower position
-                const bool low = by32 ? (m & 2) == 0 : (m & 1) == 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float ov = __uint_as_float(by32 ? x32(__float_as_uint(pv[i])) : x16(__float_as_uint(pv[i])));
-                    const int oj = (int)(by32 ? x32((unsigned)jv[i]) : x16((unsigned)jv[i]));
-                    const bool sw = low ? (desc ? pv[i] < ov : pv[i] > ov) : (desc ? ov < pv[i] : ov > pv[i]);
-                    pv[i] = sw ? ov : pv[i]; jv[i] = sw ? oj : jv[i];
-                }
-            };
-            // bitonic network over positions a = 8 m + i; a pair keeps the larger value at the lower position iff (a & k2) == 0
-#pragma unroll
-            for (int a = 0; a < 8; a += 2) {                    // k2 = 2
-                const bool desc = (a & 2) == 0;
-                const bool sw = desc ? pv[a] < pv[a + 1] : pv[a] > pv[a + 1];
-                const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-            }
-            {                                                   // k2 = 4: jj = 2, 1; direction by bit 2 of the position
-#pragma unroll
-                for (int jj = 2; jj > 0; jj >>= 1)
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) {
-                        const int c = a ^ jj;
-                        if (c > a) {
-                            const bool desc = (a & 4) == 0;
-                            const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
-                            const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
-                            const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
-                            pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
-                        }
-                    }
-            }
-            { const bool d8 = (m & 1) == 0; cex_local(4, d8); cex_local(2, d8); cex_local(1, d8); }                      // k2 = 8
-            { const bool d16 = (m & 2) == 0; cex_cross(false, d16); cex_local(4, d16); cex_local(2, d16); cex_local(1, d16); }   // k2 = 16
-            { cex_cross(true, true); cex_cross(false, true); cex_local(4, true); cex_local(2, true); cex_local(1, true); }       // k2 = 32
-            // flag: gap to the next survivor in rank not provably larger than 2 E (dead tail entries: -inf, never flagged)
-            const float nxt0 = __shfl(pv[0], lane + 16, 64), prv7 = __shfl(pv[7], lane - 16, 64);
-            unsigned amb = 0u;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) amb |= (8 * m + i + 1 < n && !(pv[i] - pv[i + 1] > E2)) ? (3u << i) : 0u;
-            amb |= (m < 3 && 8 * m + 8 < n && !(pv[7] - nxt0 > E2)) ? 0x80u : 0u;
-            amb |= (m > 0 && 8 * m < n && !(prv7 - pv[0] > E2)) ? 1u : 0u;
-            const int nfl = __builtin_popcount(amb);           // this lane's flagged entries; the query's: the four lanes' sum
-            const int f0 = __shfl(nfl, ql, 64), f1 = __shfl(nfl, ql + 16, 64), f2 = __shfl(nfl, ql + 32, 64), f3 = __shfl(nfl, ql + 48, 64);
-            const int nflag = f0 + f1 + f2 + f3;
-            const int foff = m == 0 ? 0 : m == 1 ? f0 : m == 2 ? f0 + f1 : f0 + f1 + f2;
-            unsigned* slots = wlbase + wave * 512 + ql * 32 + foff;      // this lane's part of the query's [32]: candidate index in, canonical distance out
-            {
-                int c = 0;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    if ((amb >> a) & 1u) { slots[c] = (unsigned)jv[a]; ++c; }
-                }
-            }
-            int fmaxw = nflag;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) fmaxw = max(fmaxw, __shfl_xor(fmaxw, o, 64));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // Canonical distances of the flagged pairs, DENSELY packed over the wave's lanes: pair i of the wave = (query, slot) by a prefix sum of
-            // the 16 queries' flag counts (the counts differ a lot from query to query: slot-by-slot rounds ran at a third of the lanes).  Both rows
-            // fetched whole (2 x 16 x 16 bytes in flight per lane at C = 64), fmaf chain channels ascending.  (Staging the rows through LDS with
-            // cooperative, fully coalesced fetches was built and measured: 2x slower -- the phase is bound by its chain of dependent steps, not by
-            // cache-line transactions.)
-            if (fmaxw > 0) {
-                int offs[17];
-                offs[0] = 0;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) offs[q + 1] = offs[q] + __builtin_amdgcn_readlane(nflag, q);      // (scalar)
-                const int total = offs[16];
-                unsigned* wslots = wlbase + wave * 512;
-                const int qbase = chunk * 128 + qg * 32 + ch * 16;
-                for (int i0 = 0; i0 < total; i0 += 64) {
-                    const int i = i0 + lane;
-                    if (i < total) {
-                        int q = 0, ob = 0;
-#pragma unroll
-                        for (int t = 1; t < 16; ++t) { const bool ge = i >= offs[t]; q = ge ? t : q; ob = ge ? offs[t] : ob; }
-                        unsigned* sp = wslots + q * 32 + (i - ob);
-                        const int j = (int)*sp;
-                        const int qr = qbase + q;
-                        const float* rq = xb + (size_t)qr * ld;
-                        const float* rj = xb + (size_t)j * ld;
-                        float acc = 0.f;
-                        if (!xvec) {
-                            for (int c = 0; c < C; ++c) acc = fmaf(rq[c], rj[c], acc);
-                        } else {
-                            constexpr int CHV = CT >= 128 ? 8 : 16;        // float4 pieces of both rows in flight (register budget at C = 128)
-                            for (int c = 0; c < C; c += 4 * CHV) {
-                                f32x4 a4[CHV], b4[CHV];
-#pragma unroll
-                                for (int u = 0; u < CHV; ++u)
-                                    if (c + 4 * u < C) { a4[u] = *(const f32x4*)(rq + c + 4 * u); b4[u] = *(const f32x4*)(rj + c + 4 * u); }
-#pragma unroll
-                                for (int u = 0; u < CHV; ++u)
-                                    if (c + 4 * u < C) {
-#pragma unroll
-                                        for (int e = 0; e < 4; ++e) acc = fmaf(a4[u][e], b4[u][e], acc);
-                                    }
-                            }
-                        }
-                        const float t2 = fmaf(2.0f, acc, -xxb[j]);
-                        *sp = (unsigned)__float_as_int(t2 - xxb[qr]);
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            {
-                int c = 0;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    if ((amb >> a) & 1u) { pv[a] = __int_as_float((int)slots[c]); ++c; }
-                }
-            }
-            // settle the flagged runs: odd-even transposition passes under the full order until nothing moves (a run of r entries needs <= r passes)
-            if (fmaxw > 0) {
-                for (int pass = 0; pass < 32; ++pass) {
-                    bool moved = false;
-#pragma unroll
-                    for (int a = 0; a < 7; a += 2) {             // positions (8 m + a, + 1), a even: inside the lane
-                        const bool sw = k6_beats(pv[a + 1], jv[a + 1], pv[a], jv[a]);
-                        const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                        const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                        pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-                        moved |= sw;
-                    }
-#pragma unroll
-                    for (int a = 1; a < 7; a += 2) {
-                        const bool sw = k6_beats(pv[a + 1], jv[a + 1], pv[a], jv[a]);
-                        const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                        const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                        pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-                        moved |= sw;
-                    }
-                    {                                            // the odd pair across the lane boundary: (8 m + 7, 8 (m + 1))
-                        const float nv = __shfl(pv[0], lane + 16, 64), pvv = __shfl(pv[7], lane - 16, 64);
-                        const int nj = __shfl(jv[0], lane + 16, 64), pj = __shfl(jv[7], lane - 16, 64);
-                        const bool swh = m < 3 && k6_beats(nv, nj, pv[7], jv[7]);       // the next lane's first entry beats my last one
-                        const bool swl = m > 0 && k6_beats(pv[0], jv[0], pvv, pj);      // my first entry beats the previous lane's last one
-                        pv[7] = swh ? nv : pv[7]; jv[7] = swh ? nj : jv[7];
-                        pv[0] = swl ? pvv : pv[0]; jv[0] = swl ? pj : jv[0];
-                        moved |= swh | swl;
-                    }
-                    if (!__any(moved)) break;
-                }
-            }
-            {
-                int* out = idx + ((size_t)b * N + qrow) * k;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const int pos = 8 * m + a;
-                    if (pos < k && pos < n) out[pos] = jv[a];
-                }
-            }
-            return;
-        }
-    }
-    // ---- slow final (a query with more than 32 survivors, or exact lists): rank by counting, two queries per trip (one per half-wave); lane l31
-    // owns entries l31 + 32 s of the query's concatenated quarter lists.  Per entry of the query: rank += (pd'_e > mine), near += (|pd'_e - mine|
-    // <= 2 E).  near > 1 (I count myself): AMBIGUOUS -> the wave's work list; everyone else is written out at once.  Flush: canonical distance
-    // of every listed pair back into the lists, then a recount under the full order (value desc, index asc).
-    unsigned* wl = wlbase + wave * 512;                        // items: entry offset / 8 | query of the workgroup << 16
-    int wcnt = 0;                                              // wave-uniform
-    auto flush = [&]() {
-        for (int i0 = 0; i0 < wcnt; i0 += 64) {
-            const int i = i0 + lane;
-            if (i < wcnt) {
-                const unsigned item = wl[i];
-                const int qq_ = (int)(item >> 16);
-                char* ent = lists + (size_t)(item & 0xffffu) * 8;
-                const int j = *(const int*)(ent + 4);
-                const int qrow_ = chunk * 128 + qq_;
-                const float* rq = xb + (size_t)qrow_ * ld;
-                const float* rj = xb + (size_t)j * ld;
-                float acc = 0.f;
-                if (xvec) {
-                    for (int c = 0; c < C; c += 32) {          // C % 4 == 0; up to 32 channels of both rows in flight
-                        f32x4 a4[8], b4[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            if (c + 4 * u < C) { a4[u] = *(const f32x4*)(rq + c + 4 * u); b4[u] = *(const f32x4*)(rj + c + 4 * u); }
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            if (c + 4 * u < C) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) acc = fmaf(a4[u][e], b4[u][e], acc);
-                            }
-                    }
-                } else {
-                    for (int c = 0; c < C; ++c) acc = fmaf(rq[c], rj[c], acc);
-                }
-                const float t2 = fmaf(2.0f, acc, -xxb[j]);
-                *(float*)ent = t2 - xxb[qrow_];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int i0 = 0; i0 < wcnt; i0 += 64) {
-            const int i = i0 + lane;
-            const bool on = i < wcnt;
-            const unsigned item = on ? wl[i] : 0u;
-            const int qq_ = (int)(item >> 16), qlc_ = qq_ & 31;
-            const k6u32x2 me = *(const k6u32x2*)(lists + (size_t)(item & 0xffffu) * 8);
-            const float pm = __int_as_float((int)me[0]);
-            const int jm = (int)me[1];
-            int rank = 0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const char* L = list_at(qlc_, t);
-#pragma unroll
-                for (int p0 = 0; p0 < K6_CAP; p0 += 8) {
-                    k6u32x2 ke[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) ke[u] = *(const k6u32x2*)(L + (p0 + u) * 8);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) rank += k6_beats(__int_as_float((int)ke[u][0]), (int)ke[u][1], pm, jm) ? 1 : 0;
-                }
-            }
-            if (on && rank < k) idx[((size_t)b * N + chunk * 128 + qq_) * k + rank] = jm;
-        }
-        wcnt = 0;
-    };
-    for (int it = 0; it < 8; ++it) {
-        const int qlc = ch * 16 + it * 2 + h;                  // query of the group
-        const int qq = qg * 32 + qlc;                          // query of the workgroup
-        const int qrow = chunk * 128 + qq;                     // query of the cloud
-        const float xq = xxb[qrow], xqc = VEX ? 0.f : xcb[qrow];
-        const char* L0 = list_at(qlc, 0);
-        const char* L1 = list_at(qlc, 1);
-        const char* L2 = list_at(qlc, 2);
-        const char* L3 = list_at(qlc, 3);
-        const k6i32x4 c4 = *(const k6i32x4*)(cnts + qq * 4);
-        const f32x4 m4 = *(const f32x4*)(lmn + qq * 4);
-        const float xm = -2.0f * fminf(fminf(m4[0], m4[1]), fminf(m4[2], m4[3]));       // largest centred squared norm among the query's survivors
-        const float E2 = (exact_lists || VEX) ? 0.0f : 2.0f * (K6_EPS * (xqc + xm) + K6_CANON * (xq + xxmax));     // (exact values: only exact ties go through the full-order recount)
-        const int p1 = c4[0], p2 = p1 + c4[1], p3 = p2 + c4[2], n = p3 + c4[3];
-        const int nmax = max(__builtin_amdgcn_readlane(n, 0), __builtin_amdgcn_readlane(n, 32));
-        int cmx = max(max(c4[0], c4[1]), max(c4[2], c4[3]));
-        cmx = max(__builtin_amdgcn_readlane(cmx, 0), __builtin_amdgcn_readlane(cmx, 32));
-        for (int s0 = 0; s0 < nmax; s0 += 32) {                // one trip unless a query has more than 32 survivors
-            const int e = s0 + l31;
-            const bool valid = e < n;
-            const int t = (e >= p1) + (e >= p2) + (e >= p3);
-            const int pos = e - (t == 0 ? 0 : t == 1 ? p1 : t == 2 ? p2 : p3);
-            const char* mine = list_at(qlc, valid ? t : 0) + (valid ? pos : 0) * 8;
-            const k6u32x2 me = *(const k6u32x2*)mine;
-            const float pm = __int_as_float((int)me[0]);
-            const int j = (int)me[1];
-            int rank = 0, near = 0;
-            for (int p0 = 0; p0 < cmx; p0 += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float a0 = *(const float*)(L0 + (p0 + u) * 8), a1 = *(const float*)(L1 + (p0 + u) * 8);
-                    const float a2 = *(const float*)(L2 + (p0 + u) * 8), a3 = *(const float*)(L3 + (p0 + u) * 8);
-                    rank += (a0 > pm ? 1 : 0) + (a1 > pm ? 1 : 0) + (a2 > pm ? 1 : 0) + (a3 > pm ? 1 : 0);
-                    near += (fabsf(a0 - pm) <= E2 ? 1 : 0) + (fabsf(a1 - pm) <= E2 ? 1 : 0) + (fabsf(a2 - pm) <= E2 ? 1 : 0) + (fabsf(a3 - pm) <= E2 ? 1 : 0);
-                }
-            }
-            const bool amb = valid && !(near <= 1);            // another survivor inside my 2 E window (I count once myself)
-            if (valid && !amb && rank < k) idx[((size_t)b * N + qrow) * k + rank] = j;
-            const unsigned long long m = __ballot(amb);
-            if (m) {
-                const int before = __builtin_popcountll(m & ((1ull << lane) - 1ull));
-                if (amb) wl[wcnt + before] = (unsigned)((mine - lists) >> 3) | ((unsigned)qq << 16);
-                wcnt += __builtin_popcountll(m);
-            }
-        }
-        if (wcnt > 512 - 192 || (it == 7 && wcnt > 0)) {       // (a trip adds at most 2 x 96 items)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            flush();
-        }
-    }
+    const K6Fin fin = {xb, xxb, xcb, ld, C, k, xvec, xxmax, K6_CANON, lists, cnts, lmn, wlbase + wave * 512, idx + (size_t)b * N * k,
+                       lane, qg, ch, chunk * Cut::QWG};
+    if (!exact_lists && k6_fast_final<Cut, CT, VEX>(fin)) return;
+    k6_counting_final<Cut>(fin, exact_lists || VEX);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // v6 WIDE (24 < k <= 40, N % 128 == 0, C <= 128): PointSegDA's graphs (k = 40, PointSegDA/Models.py:6-15; BASELINE.json configs[4]).
-// The same two sweeps, lists and final as knn6_kernel with the WORKGROUP re-cut so that the 232-byte survivor lists still fit the CU:
+// The phases of knn6_kernel (the k6_* functions above) under the other cut of the workgroup, K6Wide, so that the 232-byte survivor lists
+// still fit the CU:
 //   * workgroup = 64 queries (two groups of 32) x all N candidates; wave w: qg = w & 1, ch = w >> 1 sweeps a QUARTER of the candidates.
 //     A query's candidates are cut into 8 sub-ranges (quarter x half-wave lane): 512 lists of K6_CAP = 24 entries as before, but a query
 //     now owns 8 of them.  With k = 40 a query keeps ~50 survivors, ~6 per list: K6_CAP is six standard deviations away.
-//   * pass A leaves 128 running maxima per query; tau = their k-th largest.  Two lanes per query sort 64 each (the bitonic network of
-//     knn6_kernel), exchange them through v_permlane32_swap (max(a[i], b[63 - i]) = the 64 largest of the union, a bitonic sequence) and
+//   * pass A leaves 128 running maxima per query; tau = their k-th largest.  Two lanes per query sort 64 each (k6_sort64),
+//     exchange them through v_permlane32_swap (max(a[i], b[63 - i]) = the 64 largest of the union, a bitonic sequence) and
 //     merge.  Against 64 maxima the bound is tighter: ~1.2 k survivors instead of ~1.6 k.
 //   * fast final: EIGHT lanes per query (64 rank positions; exchanges at lane distance 8 through DPP row_ror, 16 / 32 through the
 //     permlane swaps); the counting final takes queries with more than 64 survivors.
 //   * no exact path inside: a workgroup whose lists overflow (massive ties: padded clouds) or whose bound is not finite raises its CLOUD's
 //     flag and leaves; the v5 kernel (knn.hip, KB = 1) runs right behind on the flagged clouds only (its workgroups of other clouds return at
 //     once) and overwrites their rows.  Indices bit-exact either way: both kernels rank by the canonical distance under the same total order.
-#define K6W_XS 132          // floats per query of the tau exchange image (128 maxima, 16-byte aligned rows, 4-bank skew)
-#define K6W_KMAX 40
-
-__device__ __forceinline__ unsigned k6w_x8(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true); }     // lane ^ 8 (row_ror:8)
-
 template <int CT>
 __global__ __launch_bounds__(512) void knn6w_kernel(const float* __restrict__ x, int ld, const float* __restrict__ xx_all, const float* __restrict__ xc_all,
                                                     const char* __restrict__ planes, int N, int C, int k, int* __restrict__ idx, int B,
                                                     int* __restrict__ cloud_flag) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    typedef K6Wide Cut;
     constexpr int NKB = CT / 16;
-    constexpr int PF = NKB >= 8 ? 1 : NKB >= 4 ? 2 : 4;
-    constexpr int NR = PF * NKB;
-    constexpr int UNR = NKB >= 8 ? 2 : 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, h = lane >> 5, qg = wave & 1, ch = wave >> 1;
+    const int l31 = lane & 31, h = lane >> 5, qg = wave & (Cut::QG - 1), ch = wave >> Cut::QGS;
     int b, chunk;
-    xcd_cloud_map(blockIdx.x, N / 64, B, b, chunk);
+    xcd_cloud_map(blockIdx.x, N / Cut::QWG, B, b, chunk);
     const float* xxb = xx_all + (size_t)b * N;
     const float* xcb = xc_all + (size_t)b * N;
     const size_t T0 = (size_t)b * (N / 32);
     const float* xb = x + (size_t)b * N * ld;
-    const int nt4 = N / 128;                                  // 32-candidate tiles of this wave's quarter
+    const int nt4 = N / (32 * Cut::PARTS);                    // 32-candidate tiles of this wave's quarter
 
-    char* lists = (char*)sm;                                  // [512 lists][K6_LSTR]; list = ((qg*4 + ch)*2 + h)*32 + query of the group = (qg*8 + t)*32 + query, t = 2 ch + h
-    float* xch = sm;                                          // tau exchange image [64 queries][K6W_XS], dead before pass B
+    char* lists = (char*)sm;                                  // [512 lists][K6_LSTR]; list = Cut::list_at(qg, query of the group, 2 ch + h)
+    float* xch = sm;                                          // tau exchange image [64 queries][Cut::XS], dead before pass B
     float* nxx = (float*)(lists + 512 * K6_LSTR);             // [N]  -xc_j / 2
     float* tauv = nxx + N;                                    // [64] (+64 unused)
-    int* cnts = (int*)(tauv + 128);                           // [64 queries][8 sub-ranges]
+    int* cnts = (int*)(tauv + 128);                           // [64 queries][8 lists]
     float* red = (float*)(cnts + 512);                        // [16]
     unsigned* wlbase = (unsigned*)(red + 16);                 // [8 waves][512 words]: fast final [8 queries][64]; counting final: work list
-    float* lmn = (float*)(wlbase + 8 * 512);                  // [64 queries][8 sub-ranges]
+    float* lmn = (float*)(wlbase + 8 * 512);                  // [64 queries][8 lists]
     const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)sm);
 
     float xcmax, xxmax;
     {
         float m = 0.f, mr = 0.f;
-        for (int j = tid; j < N; j += 512) {
-            const float v = xcb[j], w = xxb[j];
-            nxx[j] = -0.5f * v; m = fmaxf(m, v == v ? v : INFINITY); mr = fmaxf(mr, w == w ? w : INFINITY);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); mr = fmaxf(mr, __shfl_xor(mr, o, 64)); }
-        if (lane == 0) { red[wave] = m; red[8 + wave] = mr; }
-        __syncthreads();
-        xcmax = red[0]; xxmax = red[8];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) { xcmax = fmaxf(xcmax, red[w]); xxmax = fmaxf(xxmax, red[8 + w]); }
+        k6_fill_nxx(tid, N, xcb, xxb, nxx, m, mr);
+        k6_reduce_bounds(lane, wave, m, mr, red, xcmax, xxmax);
     }
     const float K6_CANON = (float)(C + 4) * 1.1920929e-07f;
-    const int q0 = chunk * 64 + qg * 32;                      // first query of this wave's group, local to the cloud
+    const int q0 = chunk * Cut::QWG + qg * 32;                // first query of this wave's group, local to the cloud
     const float xxq = xxb[q0 + l31];
     const float xcq = xcb[q0 + l31];
-    const float Eq = K6_EPS * (xcq + xcmax) + K6_CANON * (xxq + xxmax);      // (error budget: knn6_kernel / the file header)
+    const float Eq = K6_EPS * (xcq + xcmax) + K6_CANON * (xxq + xxmax);      // (error budget: the file header)
 
     k6bf16x8 qh[NKB], ql[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-        qh[kb] = *(const k6bf16x8*)(planes + k6_piece(T0 + (q0 >> 5), NKB, kb, 0, h, l31));
-        ql[kb] = *(const k6bf16x8*)(planes + k6_piece(T0 + (q0 >> 5), NKB, kb, 1, h, l31));
-    }
     const unsigned voff = (unsigned)(h * 512 + l31 * 16);
+    k6_load_query<NKB>(planes, T0 + (q0 >> 5), voff, qh, ql);
     const char* cand0 = planes + (T0 + (size_t)ch * nt4) * (NKB * 2048);
-    auto frag_load = [&](int tl, int kb, k6bf16x8& ah, k6bf16x8& al) {
-        const char* p = cand0 + (size_t)tl * (NKB * 2048) + kb * 2048;
-        ah = *(const k6bf16x8*)(p + voff);
-        al = *(const k6bf16x8*)(p + 1024 + voff);
-    };
-    // (the sweep of knn6_kernel over nt4 tiles: fragment ring, a scheduling barrier after every refill, UNR tiles per trip)
-    auto sweep = [&](auto&& sel) {
-        k6bf16x8 fh[NR], fl[NR];
-        auto tile = [&](auto SLOT, auto RING, int tl, int tn, auto&& sel_) {
-            constexpr int s0 = decltype(SLOT)::value * NKB;
-            constexpr bool ring = decltype(RING)::value;
-            f32x16 acc;
-            const float* p = nxx + (ch * nt4 + tl) * 32 + 4 * h;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const f32x4 v = *(const f32x4*)(p + 8 * g4);
-                acc[4 * g4] = v[0]; acc[4 * g4 + 1] = v[1]; acc[4 * g4 + 2] = v[2]; acc[4 * g4 + 3] = v[3];
-            }
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], qh[kb], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl[s0 + kb], qh[kb], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh[s0 + kb], ql[kb], acc, 0, 0, 0);
-                if (ring) {
-                    frag_load(tn, kb, fh[s0 + kb], fl[s0 + kb]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            sel_(acc, tl);
-        };
-        const int nmain = (nt4 / UNR) * UNR;
-        if (nmain > 0) {
-#pragma unroll
-            for (int tu = 0; tu < PF; ++tu)
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) frag_load(min(tu, nt4 - 1), kb, fh[tu * NKB + kb], fl[tu * NKB + kb]);
-            for (int t0 = 0; t0 < nmain; t0 += UNR) {
-                k6_static_for<0, UNR>([&](auto TU) {
-                    constexpr int tu = decltype(TU)::value;
-                    const int tl = t0 + tu;
-                    const int tn = min(tl + PF, nt4 - 1);
-                    tile(std::integral_constant<int, tu % PF>{}, std::true_type{}, tl, tn, sel);
-                });
-            }
-        }
-        for (int tl = nmain; tl < nt4; ++tl) {
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) frag_load(tl, kb, fh[kb], fl[kb]);
-            tile(std::integral_constant<int, 0>{}, std::false_type{}, tl, tl, sel);
-        }
-    };
 
     // ---- pass A: 16 running maxima per lane -> 128 per query
     {
         float cm[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) cm[r] = -INFINITY;
-        sweep([&](const f32x16& acc, int) {
+        k6_sweep<NKB>(cand0, voff, nxx, ch, h, nt4, qh, ql, [&](const f32x16& acc, int) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) cm[r] = fmaxf(cm[r], acc[r]);
         });
-        float* dst = xch + (qg * 32 + l31) * K6W_XS + (ch * 2 + h) * 16;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) { const f32x4 v = {cm[4 * g4], cm[4 * g4 + 1], cm[4 * g4 + 2], cm[4 * g4 + 3]}; *(f32x4*)(dst + 4 * g4) = v; }
+        k6_store_maxima(xch + (qg * 32 + l31) * Cut::XS + (ch * 2 + h) * 16, cm);
     }
     __syncthreads();
     // tau = k-th largest of the query's 128 maxima: lanes (l31, h = 0 / 1) of the group's ch = 0 wave each sort 64, then merge
     if (ch == 0) {
         const int qs = qg * 32 + l31;
         float v[64];
-        const float* src = xch + qs * K6W_XS + h * 64;
+        const float* src = xch + qs * Cut::XS + h * 64;
 #pragma unroll
         for (int i4 = 0; i4 < 16; ++i4) {
             const f32x4 t = *(const f32x4*)(src + 4 * i4);
             v[4 * i4] = t[0]; v[4 * i4 + 1] = t[1]; v[4 * i4 + 2] = t[2]; v[4 * i4 + 3] = t[3];
         }
-#pragma unroll
-        for (int k2 = 2; k2 <= 64; k2 <<= 1)
-#pragma unroll
-            for (int j = k2 >> 1; j > 0; j >>= 1)
-#pragma unroll
-                for (int i = 0; i < 64; ++i) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const float lo = fminf(v[i], v[l]), hi = fmaxf(v[i], v[l]);
-                        if ((i & k2) == 0) { v[i] = hi; v[l] = lo; }           // descending overall
-                        else { v[i] = lo; v[l] = hi; }
-                    }
-                }
+        k6_sort64(v);
         // the 64 largest of the two sorted halves: w[i] = max(mine[i], other[63 - i]) (a bitonic sequence; the partner lane holds it reversed)
         float w[64];
 #pragma unroll
@@ -982,7 +993,7 @@ __global__ __launch_bounds__(512) void knn6w_kernel(const float* __restrict__ x,
             }
         float t = w[0];
 #pragma unroll
-        for (int i = 1; i < K6W_KMAX; ++i) t = (i == k - 1) ? w[i] : t;
+        for (int i = 1; i < Cut::KMAX; ++i) t = (i == k - 1) ? w[i] : t;
         if (lane < 32) tauv[qs] = t;
     }
     __syncthreads();                                          // tau complete; the exchange image (aliases the lists) is dead from here on
@@ -990,369 +1001,26 @@ __global__ __launch_bounds__(512) void knn6w_kernel(const float* __restrict__ x,
     thr = thr == thr ? thr : -INFINITY;
 
     // ---- pass B: survivors -> this lane's private list
-    const int lid = ((qg * 4 + ch) * 2 + h) * 32 + l31;
+    const int lid = Cut::list_at(qg, l31, ch * 2 + h);
     char* LB = lists + (size_t)lid * K6_LSTR;
     const unsigned base = lds0 + (unsigned)(lid * K6_LSTR);
     unsigned ad = base, top = base;
-    sweep([&](const f32x16& acc, int tl) {
-        const int jb = (ch * nt4 + tl) * 32 + 4 * h;
-        int jv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) jv[r] = jb + (r & 3) + 8 * (r >> 2);
-        const float gate = fmaxf(acc[0], acc[15]);            // (MFMA -> VALU wait states: see knn6_kernel)
-#define K6_APPEND(ad_, val_, thr_, j_, gate_) asm volatile("v_cmpx_ge_f32_e32 vcc, %1, %2\n\tds_write2_b32 %0, %1, %3 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, -1" \
-                                                           : "+v"(ad_) : "v"(val_), "v"(thr_), "v"(j_), "v"(gate_) : "vcc", "memory")
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            K6_APPEND(ad, acc[r], thr, jv[r], gate);
-            if ((r & 3) == 3) { top = max(top, ad); ad = min(ad, base + K6_CAP * 8); }
-        }
-#undef K6_APPEND
-    });
+    k6_sweep<NKB>(cand0, voff, nxx, ch, h, nt4, qh, ql, [&](const f32x16& acc, int tl) { k6_append16(ad, top, base, acc, thr, (ch * nt4 + tl) * 32 + 4 * h); });
     const int cnt = (int)(ad - base) >> 3;
     const int ovf = (top > base + K6_CAP * 8 || !(Eq < INFINITY)) ? 1 : 0;
     if (__syncthreads_or(ovf)) {                              // overflow / no usable bound: this cloud goes to the v5 kernel launched behind
         if (tid == 0) cloud_flag[b] = 1;
         return;
     }
-    // ---- F0: lists to the pd domain (pd' = 2 a - xc_q), filled to the end with {-inf, 0}
-    {
-        float mn = 0.f;
-#pragma unroll
-        for (int p0 = 0; p0 < K6_LENT; p0 += 4) {
-            k6u32x2 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *(const k6u32x2*)(LB + (p0 + u) * 8);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float a = __int_as_float((int)v[u][0]);
-                const float p = fmaf(2.0f, a, -xcq);
-                const bool live = p0 + u < cnt;
-                const k6u32x2 w = {(unsigned)__float_as_int(live ? p : -INFINITY), live ? v[u][1] : 0u};
-                *(k6u32x2*)(LB + (p0 + u) * 8) = w;
-                if (live) mn = fminf(mn, nxx[v[u][1] & 4095u]);
-            }
-        }
-        cnts[(qg * 32 + l31) * 8 + ch * 2 + h] = cnt;
-        lmn[(qg * 32 + l31) * 8 + ch * 2 + h] = mn;
-    }
+    k6_f0<Cut, false>(LB, cnt, false, xcq, nxx, cnts, lmn, qg * 32 + l31, ch * 2 + h);              // lists -> pd domain
     __syncthreads();
 
     // ---------------------------------------------------------------------------------------------------------------- final: exact ranks
     const bool xvec = (ld & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (C & 3) == 0;
-    auto list_at = [&](int qlc_, int t) -> char* { return lists + (size_t)(((qg * 8 + t) * 32 + qlc_) * K6_LSTR); };
-    // ---- fast final (every query of the wave has at most 64 survivors): eight lanes per query, lane l serves query l & 7 of the wave's eight
-    // (queries ch * 8 .. + 7 of the group) and holds rank positions 8 m .. 8 m + 7 of its 64 (m = l >> 3)
-    {
-        const int ql8 = lane & 7, m = lane >> 3;
-        const int qlc = ch * 8 + ql8;
-        const int qq = qg * 32 + qlc, qrow = chunk * 64 + qq;
-        const k6i32x4 ca = *(const k6i32x4*)(cnts + qq * 8), cb = *(const k6i32x4*)(cnts + qq * 8 + 4);
-        int pp[9];
-        pp[0] = 0; pp[1] = ca[0]; pp[2] = pp[1] + ca[1]; pp[3] = pp[2] + ca[2]; pp[4] = pp[3] + ca[3];
-        pp[5] = pp[4] + cb[0]; pp[6] = pp[5] + cb[1]; pp[7] = pp[6] + cb[2]; pp[8] = pp[7] + cb[3];
-        const int n = pp[8];
-        int nmaxw = n;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nmaxw = max(nmaxw, __shfl_xor(nmaxw, o, 64));
-        if (nmaxw <= 64) {
-            const f32x4 ma = *(const f32x4*)(lmn + qq * 8), mb = *(const f32x4*)(lmn + qq * 8 + 4);
-            const float xm = -2.0f * fminf(fminf(fminf(ma[0], ma[1]), fminf(ma[2], ma[3])), fminf(fminf(mb[0], mb[1]), fminf(mb[2], mb[3])));
-            const float xqr = xxb[qrow], xqc = xcb[qrow];
-            const float E2 = 2.0f * (K6_EPS * (xqc + xm) + K6_CANON * (xqr + xxmax));
-            float pv[8];
-            int jv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = 8 * m + i;
-                int t = 0, pb = 0;
-#pragma unroll
-                for (int u = 1; u < 8; ++u) { const bool ge = e >= pp[u]; t = ge ? u : t; pb = ge ? pp[u] : pb; }
-                const k6u32x2 v = *(const k6u32x2*)(list_at(qlc, e < n ? t : 0) + (e < n ? e - pb : 0) * 8);
-                pv[i] = e < n ? __int_as_float((int)v[0]) : -INFINITY;
-                jv[i] = e < n ? (int)v[1] : 0x7fffffff;
-            }
-            auto x16 = [&](unsigned v) -> unsigned { const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); return (m & 2) ? r[0] : r[1]; };
-            auto x32 = [&](unsigned v) -> unsigned { const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false); return (m & 4) ? r[0] : r[1]; };
-            auto cex_local = [&](int jj, bool desc) {
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const int c = a ^ jj;
-                    if (c > a) {
-                        const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
-                        const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
-                        const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
-                        pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
-                    }
-                }
-            };
-            auto cex_cross = [&](int bit, bool desc) {       // positions 8 m + i and 8 (m ^ bit) + i: the lane whose m lacks `bit` is the lower position
-                const bool low = (m & bit) == 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const unsigned uv = __float_as_uint(pv[i]), uj = (unsigned)jv[i];
-                    const float ov = __uint_as_float(bit == 1 ? k6w_x8(uv) : bit == 2 ? x16(uv) : x32(uv));
-                    const int oj = (int)(bit == 1 ? k6w_x8(uj) : bit == 2 ? x16(uj) : x32(uj));
-                    const bool sw = low ? (desc ? pv[i] < ov : pv[i] > ov) : (desc ? ov < pv[i] : ov > pv[i]);
-                    pv[i] = sw ? ov : pv[i]; jv[i] = sw ? oj : jv[i];
-                }
-            };
-            // bitonic network over positions a = 8 m + i; a pair keeps the larger value at the lower position iff (a & k2) == 0
-#pragma unroll
-            for (int a = 0; a < 8; a += 2) {                    // k2 = 2
-                const bool desc = (a & 2) == 0;
-                const bool sw = desc ? pv[a] < pv[a + 1] : pv[a] > pv[a + 1];
-                const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-            }
-#pragma unroll
-            for (int jj = 2; jj > 0; jj >>= 1)                  // k2 = 4: direction by bit 2 of the position
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const int c = a ^ jj;
-                    if (c > a) {
-                        const bool desc = (a & 4) == 0;
-                        const bool sw = desc ? pv[a] < pv[c] : pv[a] > pv[c];
-                        const float ta = sw ? pv[c] : pv[a], tc = sw ? pv[a] : pv[c];
-                        const int ja = sw ? jv[c] : jv[a], jc = sw ? jv[a] : jv[c];
-                        pv[a] = ta; pv[c] = tc; jv[a] = ja; jv[c] = jc;
-                    }
-                }
-            { const bool d = (m & 1) == 0; cex_local(4, d); cex_local(2, d); cex_local(1, d); }                                              // k2 = 8
-            { const bool d = (m & 2) == 0; cex_cross(1, d); cex_local(4, d); cex_local(2, d); cex_local(1, d); }                             // k2 = 16
-            { const bool d = (m & 4) == 0; cex_cross(2, d); cex_cross(1, d); cex_local(4, d); cex_local(2, d); cex_local(1, d); }            // k2 = 32
-            { cex_cross(4, true); cex_cross(2, true); cex_cross(1, true); cex_local(4, true); cex_local(2, true); cex_local(1, true); }      // k2 = 64
-            // flag: gap to the next survivor in rank not provably larger than 2 E
-            const float nxt0 = __shfl(pv[0], lane + 8, 64), prv7 = __shfl(pv[7], lane - 8, 64);
-            unsigned amb = 0u;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) amb |= (8 * m + i + 1 < n && !(pv[i] - pv[i + 1] > E2)) ? (3u << i) : 0u;
-            amb |= (m < 7 && 8 * m + 8 < n && !(pv[7] - nxt0 > E2)) ? 0x80u : 0u;
-            amb |= (m > 0 && 8 * m < n && !(prv7 - pv[0] > E2)) ? 1u : 0u;
-            const int nfl = __builtin_popcount(amb);
-            int nflag = 0, foff = 0;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) { const int f = __shfl(nfl, ql8 + 8 * t, 64); nflag += f; foff += t < m ? f : 0; }
-            unsigned* slots = wlbase + wave * 512 + ql8 * 64 + foff;     // this lane's part of the query's [64]: candidate index in, canonical distance out
-            {
-                int c = 0;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    if ((amb >> a) & 1u) { slots[c] = (unsigned)jv[a]; ++c; }
-                }
-            }
-            int fmaxw = nflag;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) fmaxw = max(fmaxw, __shfl_xor(fmaxw, o, 64));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (fmaxw > 0) {                                    // canonical distances of the flagged pairs, densely packed over the wave's lanes
-                int offs[9];
-                offs[0] = 0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) offs[q + 1] = offs[q] + __builtin_amdgcn_readlane(nflag, q);
-                const int total = offs[8];
-                unsigned* wslots = wlbase + wave * 512;
-                const int qbase = chunk * 64 + qg * 32 + ch * 8;
-                for (int i0 = 0; i0 < total; i0 += 64) {
-                    const int i = i0 + lane;
-                    if (i < total) {
-                        int q = 0, ob = 0;
-#pragma unroll
-                        for (int t = 1; t < 8; ++t) { const bool ge = i >= offs[t]; q = ge ? t : q; ob = ge ? offs[t] : ob; }
-                        unsigned* sp = wslots + q * 64 + (i - ob);
-                        const int j = (int)*sp;
-                        const int qr = qbase + q;
-                        const float* rq = xb + (size_t)qr * ld;
-                        const float* rj = xb + (size_t)j * ld;
-                        float acc = 0.f;
-                        if (!xvec) {
-                            for (int c = 0; c < C; ++c) acc = fmaf(rq[c], rj[c], acc);
-                        } else {
-                            constexpr int CHV = CT >= 128 ? 8 : 16;
-                            for (int c = 0; c < C; c += 4 * CHV) {
-                                f32x4 a4[CHV], b4[CHV];
-#pragma unroll
-                                for (int u = 0; u < CHV; ++u)
-                                    if (c + 4 * u < C) { a4[u] = *(const f32x4*)(rq + c + 4 * u); b4[u] = *(const f32x4*)(rj + c + 4 * u); }
-#pragma unroll
-                                for (int u = 0; u < CHV; ++u)
-                                    if (c + 4 * u < C) {
-#pragma unroll
-                                        for (int e = 0; e < 4; ++e) acc = fmaf(a4[u][e], b4[u][e], acc);
-                                    }
-                            }
-                        }
-                        const float t2 = fmaf(2.0f, acc, -xxb[j]);
-                        *sp = (unsigned)__float_as_int(t2 - xxb[qr]);
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            {
-                int c = 0;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    if ((amb >> a) & 1u) { pv[a] = __int_as_float((int)slots[c]); ++c; }
-                }
-            }
-            if (fmaxw > 0) {                                    // settle the flagged runs under the full order (value desc, index asc)
-                for (int pass = 0; pass < 64; ++pass) {
-                    bool moved = false;
-#pragma unroll
-                    for (int a = 0; a < 7; a += 2) {
-                        const bool sw = k6_beats(pv[a + 1], jv[a + 1], pv[a], jv[a]);
-                        const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                        const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                        pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-                        moved |= sw;
-                    }
-#pragma unroll
-                    for (int a = 1; a < 7; a += 2) {
-                        const bool sw = k6_beats(pv[a + 1], jv[a + 1], pv[a], jv[a]);
-                        const float ta = sw ? pv[a + 1] : pv[a], tc = sw ? pv[a] : pv[a + 1];
-                        const int ja = sw ? jv[a + 1] : jv[a], jc = sw ? jv[a] : jv[a + 1];
-                        pv[a] = ta; pv[a + 1] = tc; jv[a] = ja; jv[a + 1] = jc;
-                        moved |= sw;
-                    }
-                    {                                            // the odd pair across the lane boundary: (8 m + 7, 8 (m + 1))
-                        const float nv = __shfl(pv[0], lane + 8, 64), pvv = __shfl(pv[7], lane - 8, 64);
-                        const int nj = __shfl(jv[0], lane + 8, 64), pj = __shfl(jv[7], lane - 8, 64);
-                        const bool swh = m < 7 && k6_beats(nv, nj, pv[7], jv[7]);
-                        const bool swl = m > 0 && k6_beats(pv[0], jv[0], pvv, pj);
-                        pv[7] = swh ? nv : pv[7]; jv[7] = swh ? nj : jv[7];
-                        pv[0] = swl ? pvv : pv[0]; jv[0] = swl ? pj : jv[0];
-                        moved |= swh | swl;
-                    }
-                    if (!__any(moved)) break;
-                }
-            }
-            {
-                int* out = idx + ((size_t)b * N + qrow) * k;
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-                    const int pos = 8 * m + a;
-                    if (pos < k && pos < n) out[pos] = jv[a];
-                }
-            }
-            return;
-        }
-    }
-    // ---- counting final (a query of the wave has more than 64 survivors): two queries per trip (one per half-wave), lane l31 owns entries
-    // l31 + 32 s of the query's eight concatenated lists; logic as in knn6_kernel
-    unsigned* wl = wlbase + wave * 512;
-    int wcnt = 0;
-    auto flush = [&]() {
-        for (int i0 = 0; i0 < wcnt; i0 += 64) {
-            const int i = i0 + lane;
-            if (i < wcnt) {
-                const unsigned item = wl[i];
-                const int qq_ = (int)(item >> 16);
-                char* ent = lists + (size_t)(item & 0xffffu) * 8;
-                const int j = *(const int*)(ent + 4);
-                const int qrow_ = chunk * 64 + qq_;
-                const float* rq = xb + (size_t)qrow_ * ld;
-                const float* rj = xb + (size_t)j * ld;
-                float acc = 0.f;
-                if (xvec) {
-                    for (int c = 0; c < C; c += 32) {
-                        f32x4 a4[8], b4[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            if (c + 4 * u < C) { a4[u] = *(const f32x4*)(rq + c + 4 * u); b4[u] = *(const f32x4*)(rj + c + 4 * u); }
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            if (c + 4 * u < C) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) acc = fmaf(a4[u][e], b4[u][e], acc);
-                            }
-                    }
-                } else {
-                    for (int c = 0; c < C; ++c) acc = fmaf(rq[c], rj[c], acc);
-                }
-                const float t2 = fmaf(2.0f, acc, -xxb[j]);
-                *(float*)ent = t2 - xxb[qrow_];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int i0 = 0; i0 < wcnt; i0 += 64) {
-            const int i = i0 + lane;
-            const bool on = i < wcnt;
-            const unsigned item = on ? wl[i] : 0u;
-            const int qq_ = (int)(item >> 16), qlc_ = qq_ & 31;
-            const k6u32x2 me = *(const k6u32x2*)(lists + (size_t)(item & 0xffffu) * 8);
-            const float pm = __int_as_float((int)me[0]);
-            const int jm = (int)me[1];
-            int rank = 0;
-            for (int t = 0; t < 8; ++t) {
-                const char* Lq = list_at(qlc_, t);
-#pragma unroll
-                for (int p0 = 0; p0 < K6_CAP; p0 += 8) {
-                    k6u32x2 ke[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) ke[u] = *(const k6u32x2*)(Lq + (p0 + u) * 8);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) rank += k6_beats(__int_as_float((int)ke[u][0]), (int)ke[u][1], pm, jm) ? 1 : 0;
-                }
-            }
-            if (on && rank < k) idx[((size_t)b * N + chunk * 64 + qq_) * k + rank] = jm;
-        }
-        wcnt = 0;
-    };
-    for (int it = 0; it < 4; ++it) {
-        const int qlc = ch * 8 + it * 2 + h;                   // query of the group
-        const int qq = qg * 32 + qlc;                          // query of the workgroup
-        const int qrow = chunk * 64 + qq;                      // query of the cloud
-        const float xq = xxb[qrow], xqc = xcb[qrow];
-        const k6i32x4 ca = *(const k6i32x4*)(cnts + qq * 8), cb = *(const k6i32x4*)(cnts + qq * 8 + 4);
-        const f32x4 ma = *(const f32x4*)(lmn + qq * 8), mb = *(const f32x4*)(lmn + qq * 8 + 4);
-        const float xm = -2.0f * fminf(fminf(fminf(ma[0], ma[1]), fminf(ma[2], ma[3])), fminf(fminf(mb[0], mb[1]), fminf(mb[2], mb[3])));
-        const float E2 = 2.0f * (K6_EPS * (xqc + xm) + K6_CANON * (xq + xxmax));
-        int pp[9];
-        pp[0] = 0; pp[1] = ca[0]; pp[2] = pp[1] + ca[1]; pp[3] = pp[2] + ca[2]; pp[4] = pp[3] + ca[3];
-        pp[5] = pp[4] + cb[0]; pp[6] = pp[5] + cb[1]; pp[7] = pp[6] + cb[2]; pp[8] = pp[7] + cb[3];
-        const int n = pp[8];
-        const int nmax = max(__builtin_amdgcn_readlane(n, 0), __builtin_amdgcn_readlane(n, 32));
-        int cmx = max(max(max(ca[0], ca[1]), max(ca[2], ca[3])), max(max(cb[0], cb[1]), max(cb[2], cb[3])));
-        cmx = max(__builtin_amdgcn_readlane(cmx, 0), __builtin_amdgcn_readlane(cmx, 32));
-        const char* Lq0 = list_at(qlc, 0);                     // list t of the query: Lq0 + t * 32 * K6_LSTR
-        for (int s0 = 0; s0 < nmax; s0 += 32) {
-            const int e = s0 + l31;
-            const bool valid = e < n;
-            int t = 0, pb = 0;
-#pragma unroll
-            for (int u = 1; u < 8; ++u) { const bool ge = e >= pp[u]; t = ge ? u : t; pb = ge ? pp[u] : pb; }
-            const char* mine = Lq0 + (size_t)(valid ? t : 0) * (32 * K6_LSTR) + (valid ? e - pb : 0) * 8;
-            const k6u32x2 me = *(const k6u32x2*)mine;
-            const float pm = __int_as_float((int)me[0]);
-            const int j = (int)me[1];
-            int rank = 0, near = 0;
-            for (int p0 = 0; p0 < cmx; ++p0) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float a0 = *(const float*)(Lq0 + (size_t)u * (32 * K6_LSTR) + p0 * 8);
-                    rank += a0 > pm ? 1 : 0;
-                    near += fabsf(a0 - pm) <= E2 ? 1 : 0;
-                }
-            }
-            const bool amb = valid && !(near <= 1);
-            if (valid && !amb && rank < k) idx[((size_t)b * N + qrow) * k + rank] = j;
-            const unsigned long long mm = __ballot(amb);
-            if (mm) {
-                const int before = __builtin_popcountll(mm & ((1ull << lane) - 1ull));
-                if (amb) wl[wcnt + before] = (unsigned)((mine - lists) >> 3) | ((unsigned)qq << 16);
-                wcnt += __builtin_popcountll(mm);
-            }
-        }
-        if (wcnt > 512 - 384 || (it == 3 && wcnt > 0)) {       // (a trip adds at most 2 x 192 items)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            flush();
-        }
-    }
+    const K6Fin fin = {xb, xxb, xcb, ld, C, k, xvec, xxmax, K6_CANON, lists, cnts, lmn, wlbase + wave * 512, idx + (size_t)b * N * k,
+                       lane, qg, ch, chunk * Cut::QWG};
+    if (k6_fast_final<Cut, CT, false>(fin)) return;
+    k6_counting_final<Cut>(fin, false);
 }
 
 static size_t knn6_lds_bytes(int N) { return (size_t)512 * K6_LSTR + (size_t)N * 4 + 128 * 4 + 512 * 4 + 64 + (size_t)8 * 512 * 4 + 512 * 4; }

@@ -1767,3 +1767,31 @@ def test_knn_wide_mixed_clouds_flag_handover(dev):
     got = Fh.knn_graph(x.view(B * N, C).to(dev), B, N, k).idx.view(B, N, k).cpu().numpy()
     assert got.min() >= 0 and got.max() < N
     assert np.array_equal(got, want), "mismatching rows per cloud: %s" % [(int((got[b] != want[b]).any(-1).sum())) for b in range(B)]
+
+
+@pytest.mark.parametrize("k,mod", [(20, 6), (40, 3)])
+def test_knn_counting_final_without_list_overflow(dev, k, mod):
+    """The counting finals of knn6_kernel (k = 20) and knn6w_kernel (k = 40) run only when a query keeps more survivors than the fast final
+    holds (32 / 64) WITHOUT any of its lists passing K6_CAP = 24 entries (that would be the exact path / the v5 hand-over instead).
+    Nothing outside the kernel shows which final ran, so the input forces it: B = 1, N = 384, C = 64, point j an exact copy of centre
+    j % mod.  Copies have identical bf16 images, hence identical approximate distances: they pass the threshold together or not at all.
+
+    Geometry (candidate j: tile T = j // 32, row = j % 32, half-wave h = (row >> 2) & 1, accumulator register r = (row & 3) + 4 (row >> 3);
+    part = T // 6 of 2 halves (narrow), T // 3 of 4 quarters (wide); list = 2 part + h; pass-A maxima slot = (part, h, r)), in numpy:
+        j = np.arange(384); T = j // 32; row = j % 32; h = (row >> 2) & 1; r = (row & 3) + 4 * (row >> 3)
+        parts = 2 (narrow) or 4 (wide); part = T // (12 // parts); m = j % mod == c (any cluster c)
+        np.bincount((2 * part + h)[m])          # copies per list
+        len(set(zip(part[m], h[m], r[m])))      # maxima slots that hold the cluster
+      narrow, mod 6: every cluster has 64 copies, 16 in each of the query's 4 lists (< 24), and sits in 32 of the 64 maxima slots (>= k = 20,
+                     so tau IS the cluster's value and all 64 copies survive: 64 > 32);
+      wide, mod 3:   128 copies, 16 in each of the 8 lists, in all 128 slots (>= k = 40): 128 survivors > 64.
+    (mod 4 for the wide case would leave the cluster in 32 slots only: tau falls to the next cluster and 192 survivors land on the cap.)
+    The centres are ~ sqrt(2 C / 3) apart, far outside every error bound: the copies are the only survivors.  All survivors of a query tie
+    exactly, so every one of them goes through the work list and the flush; the oracle's order among them is by index."""
+    Fh = _fh()
+    N, C = 384, 64
+    centres = _rand((mod, C), 640 + mod)
+    x = centres[torch.arange(N) % mod].view(1, N, C).contiguous()
+    want = knn_canon.knn_point_major(x, k)
+    got = Fh.knn_graph(x.view(N, C).to(dev), 1, N, k).idx.view(1, N, k).cpu().numpy()
+    assert np.array_equal(got, want), "mismatching rows: %d" % int((got != want).any(-1).sum())
