@@ -497,6 +497,25 @@ int mlsp_sgd_flat_f32(float* P, float* B, const uint32_t* off, const uint32_t* n
                       double momentum, double dampening, double weight_decay, int nesterov, int maximize, int first, float* tile_amax,
                       mlsp_stream_t stream);
 
+/* The same two steps for a model split into parameter groups (at most MLSP_FLAT_MAX_GROUPS: "no weight decay on BatchNorm and biases",
+ * per-group learning rates), still ONE launch: seg_group[s] (host array, nullable = all 0) names the group of segment s, groups[] (host
+ * array, ngroups entries) holds every group's hyperparameters, and each workgroup reads those of the segment that owns its tile.  The
+ * segments may come in any order of groups: tiles and tile_amax are numbered segment by segment as above.  Symbols added under ABI v13.
+ * Adam: a group's step >= 1 numbers this update for its parameters and goes to its step_out (nullable, device float).  decoupled != 0 is
+ * AdamW (fused_adam_utils.cuh ADAM_MODE::ADAMW): param -= lr * weight_decay * param in double before the moments, the gradient untouched.
+ * SGD: B may be NULL only when every group has momentum == 0; first is per group.
+ * MLSP_ERR_ARG before any launch: ngroups outside [1, 8], a seg_group entry outside [0, ngroups), a group with step < 1, a NULL or
+ * misaligned flat buffer, momentum != 0 in some group while B is NULL, a NULL gradient or an empty segment.
+ * mlsp_adam_flat_f32 / mlsp_sgd_flat_f32 are the one-group forms of these. */
+#define MLSP_FLAT_MAX_GROUPS 8
+typedef struct mlsp_adam_group { double lr, beta1, beta2, weight_decay, eps; int64_t step; int32_t decoupled; float* step_out; } mlsp_adam_group_t;
+typedef struct mlsp_sgd_group { double lr, momentum, dampening, weight_decay; int32_t nesterov, maximize, first; } mlsp_sgd_group_t;
+int mlsp_adam_flat_groups_f32(float* P, float* M, float* V, const uint32_t* off, const uint32_t* numel, const float* const* grads,
+                              const uint8_t* seg_group, int nseg, const mlsp_adam_group_t* groups, int ngroups, float* tile_amax,
+                              mlsp_stream_t stream);
+int mlsp_sgd_flat_groups_f32(float* P, float* B, const uint32_t* off, const uint32_t* numel, const float* const* grads, const uint8_t* seg_group,
+                             int nseg, const mlsp_sgd_group_t* groups, int ngroups, float* tile_amax, mlsp_stream_t stream);
+
 /* The edge stages of the vector-attention block (PointDA/hengshuang_transformer/transformer.py:28-44) between its GEMMs (csrc/vecattn.hip).
  * P = B N points, k slots per point (1 <= k <= 64), E = P k edges, e = (i, s), j = idx[i][s] (int32 [B][N][k], local to the cloud; an
  * entry may repeat inside a row).  Every [E][d] / [P][d] matrix is fp32, channels contiguous; d % 4 == 0, pointers and row pitches

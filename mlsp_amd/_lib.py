@@ -23,6 +23,8 @@ SIGNATURES = {
     "mlsp_abi_version": [],
     "mlsp_adam_flat_f32": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I64, _P, _P, _P],
     "mlsp_sgd_flat_f32": [_P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _I, _I, _I, _P, _P],
+    "mlsp_adam_flat_groups_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P],
+    "mlsp_sgd_flat_groups_f32": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P],
     "mlsp_strerror": [_I],
     "mlsp_workspace_bytes": [_I, _I, _I],
     "mlsp_knn_f32": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P],
@@ -126,6 +128,21 @@ class Seg(_c.Structure):
 class Bound(_c.Structure):
     """mlsp_bound_t of include/mlsp_hip.h: caller-owned partial maxima of one GEMM operand (functional.OperandBounds)"""
     _fields_ = [("ptr", _P), ("rows", _c.c_long), ("cols", _I), ("ld", _I), ("partials", _P), ("valid", _I), ("n", _I)]
+
+
+class MlspAdamGroup(_c.Structure):
+    """mlsp_adam_group_t of include/mlsp_hip.h: one parameter group of mlsp_adam_flat_groups_f32"""
+    _fields_ = [("lr", _D), ("beta1", _D), ("beta2", _D), ("weight_decay", _D), ("eps", _D), ("step", _I64), ("decoupled", _c.c_int32),
+                ("step_out", _P)]
+
+
+class MlspSgdGroup(_c.Structure):
+    """mlsp_sgd_group_t of include/mlsp_hip.h: one parameter group of mlsp_sgd_flat_groups_f32"""
+    _fields_ = [("lr", _D), ("momentum", _D), ("dampening", _D), ("weight_decay", _D), ("nesterov", _c.c_int32), ("maximize", _c.c_int32),
+                ("first", _c.c_int32)]
+
+
+FLAT_MAX_GROUPS = 8            # MLSP_FLAT_MAX_GROUPS
 
 
 # Sources of ready-made bounds for weight operands (objects with .weight_bounds(tensor) -> (device pointer, n) | None): mlsp_amd.optim.FlatAdam
