@@ -49,7 +49,7 @@ extern "C" {
 
 typedef struct ihipStream_t* mlsp_stream_t; /* == hipStream_t */
 
-#define MLSP_ABI_VERSION 13
+#define MLSP_ABI_VERSION 14
 #define MLSP_OK 0
 #define MLSP_ERR_ARG (-1)
 #define MLSP_ERR_WORKSPACE (-2)
@@ -220,7 +220,11 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
  * conv5/bn5/LeakyReLU/adaptive_max_pool1d (PointDA/Models.py:132-136) and the T-Net's conv2d3 + torch.max(dim=2)
  * (PointDA/model_utils.py:116-117).  out [B][Cout].  Backward is closed-form through the Gram matrix X^T X (colmax.hip):
  * the dense [P][Cout] gradient is never formed.  Saved: ysel [B][Cout], arg [B][Cout], bn_save [4][Cout].  X must be
- * contiguous (ldx == Cin) for the backward. */
+ * contiguous (ldx == Cin) for the backward.  arg is always in [0, N): a column of a cloud whose Y is all NaN names row 0.
+ * mlsp_pointmlp_colmax_panel_rows (ABI v14; a shape query like mlsp_pointmlp_bwd_stats_parts, launches nothing): the height (64 or 128) of
+ * the row panels whose column extremes the forward takes in its GEMM epilogue for this shape and product mode -- Y is then never written,
+ * N / rows panels per cloud are merged --, or 0 when the forward writes Y and selects in a pass of its own. */
+int mlsp_pointmlp_colmax_panel_rows(int B, int N, int Cin, int Cout, int precision);
 int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin, const float* W, int ldw, int Cout,
                                  const float* gamma, const float* beta, float* run_mean, float* run_var, float momentum, float eps,
                                  int training, int act, float slope, float* out, float* ysel, int32_t* arg, float* bn_save, int precision, void* ws,

@@ -762,6 +762,22 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
     return MLSP_OK;
 }
 
+// Panel height of the fused forward of pointmlp_colmax -- statistics AND the per-cloud column extreme out of the GEMM epilogue, Y never
+// written: the GEMM keeps K whole and every cloud is a whole number of its row panels --, or 0: Y is written and colsel_kernel reads it.
+// (under the caller's GemmPrecisionScope: the tile choice depends on the product mode)
+static int colmax_fused_panel_rows(int N, int P, int Cin, int Cout) {
+    const int prow = gemm_panel_rows(P, Cout, Cin);
+    return ((N % prow == 0) && gemm_stat_parts(P, Cout, Cin) > 0) ? prow : 0;
+}
+
+// Shape query: the row-panel height (64 or 128) mlsp_pointmlp_colmax_fwd_f32 takes its per-panel column extremes at for this shape and
+// product mode (N / rows panels per cloud), or 0 when that forward writes Y and selects in a pass of its own.
+int mlsp_pointmlp_colmax_panel_rows(int B, int N, int Cin, int Cout, int precision) {
+    if (precision < 0 || precision > 3 || B <= 0 || N <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    GemmPrecisionScope prec_scope_(precision);
+    return colmax_fused_panel_rows(N, B * N, Cin, Cout);
+}
+
 int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin, const float* W, int ldw, int Cout,
                                  const float* gamma, const float* beta, float* run_mean, float* run_var, float momentum, float eps,
                                  int training, int act, float slope, float* out, float* ysel, int32_t* arg, float* bn_save, int precision, void* ws,
@@ -773,12 +789,11 @@ int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin,
     Workspace w(ws, ws_bytes);
     const int fused_parts = training ? gemm_stat_parts(P, Cout, Cin) : 0;
     // fully fused path: statistics AND the per-cloud column extreme come out of the GEMM epilogue, Y is never written
-    const int prow = gemm_panel_rows(P, Cout, Cin);
-    const bool fuse_sel = (N % prow == 0) && gemm_stat_parts(P, Cout, Cin) > 0;
+    const int prow = colmax_fused_panel_rows(N, P, Cin, Cout);             // 0: Y is written
+    const bool fuse_sel = prow > 0;
     float* Y = fuse_sel ? nullptr : w.take<float>((size_t)P * Cout);
-    const int ntm = (P + prow - 1) / prow;
-    float* pv = fuse_sel ? w.take<float>((size_t)ntm * Cout) : nullptr;
-    int* pr = fuse_sel ? w.take<int>((size_t)ntm * Cout) : nullptr;
+    float* pv = fuse_sel ? w.take<float>((size_t)(P / prow) * Cout) : nullptr;      // (N % prow == 0: P / prow whole panels)
+    int* pr = fuse_sel ? w.take<int>((size_t)(P / prow) * Cout) : nullptr;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(P);
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
     GemmOpts o; o.stat_part = fused_parts ? part : nullptr; o.sel_gamma = fuse_sel ? gamma : nullptr; o.sel_val = pv; o.sel_row = pr;

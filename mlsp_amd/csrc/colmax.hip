@@ -62,7 +62,7 @@ __global__ void colsel_panels_kernel(const float* __restrict__ pv, const int* __
         if (better || (v == best && r < brow)) { best = v; brow = r; }
     }
     ysel[t] = best;
-    arg[t] = brow - b * N;
+    arg[t] = brow == 0x7fffffff ? 0 : brow - b * N;      // no panel took a row (a column of NaN): in range, as colsel_kernel
     if (bn) out[t] = lrelu_or_relu(fmaf(best, bn[c], bn[C + c]), act, slope);
 }
 

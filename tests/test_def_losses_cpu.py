@@ -65,7 +65,7 @@ def test_library_exports_the_def_loss_entry_points():
     for name in SYMBOLS:
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
-    assert lib.mlsp_abi_version() == 13
+    assert lib.mlsp_abi_version() == 14
 
 
 def test_def_losses_have_no_cpu_fallback():

@@ -102,7 +102,7 @@ def test_group_structs_match_the_header():
         assert names == [n for n, _ in cls._fields_], (cname, names)
     assert ctypes.sizeof(_lib.MlspAdamGroup) == 64 and ctypes.sizeof(_lib.MlspSgdGroup) == 48
     assert "#define MLSP_FLAT_MAX_GROUPS 8" in src and _lib.FLAT_MAX_GROUPS == 8
-    assert "#define MLSP_ABI_VERSION 13" in src
+    assert "#define MLSP_ABI_VERSION 14" in src
 
 
 ERR_ARG = -1                                                   # MLSP_ERR_ARG: refused before any launch
