@@ -550,6 +550,35 @@ int mlsp_vecattn_aggregate_bwd_f32(const float* dres, const float* attn, const f
 int mlsp_vecattn_relu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t stream);
 int mlsp_vecattn_relu_bwd_f32(const float* dy, const float* y, int64_t rows, int d, float* dx, mlsp_stream_t stream);
 
+/* What the Point-BERT transformer encoder (PointDA/model_utils.py:201-289) runs between its GEMMs (csrc/attn.hip): the multi-head attention
+ * core, LayerNorm and GELU.  fp32 throughout (no product mode); every pointer and row pitch 16-byte aligned, channel counts multiples of 4;
+ * anything outside the limits returns MLSP_ERR_UNSUPPORTED and launches nothing.  No atomics: results are bit-identical run to run.
+ *
+ * Attention core.  qkv [B L][ld] is the qkv GEMM's output as it stands: with d = H dh, the q, k and v of head h are the column slices at
+ * h dh, d + h dh and 2 d + h dh (ld >= 3 d).  out [B L][d] (head-interleaved: the reference's transpose(1, 2).reshape) = softmax(scale q k^T) v
+ * per (cloud, head); lse [B][H][L] = row maximum + log(row sum) of the scaled logits.  One launch; nothing of size L^2 touches memory.
+ * Limits: dh % 4 == 0, dh <= 128, L <= 512 and L dh <= 16384 (two [L][dh] fp32 arrays of a head stay in LDS). */
+int mlsp_mhsa_fwd_f32(const float* qkv, int ld, int B, int L, int H, int dh, float scale, float* out, float* lse, mlsp_stream_t stream);
+/* dqkv [B L][ldd] in qkv's layout (every element of its first 3 d columns is written) from dout [B L][d] and the forward's qkv and lse:
+ * P = exp(scale q k^T - lse) and dP = dout v^T are recomputed, delta_i = sum_j P_ij dP_ij / sum_j P_ij (= dout_i . out_i in exact arithmetic; `out`
+ * itself is not read), dS = P (dP - delta), dq = scale dS k, dk = scale dS^T q, dv = P^T dout.  One launch; same limits. */
+int mlsp_mhsa_bwd_f32(const float* qkv, int ld, const float* lse, const float* dout, int B, int L, int H, int dh, float scale, float* dqkv, int ldd,
+                      mlsp_stream_t stream);
+/* u = x + sample_scale[row / rows_per_sample] * add (add NULL: u = x and `u` is not written; sample_scale NULL: 1), y = LayerNorm(u) * gamma
+ * + beta over the d channels of each of `rows` contiguous rows (biased variance), mean / rstd [rows] saved for the backward.  gamma NULL:
+ * only u is written (the residual add at a block's exit; add and u required).  sample_scale carries DropPath: mask_b / keep_prob. */
+int mlsp_layernorm_fwd_f32(const float* x, const float* add, const float* sample_scale, int rows_per_sample, const float* gamma, const float* beta,
+                           int64_t rows, int d, float eps, float* u, float* y, float* mean, float* rstd, mlsp_stream_t stream);
+/* dx = (gradient of y through the normalisation, from the saved u, mean, rstd) + du (du nullable: the gradient that reached u directly);
+ * dadd (nullable) = sample_scale * dx; dgamma / dbeta [d]: per-workgroup partials in the workspace summed in a fixed order in fp64.
+ * dy NULL is the backward of the gamma == NULL forward: dadd = sample_scale * du and nothing else is written. */
+int mlsp_layernorm_bwd_f32(const float* dy, const float* du, const float* u, const float* sample_scale, int rows_per_sample, const float* gamma,
+                           const float* mean, const float* rstd, int64_t rows, int d, float* dx, float* dadd, float* dgamma, float* dbeta,
+                           void* ws, size_t ws_bytes, mlsp_stream_t stream);
+/* y = x Phi(x), the erf form of GELU (nn.GELU()'s default), on [rows][d];  dx = dy (Phi(x) + x phi(x)) from the saved x. */
+int mlsp_gelu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t stream);
+int mlsp_gelu_bwd_f32(const float* dy, const float* x, int64_t rows, int d, float* dx, mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,12 @@ SIGNATURES = {
     "mlsp_vecattn_aggregate_bwd_f32": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "mlsp_vecattn_relu_fwd_f32": [_P, _I64, _I, _P, _P],
     "mlsp_vecattn_relu_bwd_f32": [_P, _P, _I64, _I, _P, _P],
+    "mlsp_mhsa_fwd_f32": [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P],
+    "mlsp_mhsa_bwd_f32": [_P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P],
+    "mlsp_layernorm_fwd_f32": [_P, _P, _P, _I, _P, _P, _I64, _I, _F, _P, _P, _P, _P, _P],
+    "mlsp_layernorm_bwd_f32": [_P, _P, _P, _P, _I, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_gelu_fwd_f32": [_P, _I64, _I, _P, _P],
+    "mlsp_gelu_bwd_f32": [_P, _P, _I64, _I, _P, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],

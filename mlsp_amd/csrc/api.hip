@@ -1048,4 +1048,37 @@ int mlsp_vecattn_relu_bwd_f32(const float* dy, const float* y, int64_t rows, int
     return launch_vecattn_relu_bwd(st, dy, y, rows, d, dx);
 }
 
+int mlsp_mhsa_fwd_f32(const float* qkv, int ld, int B, int L, int H, int dh, float scale, float* out, float* lse, mlsp_stream_t st) {
+    if (!qkv || !out || !lse || B <= 0 || L <= 0 || H <= 0 || dh <= 0) return MLSP_ERR_ARG;
+    return launch_mhsa_fwd(st, qkv, ld, B, L, H, dh, scale, out, lse);
+}
+int mlsp_mhsa_bwd_f32(const float* qkv, int ld, const float* lse, const float* dout, int B, int L, int H, int dh, float scale, float* dqkv, int ldd,
+                      mlsp_stream_t st) {
+    if (!qkv || !lse || !dout || !dqkv || B <= 0 || L <= 0 || H <= 0 || dh <= 0) return MLSP_ERR_ARG;
+    return launch_mhsa_bwd(st, qkv, ld, lse, dout, B, L, H, dh, scale, dqkv, ldd);
+}
+int mlsp_layernorm_fwd_f32(const float* x, const float* add, const float* sample_scale, int rows_per_sample, const float* gamma, const float* beta,
+                           int64_t rows, int d, float eps, float* u, float* y, float* mean, float* rstd, mlsp_stream_t st) {
+    if (!x || (sample_scale && !add) || (!gamma && !(add && u)) || (gamma && (!beta || !y || !mean || !rstd)) || (add && !u)) return MLSP_ERR_ARG;
+    return launch_layernorm_fwd(st, x, add, sample_scale, rows_per_sample, gamma, beta, rows, d, eps, u, y, mean, rstd);
+}
+int mlsp_layernorm_bwd_f32(const float* dy, const float* du, const float* u, const float* sample_scale, int rows_per_sample, const float* gamma,
+                           const float* mean, const float* rstd, int64_t rows, int d, float* dx, float* dadd, float* dgamma, float* dbeta,
+                           void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    if (dy ? (!u || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta) : (!du || !dadd)) return MLSP_ERR_ARG;
+    if (rows <= 0 || d <= 0 || d % 4) return MLSP_ERR_UNSUPPORTED;
+    Workspace w(ws, ws_bytes);
+    float* part = dy ? w.take<float>(layernorm_bwd_ws_floats(rows, d)) : nullptr;
+    if (!w.ok()) return MLSP_ERR_WORKSPACE;
+    return launch_layernorm_bwd(st, dy, du, u, sample_scale, rows_per_sample, gamma, mean, rstd, rows, d, dx, dadd, part, dgamma, dbeta);
+}
+int mlsp_gelu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t st) {
+    if (!x || !y) return MLSP_ERR_ARG;
+    return launch_gelu_fwd(st, x, rows, d, y);
+}
+int mlsp_gelu_bwd_f32(const float* dy, const float* x, int64_t rows, int d, float* dx, mlsp_stream_t st) {
+    if (!dy || !x || !dx) return MLSP_ERR_ARG;
+    return launch_gelu_bwd(st, dy, x, rows, d, dx);
+}
+
 }  // extern "C"

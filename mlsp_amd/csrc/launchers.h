@@ -276,3 +276,18 @@ int launch_vecattn_aggregate_bwd(hipStream_t st, const float* dres, const float*
 int launch_vecattn_relu_fwd(hipStream_t st, const float* x, long long rows, int d, float* y);
 int launch_vecattn_relu_bwd(hipStream_t st, const float* dy, const float* y, long long rows, int d, float* dx);
 
+
+// attn.hip
+int launch_mhsa_fwd(hipStream_t st, const float* qkv, int ld, int B, int L, int H, int dh, float scale, float* out, float* lse);
+int launch_mhsa_bwd(hipStream_t st, const float* qkv, int ld, const float* lse, const float* dout, int B, int L, int H, int dh, float scale,
+                    float* dqkv, int ldd);
+// a / s / gamma (with beta, y, mean, rstd) nullable: u = x + s[row / rows_per_sample] a;  gamma == NULL writes u only
+int launch_layernorm_fwd(hipStream_t st, const float* x, const float* a, const float* s, int rows_per_sample, const float* gamma, const float* beta,
+                         long long rows, int d, float eps, float* u, float* y, float* mean, float* rstd);
+size_t layernorm_bwd_ws_floats(long long rows, int d);                // floats of `part` that launch_layernorm_bwd writes
+// dy NULL: the residual add alone (da = s du; dx, part, dgamma, dbeta untouched);  du / s / dx / da nullable
+int launch_layernorm_bwd(hipStream_t st, const float* dy, const float* du, const float* u, const float* s, int rows_per_sample, const float* gamma,
+                         const float* mean, const float* rstd, long long rows, int d, float* dx, float* da, float* part, float* dgamma,
+                         float* dbeta);
+int launch_gelu_fwd(hipStream_t st, const float* x, long long rows, int d, float* y);
+int launch_gelu_bwd(hipStream_t st, const float* dy, const float* x, long long rows, int d, float* dx);

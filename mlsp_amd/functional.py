@@ -2063,6 +2063,166 @@ def vector_attention(xyz_rows, idx32, q, kk, v, delta_w1, delta_b1, delta_w2, de
     return _VaAggregate.apply(A, v, pos, eidx)
 
 
+def _attn_check(rc, what):
+    """MLSP_ERR_UNSUPPORTED of the attention / LayerNorm / GELU kernels is a MlspLibraryError: there is no other path"""
+    if rc == -3:
+        raise _lib.MlspLibraryError("%s: %s (needs channel counts %% 4 == 0 and 16-byte-aligned rows; the attention core head_dim <= 128, "
+                                    "L <= 512 and L * head_dim <= 16384)" % (what, _lib.load().mlsp_strerror(rc).decode()))
+    _lib.check(rc, what)
+
+
+class _Mhsa(Function):
+    """softmax(scale q k^T) v per (cloud, head) straight from the qkv GEMM's output (mlsp_mhsa_*_f32).  Saved for the backward: qkv and lse
+    [B,H,L] (`out` is not needed: the kernel forms delta_i from the P and dP it recomputes) -- nothing of size L^2 exists in memory in
+    either direction.  lse is returned non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, L, H, scale):
+        lib = _lib.load()
+        qkv = _rows(qkv)
+        d = qkv.shape[1] // 3
+        assert qkv.shape == (B * L, 3 * d) and d % H == 0, (qkv.shape, B, L, H)
+        out = torch.empty((B * L, d), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
+        _attn_check(lib.mlsp_mhsa_fwd_f32(qkv.data_ptr(), qkv.stride(0), B, L, H, d // H, scale, out.data_ptr(), lse.data_ptr(), _lib.stream()),
+                    "mlsp_mhsa_fwd_f32")
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (B, L, H, d // H, scale)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dlse=None):
+        lib = _lib.load()
+        qkv, lse = ctx.saved_tensors
+        B, L, H, dh, scale = ctx.dims
+        dout = dout.contiguous()
+        dqkv = torch.empty((B * L, 3 * H * dh), dtype=torch.float32, device=dout.device)
+        _attn_check(lib.mlsp_mhsa_bwd_f32(qkv.data_ptr(), qkv.stride(0), lse.data_ptr(), dout.data_ptr(), B, L, H, dh, scale,
+                                          dqkv.data_ptr(), dqkv.stride(0), _lib.stream()), "mlsp_mhsa_bwd_f32")
+        return dqkv, None, None, None, None
+
+
+def mhsa(qkv, B, L, H, scale):
+    """The attention core of PointDA/model_utils.py:234-241 on qkv [B*L, 3*d] as `Attention.qkv` leaves it (row stride >= 3*d; the q, k, v
+    of head h are the column slices at h*dh, d + h*dh, 2*d + h*dh, dh = d / H) -> (out [B*L, d] head-interleaved, lse [B,H,L]: row maximum
+    + log of the row sum of the scaled logits, non-differentiable).  One HIP launch per direction; no [L,L] array is written or read."""
+    _lib.require_gpu(qkv)
+    return _Mhsa.apply(qkv, int(B), int(L), int(H), float(scale))
+
+
+class _LayerNorm(Function):
+    """u = x + sample_scale[row // rows_per_sample] * add, y = LayerNorm(u) * weight + bias (mlsp_layernorm_*_f32).  weight None: u only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, add, sample_scale, rows_per_sample):
+        lib = _lib.load()
+        x = x.contiguous()
+        rows, d = x.shape
+        dev = x.device
+        if add is not None:
+            add = add.contiguous()
+            assert add.shape == x.shape, (add.shape, x.shape)
+        if sample_scale is not None:
+            sample_scale = sample_scale.contiguous().float()
+            assert add is not None and rows_per_sample > 0 and sample_scale.numel() * rows_per_sample == rows, (sample_scale.shape, rows_per_sample, rows)
+        u = torch.empty_like(x) if add is not None else x
+        y = mean = rstd = None
+        if weight is not None:
+            weight, bias = weight.contiguous(), bias.contiguous()
+            assert weight.shape == (d,) and bias.shape == (d,), (weight.shape, bias.shape, d)
+            y = torch.empty_like(x)
+            mean, rstd = (torch.empty((rows,), dtype=torch.float32, device=dev) for _ in range(2))
+        else:
+            assert add is not None, "layernorm without weight is the residual add: it needs `add`"
+        _attn_check(lib.mlsp_layernorm_fwd_f32(x.data_ptr(), _lib.ptr(add), _lib.ptr(sample_scale), rows_per_sample, _lib.ptr(weight), _lib.ptr(bias),
+                                               rows, d, eps, u.data_ptr() if add is not None else None, _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd),
+                                               _lib.stream()), "mlsp_layernorm_fwd_f32")
+        ctx.has_add, ctx.rps, ctx.has_ln = add is not None, rows_per_sample, weight is not None
+        if weight is not None:
+            ctx.save_for_backward(u, weight, mean, rstd, sample_scale)
+            ctx.mark_non_differentiable(mean, rstd)
+        else:
+            ctx.save_for_backward(sample_scale)
+        return u, y, mean, rstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, du, dy=None, _dmean=None, _drstd=None):
+        lib = _lib.load()
+        if ctx.has_ln:
+            u, weight, mean, rstd, s = ctx.saved_tensors
+        else:
+            s, = ctx.saved_tensors
+            u = weight = mean = rstd = None
+            dy = None
+        ref = du if du is not None else dy
+        if ref is None:
+            return (None,) * 7
+        rows, d = ref.shape
+        du = du.contiguous() if du is not None else None
+        dy = dy.contiguous() if dy is not None else None
+        want_add = ctx.has_add and ctx.needs_input_grad[4]
+        if dy is None:                                   # the residual add alone: dx is du itself
+            dx = du
+            da = du if want_add else None
+            if want_add and s is not None:
+                da = torch.empty_like(du)
+                ws, wsn = _lib.workspace(du.device, 4096, d, 4)
+                _attn_check(lib.mlsp_layernorm_bwd_f32(None, du.data_ptr(), None, s.data_ptr(), ctx.rps, None, None, None, rows, d, None,
+                                                       da.data_ptr(), None, None, ws, wsn, _lib.stream()), "mlsp_layernorm_bwd_f32")
+            return dx, None, None, None, da, None, None
+        dx = torch.empty_like(dy)
+        da = None
+        if want_add:
+            da = torch.empty_like(dy) if s is not None else dx
+        dw, db = (torch.empty((d,), dtype=torch.float32, device=dy.device) for _ in range(2))
+        ws, wsn = _lib.workspace(dy.device, 4096, d, 4)
+        _attn_check(lib.mlsp_layernorm_bwd_f32(dy.data_ptr(), _lib.ptr(du), u.data_ptr(), _lib.ptr(s) if want_add else None, ctx.rps, weight.data_ptr(),
+                                               mean.data_ptr(), rstd.data_ptr(), rows, d, dx.data_ptr(),
+                                               da.data_ptr() if (want_add and s is not None) else None, dw.data_ptr(), db.data_ptr(), ws, wsn,
+                                               _lib.stream()), "mlsp_layernorm_bwd_f32")
+        return dx, dw, db, None, da, None, None
+
+
+def layernorm(x, weight, bias, eps, add=None, sample_scale=None, rows_per_sample=0):
+    """x [rows, d] -> (u, y, mean, rstd): u = x + sample_scale[row // rows_per_sample] * add (the residual stream; x itself without `add`),
+    y = LayerNorm(u) * weight + bias with nn.LayerNorm's biased variance, mean / rstd [rows] (non-differentiable).  `sample_scale` [rows /
+    rows_per_sample] carries DropPath (mask / keep_prob).  weight None: the residual add alone -> (u, None, None, None).  One HIP launch."""
+    _lib.require_gpu(x, weight, bias, add, sample_scale)
+    return _LayerNorm.apply(x, weight, bias, float(eps), add, sample_scale, int(rows_per_sample))
+
+
+class _Gelu(Function):
+    """y = x Phi(x), the erf form (mlsp_gelu_*_f32: pointmlp activates only behind a BatchNorm)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        _attn_check(lib.mlsp_gelu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()), "mlsp_gelu_fwd_f32")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        _attn_check(lib.mlsp_gelu_bwd_f32(dy.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1], dx.data_ptr(), _lib.stream()), "mlsp_gelu_bwd_f32")
+        return dx
+
+
+def gelu(x):
+    """nn.GELU()'s default (erf) form on [rows, d] float32"""
+    _lib.require_gpu(x)
+    return _Gelu.apply(x)
+
+
 def gemm(A, B, ta=False, tb=False, bias=None):
     """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests."""
     lib = _lib.load()

@@ -303,3 +303,7 @@ class density_classifier(nn.Module):
         x = self.mlp1(x, p_drop=self.dp1.p)
         x2 = self.mlp2(x, p_drop=self.dp2.p)
         return Fh.pointmlp(x2, self.mlp3.weight, bias=self.mlp3.bias, training=self.training)
+
+
+# model_utils.py:201-289: the Point-BERT transformer encoder (mlsp_amd/vit.py)
+from .vit import Mlp, Attention, Block, TransformerEncoder   # noqa: E402,F401
