@@ -579,6 +579,34 @@ int mlsp_layernorm_bwd_f32(const float* dy, const float* du, const float* u, con
 int mlsp_gelu_fwd_f32(const float* x, int64_t rows, int d, float* y, mlsp_stream_t stream);
 int mlsp_gelu_bwd_f32(const float* dy, const float* x, int64_t rows, int d, float* dx, mlsp_stream_t stream);
 
+/* The edge stage of DGCNN_Propagation (PointDA/Models.py:327-363: get_graph_feature, layer1 / layer2 = Conv2d(1x1, no bias) + GroupNorm +
+ * LeakyReLU, max over the k neighbours) behind its FOLDED convolution.  With the conv weight W = [Wa | Wb] over the edge input
+ * [f_j - f_i ; f_i] (:347) the pre-norm value of edge (i, s) is y(i, s, c) = u[j][c] + w[i][c], j = idx[i][s]: u [B*Nk][C] = f_k Wa^T per
+ * source point (row pitch ldu), w [B*Nq][C] = f_q (Wb - Wa)^T per query point (row pitch ldw) -- two per-point GEMMs the caller runs
+ * (mlsp_pointmlp_fwd_f32).  idx [B][Nq][k] int32, local to the cloud, as mlsp_knn_query_f32 returns it (an index outside [0, Nk) is read
+ * as 0; an entry may repeat inside a row).  Never materialised, in either direction: the [B][2 Cin][Nq][k] edge tensor, the [B][C][Nq][k]
+ * conv output, its normalised / activated copies and their gradients.
+ * fwd: stats [B][groups][2] = mean and 1 / sqrt(biased variance + eps) of y over the (C / groups) Nq k values of a (cloud, group) (fp64
+ * sums, per-workgroup partials in the workspace added in ascending order);  out [B*Nq][C] = max_s lrelu((y - mean) rstd gamma[c] + beta[c]);
+ * argk [B*Nq][C] uint8 = the slot that attains it: the first maximum of y where gamma[c] rstd >= 0, the first minimum otherwise -- in [0, k)
+ * for every input (a NaN in y makes the group's statistics, hence its outputs, NaN).
+ * bwd: from dOut [B*Nq][C] and the saved u, w, idx, argk, stats and the reverse index of idx (mlsp_group_reverse(idx, B, Nq, Nk, k, ...)):
+ * dz = dOut lrelu'(.) at the selected slot, dy(i, s, c) = rstd (gamma[c] dz [s == argk] - A - yhat(i, s, c) Bm) with A / Bm the group means
+ * of gamma dz / gamma dz yhat;  dw [B*Nq][C] = sum_s dy (ascending s), du [B*Nk][C] = sum of dy over the edges that name the row
+ * (reverse-index order; exactly 0 for a row no edge names), dgamma / dbeta [C] = sum dz yhat_sel / sum dz (fp32 per-workgroup partials,
+ * added in fp64 in ascending order).  No atomics.
+ * Limits: C % (4 groups) == 0, groups <= 256, 1 <= k <= 64, Nk, Nq <= 2^22, 16-byte-aligned pointers and row pitches (ldu, ldw % 4 == 0)
+ * -- anything else returns MLSP_ERR_UNSUPPORTED and launches nothing.  No entry reaches a matrix core.
+ * ws: at least mlsp_gn_edge_workspace_bytes(...) bytes (0 for a shape outside the limits). */
+size_t mlsp_gn_edge_workspace_bytes(int B, int Nk, int Nq, int k, int C, int groups);
+int mlsp_gn_edge_fwd_f32(const float* u, int ldu, const float* w, int ldw, const int32_t* idx, const float* gamma, const float* beta, int B, int Nk,
+                         int Nq, int k, int C, int groups, float eps, float slope, float* out, uint8_t* argk, float* stats, void* ws,
+                         size_t ws_bytes, mlsp_stream_t stream);
+int mlsp_gn_edge_bwd_f32(const float* dOut, const float* u, int ldu, const float* w, int ldw, const int32_t* idx, const uint8_t* argk,
+                         const float* stats, const int32_t* rev_off, const int32_t* rev_ent, const float* gamma, const float* beta, int B, int Nk,
+                         int Nq, int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, void* ws,
+                         size_t ws_bytes, mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

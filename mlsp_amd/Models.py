@@ -429,3 +429,6 @@ class DGCNN(nn.Module):
             else:
                 logits[key] = head.rows(xa, x5, B, N, grad_accum=acc)
         return logits
+
+
+from .propagation import DGCNN_Propagation  # noqa: E402,F401  (PointDA/Models.py:289)

@@ -92,6 +92,9 @@ SIGNATURES = {
     "mlsp_layernorm_bwd_f32": [_P, _P, _P, _P, _I, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _SZ, _P],
     "mlsp_gelu_fwd_f32": [_P, _I64, _I, _P, _P],
     "mlsp_gelu_bwd_f32": [_P, _P, _I64, _I, _P, _P],
+    "mlsp_gn_edge_workspace_bytes": [_I, _I, _I, _I, _I, _I],
+    "mlsp_gn_edge_fwd_f32": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_gn_edge_bwd_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -163,7 +166,7 @@ class Defer(_c.Structure):
     _fields_ = [("bn_save", _P), ("ld", _I), ("col", _I), ("act", _I), ("slope", _F), ("p_drop", _F), ("seed", _U64)]
 
 
-_RESTYPE = {"mlsp_strerror": _c.c_char_p, "mlsp_workspace_bytes": _SZ}
+_RESTYPE = {"mlsp_strerror": _c.c_char_p, "mlsp_workspace_bytes": _SZ, "mlsp_gn_edge_workspace_bytes": _SZ}
 
 _lib = None
 
@@ -262,6 +265,11 @@ def workspace(device, rows, cin, cout):
     need = _ws_need.get(shape)
     if need is None:
         need = _ws_need[shape] = load().mlsp_workspace_bytes(*shape)
+    return workspace_of(device, need)
+
+
+def workspace_of(device, need):
+    """(pointer, bytes) of this (device, stream)'s scratch buffer, grown to `need` bytes (an entry point's own size query)"""
     key = (device.index if device.index is not None else torch._C._cuda_getDevice(), stream())
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < need:

@@ -1081,4 +1081,25 @@ int mlsp_gelu_bwd_f32(const float* dy, const float* x, int64_t rows, int d, floa
     return launch_gelu_bwd(st, dy, x, rows, d, dx);
 }
 
+size_t mlsp_gn_edge_workspace_bytes(int B, int Nk, int Nq, int k, int C, int groups) { return gn_edge_ws_bytes(B, Nk, Nq, k, C, groups); }
+int mlsp_gn_edge_fwd_f32(const float* u, int ldu, const float* w, int ldw, const int32_t* idx, const float* gamma, const float* beta, int B, int Nk,
+                         int Nq, int k, int C, int groups, float eps, float slope, float* out, uint8_t* argk, float* stats, void* ws,
+                         size_t ws_bytes, mlsp_stream_t st) {
+    if (!u || !w || !idx || !gamma || !beta || !out || !argk || !stats || B <= 0 || Nk <= 0 || Nq <= 0 || k <= 0 || C <= 0 || groups <= 0)
+        return MLSP_ERR_ARG;
+    Workspace wsp(ws, ws_bytes);
+    return launch_gn_edge_fwd(st, u, ldu, w, ldw, idx, gamma, beta, B, Nk, Nq, k, C, groups, eps, slope, out, argk, stats, wsp);
+}
+int mlsp_gn_edge_bwd_f32(const float* dOut, const float* u, int ldu, const float* w, int ldw, const int32_t* idx, const uint8_t* argk,
+                         const float* stats, const int32_t* rev_off, const int32_t* rev_ent, const float* gamma, const float* beta, int B, int Nk,
+                         int Nq, int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, void* ws,
+                         size_t ws_bytes, mlsp_stream_t st) {
+    if (!dOut || !u || !w || !idx || !argk || !stats || !rev_off || !rev_ent || !gamma || !beta || !du || !dw || !dgamma || !dbeta || B <= 0 ||
+        Nk <= 0 || Nq <= 0 || k <= 0 || C <= 0 || groups <= 0)
+        return MLSP_ERR_ARG;
+    Workspace wsp(ws, ws_bytes);
+    return launch_gn_edge_bwd(st, dOut, u, ldu, w, ldw, idx, argk, stats, rev_off, rev_ent, gamma, beta, B, Nk, Nq, k, C, groups, slope, du, dw,
+                              dgamma, dbeta, wsp);
+}
+
 }  // extern "C"

@@ -291,3 +291,12 @@ int launch_layernorm_bwd(hipStream_t st, const float* dy, const float* du, const
                          float* dbeta);
 int launch_gelu_fwd(hipStream_t st, const float* x, long long rows, int d, float* y);
 int launch_gelu_bwd(hipStream_t st, const float* dy, const float* x, long long rows, int d, float* dx);
+
+// gnedge.hip
+size_t gn_edge_ws_bytes(int B, int Nk, int Nq, int k, int C, int groups);   // what the two launchers below take from `ws` (0: shape outside the limits)
+int launch_gn_edge_fwd(hipStream_t st, const float* u, int ldu, const float* w, int ldw, const int* idx, const float* gamma, const float* beta,
+                       int B, int Nk, int Nq, int k, int C, int groups, float eps, float slope, float* out, uint8_t* argk, float* stats,
+                       Workspace& ws);
+int launch_gn_edge_bwd(hipStream_t st, const float* dOut, const float* u, int ldu, const float* w, int ldw, const int* idx, const uint8_t* argk,
+                       const float* stats, const int* rev_off, const int* rev_ent, const float* gamma, const float* beta, int B, int Nk, int Nq,
+                       int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, Workspace& ws);

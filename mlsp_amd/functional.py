@@ -2063,6 +2063,80 @@ def vector_attention(xyz_rows, idx32, q, kk, v, delta_w1, delta_b1, delta_w2, de
     return _VaAggregate.apply(A, v, pos, eidx)
 
 
+def _gn_check(rc, what):
+    """MLSP_ERR_UNSUPPORTED of the GroupNorm edge kernels is a MlspLibraryError: there is no other path"""
+    if rc == -3:
+        raise _lib.MlspLibraryError("%s: %s (needs C %% (4 groups) == 0, 1 <= k <= 64, 16-byte-aligned rows)"
+                                    % (what, _lib.load().mlsp_strerror(rc).decode()))
+    _lib.check(rc, what)
+
+
+class _GnEdgeMax(Function):
+    """out[i] = max_s lrelu(GroupNorm(u[idx[i][s]] + w[i]))  (mlsp_gn_edge_*_f32): the edge tensor and its gradient are never materialised.
+    `rev`: an empty list that the first backward fills with the reverse index of idx32 (as _EdgeIndex does)."""
+
+    @staticmethod
+    def forward(ctx, u, w, idx32, gamma, beta, groups, eps, slope, rev):
+        lib = _lib.load()
+        u, w = _rows(u), _rows(w)
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        B, Nq, k = idx32.shape
+        C = u.shape[1]
+        Nk = u.shape[0] // B
+        assert u.shape[0] == B * Nk and w.shape == (B * Nq, C) and gamma.shape == (C,) and beta.shape == (C,), (u.shape, w.shape, idx32.shape)
+        dev = u.device
+        out = torch.empty((B * Nq, C), dtype=torch.float32, device=dev)
+        argk = torch.empty((B * Nq, C), dtype=torch.uint8, device=dev)
+        stats = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
+        ws, wsn = _lib.workspace_of(dev, lib.mlsp_gn_edge_workspace_bytes(B, Nk, Nq, k, C, groups))
+        _gn_check(lib.mlsp_gn_edge_fwd_f32(u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(), gamma.data_ptr(),
+                                           beta.data_ptr(), B, Nk, Nq, k, C, groups, eps, slope, out.data_ptr(), argk.data_ptr(),
+                                           stats.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_fwd_f32")
+        if _sel_record is not None or _sel_forced is not None:
+            _selection_hook(argk)              # test hooks: the slot the backward routes each entry's gradient to (it reads nothing else of the choice)
+        ctx.save_for_backward(u, w, idx32, gamma, beta, argk, stats)
+        ctx.cfg = (int(groups), float(slope), rev)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dOut):
+        lib = _lib.load()
+        u, w, idx32, gamma, beta, argk, stats = ctx.saved_tensors
+        groups, slope, rev = ctx.cfg
+        B, Nq, k = idx32.shape
+        C = u.shape[1]
+        Nk = u.shape[0] // B
+        dev = dOut.device
+        dOut = dOut.contiguous()
+        if not rev:
+            rev_off = torch.empty((B * Nk + 1,), dtype=torch.int32, device=dev)
+            rev_ent = torch.empty((B * Nq * k,), dtype=torch.int32, device=dev)
+            _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, Nq, Nk, k, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
+                       "mlsp_group_reverse")
+            rev.append((rev_off, rev_ent))
+        rev_off, rev_ent = rev[0]
+        du = torch.empty((B * Nk, C), dtype=torch.float32, device=dev)
+        dw = torch.empty((B * Nq, C), dtype=torch.float32, device=dev)
+        dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2))
+        ws, wsn = _lib.workspace_of(dev, lib.mlsp_gn_edge_workspace_bytes(B, Nk, Nq, k, C, groups))
+        _gn_check(lib.mlsp_gn_edge_bwd_f32(dOut.data_ptr(), u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(),
+                                           argk.data_ptr(), stats.data_ptr(), rev_off.data_ptr(), rev_ent.data_ptr(), gamma.data_ptr(),
+                                           beta.data_ptr(), B, Nk, Nq, k, C, groups, slope, du.data_ptr(), dw.data_ptr(), dgamma.data_ptr(),
+                                           dbeta.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_bwd_f32")
+        return du, dw, None, dgamma, dbeta, None, None, None, None
+
+
+def gn_edge_max(u, w, idx32, gamma, beta, groups, eps=1e-5, slope=0.2):
+    """The edge stage of DGCNN_Propagation behind its folded conv (PointDA/Models.py:355-357): u [B*Nk, C] per source point, w [B*Nq, C]
+    per query point, idx32 [B, Nq, k] int32 local to the cloud ->  max over the k slots of LeakyReLU(GroupNorm(groups)(u[idx] + w)),
+    [B*Nq, C].  Gradients to u, w, gamma, beta (none to idx).  C % (4 groups) == 0 and 1 <= k <= 64, or MlspLibraryError.  The first
+    backward of a call builds the reverse index of idx (mlsp_group_reverse) and keeps it for the next."""
+    _lib.require_gpu(u, w, idx32, gamma, beta)
+    assert idx32.dtype == torch.int32 and idx32.dim() == 3, (idx32.dtype, idx32.shape)
+    return _GnEdgeMax.apply(u, w, idx32.contiguous(), gamma, beta, int(groups), float(eps), float(slope), [])
+
+
 def _attn_check(rc, what):
     """MLSP_ERR_UNSUPPORTED of the attention / LayerNorm / GELU kernels is a MlspLibraryError: there is no other path"""
     if rc == -3:
