@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 import golden_common as gc
 from oracle import knn_canon, ref_cpu, ref_torch_modules
+from tnet_restatement import tnet_edge_f64 as _tnet_edge_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -1256,18 +1257,6 @@ def test_tnet_edge_bf16_operands_vs_fp32_products(dev, B, N, k):
         assert rel < 1e-2, (name, rel)
         if name == "dW2":
             assert rel > 1e-5, (name, rel)
-
-
-def _tnet_edge_f64(xp, idx, W1, g1, b1, W2, g2, b2, slope, sel=None):
-    """The T-Net per-edge stage through the reference's op sequence (oracle/ref_torch_modules.py: edge features, then 1x1 Conv2d +
-    BatchNorm2d on batch statistics + LeakyReLU twice, max over k), in the precision of its arguments: xp [P, C], idx [B, N, k] -> [P, 128].
-    sel [P, 128] (optional): the slot each max takes, instead of the arg-max of its own values."""
-    B, N, k = idx.shape
-    h = ref_torch_modules.edge_features(xp.view(B, N, -1).transpose(2, 1), k, lambda *_: idx)
-    for W, g, b in ((W1, g1, b1), (W2, g2, b2)):
-        h = F.leaky_relu(F.batch_norm(F.conv2d(h, W[:, :, None, None]), None, None, g, b, True, 0.1, 1e-5), slope)
-    z = h.max(dim=-1)[0] if sel is None else h.gather(-1, sel.long().view(B, N, -1).transpose(2, 1)[..., None])[..., 0]
-    return z.transpose(2, 1).reshape(B * N, -1)
 
 
 @pytest.mark.parametrize("B,N,k", [(8, 512, 20), (4, 512, 40)])
