@@ -369,7 +369,11 @@ int mlsp_knn_normals_f32(const float* x, int ldx, const int32_t* idx, int B, int
 /* kNN of query points among DIFFERENT reference points: `square_distance` + argsort()[:, :, :k] (pointnet_util.py:26-38,116-118 knn=True
  * grouping, :237-239 Msg, :287-289 the 3-NN of feature propagation; the KNN calls of PointDA/model_utils.py:175,188 have this shape).
  * d = (-2 q.r + |q|^2) + |r|^2 in fp32 (dot = fmaf chain over the C <= 8 coordinates), ascending, ties -> lower reference index.
- * ref [B][Nr] rows (pitch ldr), qry [B][Nq] rows (pitch ldq) -> idx [B][Nq][k] (local to the cloud), dist [B][Nq][k] (nullable). k <= 64. */
+ * ref [B][Nr] rows (pitch ldr), qry [B][Nq] rows (pitch ldq) -> idx [B][Nq][k] (local to the cloud), dist [B][Nq][k] (nullable). k <= 64.
+ * Index contract: every returned index lies in [0, Nr), whatever the coordinates hold (k <= Nr is required).  A distance that is not
+ * finite (a NaN coordinate in the query or the reference, a squared norm that overflows) counts as +inf; +inf candidates fill the slots
+ * that no finite candidate took, lowest reference index first, and dist reports +inf for them.  The consumers of idx gather without a
+ * range check. */
 int mlsp_knn_query_f32(const float* ref, int ldr, int Nr, const float* qry, int ldq, int Nq, int B, int C, int k, int32_t* idx, float* dist,
                        mlsp_stream_t stream);
 /* PointNetFeaturePropagation interpolation (pointnet_util.py:287-294): out [B][N][D] = inverse-distance weighted mean of the features
@@ -422,7 +426,9 @@ int mlsp_sa_fold_bwd_f32(const float* dZ, const float* u, const float* w, const 
 /* Reverse index of padded groups WITHOUT their padding slots (ball-query groups repeat their first hit: slot s > 0 with idx[i][s] ==
  * idx[i][0]): rev_off [B*N+1] list starts, rev_cnt [B*N] list lengths (the lists of a cloud no longer fill its S*ns entries), rev_ent as
  * mlsp_group_reverse, pad_cnt [B*S] padding slots per group.  mlsp_sa_fold_bwd_f32 takes rev_cnt / pad_cnt (both or neither, NULL = the
- * full index of mlsp_group_reverse) and adds a group's identical padding rows as a multiple of one row. */
+ * full index of mlsp_group_reverse) and adds a group's identical padding rows as a multiple of one row.  The compact form rests on a
+ * premise the caller must meet: every padding row of a group carries the same dZ as the group's LAST slot (the row that is read for all
+ * of them), as it does behind the layer's own forward; for any other dZ pass the full index. */
 int mlsp_group_reverse_compact(const int32_t* idx, int B, int S, int N, int ns, int32_t* rev_off, int32_t* rev_cnt, int32_t* rev_ent,
                                int32_t* pad_cnt, mlsp_stream_t stream);
 

@@ -5,6 +5,7 @@
 // contraction), same tie rule (first index), same "first nsample in index order, padded with the first" selection.
 // The SA-MLP behind the grouping is the existing Linear+BN+act kernel family over the B*S*nsample edge rows.
 #include "common.h"
+#include <cfloat>
 
 // ---- FPS: one workgroup per cloud, the cloud in LDS, running distances in registers.
 // out[b][i] = index of the i-th sample; sample 0 is start[b].  N <= 8 * 1024.
@@ -297,17 +298,23 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float* __restrict_
             for (int c = 0; c < 8; ++c)
                 if (c < C) dot = fmaf(qv[c], rs[j * 8 + c], dot);
             const float d = (-2.f * dot + qn) + rn[j];
-            if (d < bv[KMAX - 1]) {                                     // strict: an equal distance with a higher index stays out
-                const int jj = r0 + j;
+            const int jj = r0 + j;
+            // strict: an equal distance with a higher index stays out.  The first KMAX references (a uniform test) enter whatever their
+            // distance: a NaN or overflowed distance counts as +inf -- held as FLT_MAX in the list, below the INFINITY of a slot that is
+            // still empty -- and takes such a slot, lowest index first, so with Nr >= k no empty slot (index 0x7fffffff) is ever written
+            // out: the gathers downstream do not range-check.  Once KMAX references have passed, every slot is taken and such a candidate
+            // (a higher index than any it ties with) stays out.
+            if (d < bv[KMAX - 1] || jj < KMAX) {
+                const float dd = fabsf(d) < INFINITY ? d : FLT_MAX;
 #pragma unroll
                 for (int s = KMAX - 1; s >= 1; --s) {
-                    const bool up = d < bv[s - 1];
-                    const bool here = d < bv[s];
-                    const float nv = up ? bv[s - 1] : (here ? d : bv[s]);
+                    const bool up = dd < bv[s - 1];
+                    const bool here = dd < bv[s];
+                    const float nv = up ? bv[s - 1] : (here ? dd : bv[s]);
                     const int ni = up ? bi[s - 1] : (here ? jj : bi[s]);
                     bv[s] = nv; bi[s] = ni;
                 }
-                if (d < bv[0]) { bv[0] = d; bi[0] = jj; }
+                if (dd < bv[0]) { bv[0] = dd; bi[0] = jj; }
             }
         }
     }
@@ -316,7 +323,7 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float* __restrict_
         for (int s = 0; s < KMAX; ++s)
             if (s < k) {
                 idx[((size_t)b * Nq + q) * k + s] = bi[s];
-                if (dist) dist[((size_t)b * Nq + q) * k + s] = bv[s];
+                if (dist) dist[((size_t)b * Nq + q) * k + s] = bv[s] < FLT_MAX ? bv[s] : INFINITY;     // (non-finite distances: +inf)
             }
     }
 }
