@@ -613,6 +613,33 @@ int mlsp_gn_edge_bwd_f32(const float* dOut, const float* u, int ldu, const float
                          int Nq, int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, void* ws,
                          size_t ws_bytes, mlsp_stream_t stream);
 
+/* The two stages of the Point-BERT PointTransformer (PointDA/Models.py:365-531) that the GEMM family serves badly (token.hip).  fp32; no
+ * atomics: results are bit-identical run to run; anything outside the limits returns MLSP_ERR_UNSUPPORTED and launches nothing.
+ *
+ * Thin-input layer: H [M][C] = act(BN?(X W^T + b)), X [M][Cin] (row pitch ldx >= Cin, Cin <= 8), W [C][Cin] contiguous, C % 4 == 0,
+ * C <= 4096, act in {0 none, 1 relu, 3 gelu (erf form)}; H and every per-channel vector 16-byte aligned.  bias nullable.
+ * gamma == NULL (then beta == NULL): no BatchNorm.  Otherwise training != 0 normalises with the batch statistics, which come from the
+ * input's first and second moments (mean_c = w_c mu + b_c, var_c = w_c^T Sigma w_c; fp64 sums, fixed order) -- no pre-BN tensor exists;
+ * M < 2 is MLSP_ERR_ARG.  xmom [72] doubles = mu[8] | Sigma[8][8] is written for the backward; run_mean / run_var (nullable) are updated
+ * as torch does (unbiased variance, `momentum`).  training == 0 normalises with run_mean / run_var (required).  bn_save [4][C] = scale |
+ * shift | mean | invstd is written in both BatchNorm modes.  ws: at least mlsp_thin_in_workspace_bytes(M, Cin, C) bytes.
+ * Backward (same arguments as the forward saw; y is recomputed from X, H is not read): dW [C][Cin]; db [C] (nullable; exactly 0 in training
+ * with BatchNorm); dgamma, dbeta [C] with BatchNorm.  There is no gradient for X. */
+size_t mlsp_thin_in_workspace_bytes(int M, int Cin, int C);
+int mlsp_thin_in_fwd_f32(const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma, const float* beta,
+                         float* run_mean, float* run_var, float momentum, float eps, int training, int act, float* H, float* bn_save, double* xmom,
+                         void* ws, size_t ws_bytes, mlsp_stream_t stream);
+int mlsp_thin_in_bwd_f32(const float* dH, const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma,
+                         const float* beta, const float* bn_save, const double* xmom, int training, int act, float* dW, float* db, float* dgamma,
+                         float* dbeta, void* ws, size_t ws_bytes, mlsp_stream_t stream);
+
+/* Token pooling (Models.py:498 cat([x[:,0], x[:,1:].max(1)[0]])): y [B L][d] -> out [B][2 d] = y[b L] | max over the rows 1 .. L-1 of cloud b,
+ * arg [B][d] = the row of that maximum, local to the cloud.  Strict comparison: the lowest row wins ties.  arg is always in [1, L): a NaN
+ * never displaces a number, and an all-NaN column takes row 1 and reports NaN.  L >= 2, d % 4 == 0, 16-byte-aligned pointers.
+ * Backward: dy [B L][d] is written completely (row 0 = the first half of dOut, row arg = the second half, 0 elsewhere). */
+int mlsp_token_pool_fwd_f32(const float* y, int B, int L, int d, float* out, int32_t* arg, mlsp_stream_t stream);
+int mlsp_token_pool_bwd_f32(const float* dOut, const int32_t* arg, int B, int L, int d, float* dy, mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -432,3 +432,4 @@ class DGCNN(nn.Module):
 
 
 from .propagation import DGCNN_Propagation  # noqa: E402,F401  (PointDA/Models.py:289)
+from .pointbert import PointTransformer, fps  # noqa: E402,F401  (PointDA/Models.py:16, :365)

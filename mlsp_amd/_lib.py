@@ -95,6 +95,11 @@ SIGNATURES = {
     "mlsp_gn_edge_workspace_bytes": [_I, _I, _I, _I, _I, _I],
     "mlsp_gn_edge_fwd_f32": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _SZ, _P],
     "mlsp_gn_edge_bwd_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_thin_in_workspace_bytes": [_I, _I, _I],
+    "mlsp_thin_in_fwd_f32": [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_thin_in_bwd_f32": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_token_pool_fwd_f32": [_P, _I, _I, _I, _P, _P, _P],
+    "mlsp_token_pool_bwd_f32": [_P, _P, _I, _I, _I, _P, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -166,7 +171,8 @@ class Defer(_c.Structure):
     _fields_ = [("bn_save", _P), ("ld", _I), ("col", _I), ("act", _I), ("slope", _F), ("p_drop", _F), ("seed", _U64)]
 
 
-_RESTYPE = {"mlsp_strerror": _c.c_char_p, "mlsp_workspace_bytes": _SZ, "mlsp_gn_edge_workspace_bytes": _SZ}
+_RESTYPE = {"mlsp_strerror": _c.c_char_p, "mlsp_workspace_bytes": _SZ, "mlsp_gn_edge_workspace_bytes": _SZ,
+            "mlsp_thin_in_workspace_bytes": _SZ}
 
 _lib = None
 

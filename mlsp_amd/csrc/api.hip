@@ -1102,4 +1102,34 @@ int mlsp_gn_edge_bwd_f32(const float* dOut, const float* u, int ldu, const float
                               dgamma, dbeta, wsp);
 }
 
+size_t mlsp_thin_in_workspace_bytes(int M, int Cin, int C) { return thin_in_ws_bytes(M, Cin, C); }
+int mlsp_thin_in_fwd_f32(const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma, const float* beta,
+                         float* run_mean, float* run_var, float momentum, float eps, int training, int act, float* H, float* bn_save, double* xmom,
+                         void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    const bool bn = gamma != nullptr;
+    if (!X || !W || !H || (bn && (!beta || !bn_save)) || (!bn && beta) || M <= 0 || Cin <= 0 || C <= 0) return MLSP_ERR_ARG;
+    if (bn && training && (M < 2 || !xmom)) return MLSP_ERR_ARG;              // (torch refuses one value per channel too)
+    if (bn && !training && (!run_mean || !run_var)) return MLSP_ERR_ARG;
+    Workspace wsp(ws, ws_bytes);
+    return launch_thin_in_fwd(st, X, ldx, M, Cin, W, bias, C, gamma, beta, run_mean, run_var, momentum, eps, training, act, H, bn_save, xmom, wsp);
+}
+int mlsp_thin_in_bwd_f32(const float* dH, const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma,
+                         const float* beta, const float* bn_save, const double* xmom, int training, int act, float* dW, float* db, float* dgamma,
+                         float* dbeta, void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    const bool bn = gamma != nullptr;
+    if (!dH || !X || !W || !dW || (bn && (!beta || !bn_save || !dgamma || !dbeta)) || (!bn && beta) || M <= 0 || Cin <= 0 || C <= 0)
+        return MLSP_ERR_ARG;
+    if (bn && training && (M < 2 || !xmom)) return MLSP_ERR_ARG;
+    Workspace wsp(ws, ws_bytes);
+    return launch_thin_in_bwd(st, dH, X, ldx, M, Cin, W, bias, C, gamma, beta, bn_save, xmom, training, act, dW, db, dgamma, dbeta, wsp);
+}
+int mlsp_token_pool_fwd_f32(const float* y, int B, int L, int d, float* out, int32_t* arg, mlsp_stream_t st) {
+    if (!y || !out || !arg || B <= 0 || L <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_token_pool_fwd(st, y, B, L, d, out, arg);
+}
+int mlsp_token_pool_bwd_f32(const float* dOut, const int32_t* arg, int B, int L, int d, float* dy, mlsp_stream_t st) {
+    if (!dOut || !arg || !dy || B <= 0 || L <= 0 || d <= 0) return MLSP_ERR_ARG;
+    return launch_token_pool_bwd(st, dOut, arg, B, L, d, dy);
+}
+
 }  // extern "C"

@@ -300,3 +300,15 @@ int launch_gn_edge_fwd(hipStream_t st, const float* u, int ldu, const float* w, 
 int launch_gn_edge_bwd(hipStream_t st, const float* dOut, const float* u, int ldu, const float* w, int ldw, const int* idx, const uint8_t* argk,
                        const float* stats, const int* rev_off, const int* rev_ent, const float* gamma, const float* beta, int B, int Nk, int Nq,
                        int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, Workspace& ws);
+
+// token.hip
+size_t thin_in_ws_bytes(int M, int Cin, int C);                             // what the two launchers below take from `ws` (0: shape outside the limits)
+// gamma / beta NULL: no BatchNorm;  bias / run_mean / run_var nullable;  xmom [72] doubles (mu | Sigma) is written in training with BatchNorm
+int launch_thin_in_fwd(hipStream_t st, const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma,
+                       const float* beta, float* run_mean, float* run_var, float momentum, float eps, int training, int act, float* H,
+                       float* bn_save, double* xmom, Workspace& ws);
+int launch_thin_in_bwd(hipStream_t st, const float* dH, const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C,
+                       const float* gamma, const float* beta, const float* bn_save, const double* xmom, int training, int act, float* dW,
+                       float* db, float* dgamma, float* dbeta, Workspace& ws);
+int launch_token_pool_fwd(hipStream_t st, const float* y, int B, int L, int d, float* out, int* arg);
+int launch_token_pool_bwd(hipStream_t st, const float* dOut, const int* arg, int B, int L, int d, float* dy);

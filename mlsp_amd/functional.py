@@ -14,6 +14,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
+ACT_GELU = 3             # thin_in only: pointmlp activates behind a BatchNorm with relu / leaky relu
 _seed_counter = itertools.count(1)
 
 
@@ -1343,6 +1344,8 @@ class _SegMax(Function):
         argk = torch.empty((P, C), dtype=torch.uint8, device=Z.device)
         _lib.check(lib.mlsp_segmax_fwd_f32(Z.data_ptr(), P, k, C, out.data_ptr(), argk.data_ptr(), _lib.stream()),
                    "mlsp_segmax_fwd_f32")
+        if _sel_record is not None or _sel_forced is not None:
+            _selection_hook(argk)              # test hooks: the slot the backward routes each entry's gradient to
         ctx.save_for_backward(argk)
         ctx.k = k
         return out
@@ -2295,6 +2298,111 @@ def gelu(x):
     """nn.GELU()'s default (erf) form on [rows, d] float32"""
     _lib.require_gpu(x)
     return _Gelu.apply(x)
+
+
+def _token_check(rc, what):
+    """MLSP_ERR_UNSUPPORTED and MLSP_ERR_ARG of the token kernels are a MlspLibraryError: there is no other path"""
+    if rc in (-1, -3):
+        raise _lib.MlspLibraryError("%s: %s (thin_in needs Cin <= 8, C %% 4 == 0, C <= 4096 and at least 2 rows in training with BatchNorm; "
+                                    "token_pool needs L >= 2 and d %% 4 == 0)" % (what, _lib.load().mlsp_strerror(rc).decode()))
+    _lib.check(rc, what)
+
+
+class _ThinIn(Function):
+    """H = act(BN?(X W^T + b)) for X [M, Cin <= 8] (mlsp_thin_in_*_f32).  Saved for the backward: X, W, bias, gamma, beta, bn_save [4, C] and
+    xmom [72] float64 (the input's mean and covariance) -- no pre-BN tensor exists and H is not kept."""
+
+    @staticmethod
+    def forward(ctx, X, W, bias, gamma, beta, run_mean, run_var, training, act, momentum, eps):
+        lib = _lib.load()
+        if X.dim() != 2 or X.stride(1) != 1:
+            X = X.contiguous()
+        W = W.contiguous()
+        M, Cin = X.shape
+        C = W.shape[0]
+        assert W.shape == (C, Cin), (W.shape, X.shape)
+        dev = X.device
+        bn = gamma is not None
+        H = torch.empty((M, C), dtype=torch.float32, device=dev)
+        bn_save = torch.empty((4, C), dtype=torch.float32, device=dev) if bn else None
+        xmom = torch.empty((72,), dtype=torch.float64, device=dev) if bn and training else None
+        ws, wsn = _lib.workspace_of(dev, lib.mlsp_thin_in_workspace_bytes(M, Cin, C))
+        _token_check(lib.mlsp_thin_in_fwd_f32(X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma), _lib.ptr(beta),
+                                              _lib.ptr(run_mean), _lib.ptr(run_var), float(momentum), float(eps), int(training), int(act),
+                                              H.data_ptr(), _lib.ptr(bn_save), _lib.ptr(xmom), ws, wsn, _lib.stream()), "mlsp_thin_in_fwd_f32")
+        ctx.save_for_backward(X, W, bias, gamma, beta, bn_save, xmom)
+        ctx.cfg = (bool(training), int(act))
+        if bn:
+            ctx.mark_non_differentiable(bn_save)
+        return H, bn_save
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dH, _dsave=None):
+        lib = _lib.load()
+        X, W, bias, gamma, beta, bn_save, xmom = ctx.saved_tensors
+        training, act = ctx.cfg
+        dH = dH.contiguous()
+        M, Cin = X.shape
+        C = W.shape[0]
+        dev = dH.device
+        bn = gamma is not None
+        dW = torch.empty((C, Cin), dtype=torch.float32, device=dev)
+        db = torch.empty((C,), dtype=torch.float32, device=dev) if bias is not None else None
+        dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2)) if bn else (None, None)
+        ws, wsn = _lib.workspace_of(dev, lib.mlsp_thin_in_workspace_bytes(M, Cin, C))
+        _token_check(lib.mlsp_thin_in_bwd_f32(dH.data_ptr(), X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma),
+                                              _lib.ptr(beta), _lib.ptr(bn_save), _lib.ptr(xmom), int(training), act, dW.data_ptr(), _lib.ptr(db),
+                                              _lib.ptr(dgamma), _lib.ptr(dbeta), ws, wsn, _lib.stream()), "mlsp_thin_in_bwd_f32")
+        return None, dW, db, dgamma, dbeta, None, None, None, None, None, None
+
+
+def thin_in(X, W, bias, gamma=None, beta=None, run_mean=None, run_var=None, training=True, act=ACT_RELU, momentum=0.1, eps=1e-5,
+            return_stats=False):
+    """act(BN?(X W^T + b)) on a row matrix X [M, Cin] with Cin <= 8 (the tokeniser's Conv1d(3,128)+BN+ReLU, pos_embed's Linear(3,128)+GELU):
+    [M, C] float32.  gamma None: no BatchNorm.  In training the batch statistics come from the input's mean and covariance, the running
+    buffers are updated in place as torch does.  act: ACT_NONE, ACT_RELU or ACT_GELU (erf form).  Gradients to W, bias, gamma, beta; none
+    to X (coordinates are inputs here).  `return_stats`: also bn_save [4, C] = scale | shift | mean | invstd (non-differentiable)."""
+    _lib.require_gpu(X, W, bias, gamma, beta, run_mean, run_var)
+    if X.requires_grad:
+        raise NotImplementedError("thin_in has no gradient with respect to its input")
+    H, bn_save = _ThinIn.apply(X, W, bias, gamma, beta, run_mean, run_var, bool(training), int(act), float(momentum), float(eps))
+    return (H, bn_save) if return_stats else H
+
+
+class _TokenPool(Function):
+    @staticmethod
+    def forward(ctx, y, B, L):
+        lib = _lib.load()
+        y = y.contiguous()
+        d = y.shape[1]
+        assert y.shape == (B * L, d), (y.shape, B, L)
+        out = torch.empty((B, 2 * d), dtype=torch.float32, device=y.device)
+        arg = torch.empty((B, d), dtype=torch.int32, device=y.device)
+        _token_check(lib.mlsp_token_pool_fwd_f32(y.data_ptr(), B, L, d, out.data_ptr(), arg.data_ptr(), _lib.stream()), "mlsp_token_pool_fwd_f32")
+        if _sel_record is not None or _sel_forced is not None:
+            _selection_hook(arg)               # test hooks: the row the backward routes each column's gradient to
+        ctx.save_for_backward(arg)
+        ctx.dims = (B, L, d)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dOut):
+        lib = _lib.load()
+        arg, = ctx.saved_tensors
+        B, L, d = ctx.dims
+        dOut = dOut.contiguous()
+        dy = torch.empty((B * L, d), dtype=torch.float32, device=dOut.device)
+        _token_check(lib.mlsp_token_pool_bwd_f32(dOut.data_ptr(), arg.data_ptr(), B, L, d, dy.data_ptr(), _lib.stream()), "mlsp_token_pool_bwd_f32")
+        return dy, None, None
+
+
+def token_pool(y, B, L):
+    """cat([x[:, 0], x[:, 1:].max(1)[0]], -1) of PointDA/Models.py:498 on the row matrix y [B*L, d] of the final LayerNorm -> [B, 2*d].  The
+    lowest row wins ties and a NaN row is never chosen while a number exists.  One HIP launch per direction."""
+    _lib.require_gpu(y)
+    return _TokenPool.apply(y, int(B), int(L))
 
 
 def gemm(A, B, ta=False, tb=False, bias=None):

@@ -123,6 +123,11 @@ def calc_loss(args, logits, labels, mask):
     return Fh.chamfer_masked(pred, labels, mask, args.DefRec_weight * DefRec_SCALER / pred.size(0))
 
 
+def calc_loss_ptrans(args, logits, labels, mask):
+    """MLSP/mlsp.py:461-468: calc_loss on the PointTransformer's bare DefRec prediction [B,N,3]."""
+    return Fh.chamfer_masked(logits, labels, mask, args.DefRec_weight * DefRec_SCALER / logits.size(0))
+
+
 def calc_scan_loss(args, logits, labels, mask):
     """MLSP/mlsp.py:231-238."""
     pred = logits['Rec_scan']

@@ -307,3 +307,16 @@ class density_classifier(nn.Module):
 
 # model_utils.py:201-289: the Point-BERT transformer encoder (mlsp_amd/vit.py)
 from .vit import Mlp, Attention, Block, TransformerEncoder   # noqa: E402,F401
+
+
+# model_utils.py:170-198, 292-336, 517-599: Group, Encoder (mlsp_amd/pointbert.py) and PointNetFeaturePropagation with its two helpers
+# (mlsp_amd/pointnet2.py).  Those modules import this one, so the names resolve on first use (PEP 562) instead of at import.
+_LAZY = {"Group": "pointbert", "Encoder": "pointbert", "PointNetFeaturePropagation": "pointnet2", "square_distance": "pointnet2",
+         "index_points": "pointnet2"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __package__), name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

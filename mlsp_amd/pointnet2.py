@@ -37,6 +37,12 @@ def index_points(points, idx):
     return res.reshape(*raw_size, -1)
 
 
+def square_distance(src, dst):
+    """PointDA/model_utils.py:517-531: src [B,N,C], dst [B,M,C] -> squared distances [B,N,M] (torch glue for callers of the reference's
+    helper; the kernels here never build this matrix)."""
+    return torch.sum((src[:, :, None] - dst[:, None]) ** 2, dim=-1)
+
+
 def farthest_point_sample(xyz, npoint, start=None):
     """pointnet_util.py:53-73.  xyz [B,N,3] -> sampled indices [B,npoint] (int64).  `start` [B] fixes the first sample
     (the reference draws it with torch.randint, :65; omitted -> drawn here the same way)."""

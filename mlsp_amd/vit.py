@@ -16,7 +16,7 @@ pointmlp GEMMs with functional.layernorm / mhsa / gelu (csrc/attn.hip) between t
 
 No CPU fallback.  `drop` / `attn_drop` > 0 (which the reference's encoder never sets) raise NotImplementedError at construction.
 
-Not built: PointTransformer (PointDA/Models.py:365), Group, Encoder and its variants (DGCNN_Propagation: mlsp_amd/propagation.py).
+The model around the stack -- PointTransformer, Group, Encoder -- is mlsp_amd/pointbert.py (DGCNN_Propagation: mlsp_amd/propagation.py).
 """
 import torch
 import torch.nn as nn
