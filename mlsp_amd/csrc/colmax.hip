@@ -12,6 +12,9 @@
 //     dX = X (-M) - 1 (x) r + rows scattered from g,            M = W^T diag(Bc) W,  r = W^T (A - Bc*mean)
 // i.e. two [Cin x Cin]-sized contractions over the points instead of two [Cout x Cin]-sized ones (conv5: 2x fewer
 // FLOPs, conv3: 8x), no BN streaming passes over [P,Cout], no dense scatter target.
+// The two sparse products -- S = rows of X gathered by arg (dW), rows of W scattered into dX by arg -- have B*Cout non-zeros and are
+// bound by the latency of dependent loads (index, then row), not by bandwidth: both fetch the indices of a batch of entries first and
+// issue the batch's row loads together.  Neither uses a global atomic, and both add in an order fixed by (arg, shape).
 #include "common.h"
 #include <math.h>
 
@@ -140,19 +143,40 @@ __global__ __launch_bounds__(1024) void wt_vec_neg_kernel(const float* __restric
     }
 }
 
-// S[c][:] = sum_b g[b][c] * X[b*N + arg[b][c]][:]       block = (c, 256-wide chunk of Cin), fixed order over b
+// Both sparse products below walk their lists in batches of ROW_BATCH entries: the entries' indices and coefficients sit one per lane,
+// are handed to the whole wave with readlane, and the batch's row loads are issued together before the first of them is used.
+// A batch that runs past its list repeats the list's last entry (a load that hits the line just fetched) and does not accumulate it.
+#define ROW_BATCH 16
+#define ROW_COLS 64          // columns per wave: lane = column
+
+// S[c][:] = sum_b g[b][c] * X[b*N + arg[b][c]][:]       one wave per (c, 64-column chunk of Cin), ascending b
+// (g and arg of up to 64 clouds are one vector load each, and the clouds' rows are loaded ROW_BATCH at a time: the kernel is bound
+// by the latency of its dependent loads -- arg, then the row -- and takes the same time at Cin 128 and 512)
 __global__ __launch_bounds__(256) void colmax_gather_rows_kernel(const float* __restrict__ g, const int* __restrict__ arg,
                                                                  const float* __restrict__ X, int ldx, int B, int N, int Cout,
-                                                                 int Cin, float* __restrict__ S) {
-    const int c = blockIdx.x;
-    const int i = blockIdx.y * 256 + threadIdx.x;
-    if (i >= Cin) return;
+                                                                 int Cin, int nchunk, float* __restrict__ S) {
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)Cout * nchunk) return;                      // (wave-uniform)
+    const int c = (int)(item / nchunk), col = (int)(item % nchunk) * ROW_COLS + lane;
+    const int colc = min(col, Cin - 1);
     float acc = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const size_t t = (size_t)b * Cout + c;
-        acc = fmaf(g[t], X[((size_t)b * N + arg[t]) * ldx + i], acc);
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int nb = min(64, B - b0);
+        const int bj = b0 + min(lane, nb - 1);
+        const size_t t = (size_t)bj * Cout + c;
+        const int rowj = bj * N + min(max(arg[t], 0), N - 1);
+        const int gj = __float_as_int(g[t]);
+        for (int bb = 0; bb < nb; bb += ROW_BATCH) {
+            float xv[ROW_BATCH];
+#pragma unroll
+            for (int u = 0; u < ROW_BATCH; ++u) xv[u] = X[(size_t)__builtin_amdgcn_readlane(rowj, bb + u) * ldx + colc];
+#pragma unroll
+            for (int u = 0; u < ROW_BATCH; ++u)
+                if (bb + u < nb) acc = fmaf(__int_as_float(__builtin_amdgcn_readlane(gj, bb + u)), xv[u], acc);
+        }
     }
-    S[(size_t)c * Cin + i] = acc;
+    if (col < Cin) S[(size_t)c * Cin + col] = acc;
 }
 
 // dW = S - A (x) sx - Bc (WG - mean (x) sx)
@@ -171,8 +195,43 @@ __global__ void colmax_dw_kernel(const float* __restrict__ S, const float* __res
 // channel -> fixed summation order) and accumulates its slice of the rows.  The arg-max of many channels lands on the same
 // few "critical" points, so list lengths are heavily skewed: rows with up to CSR_LONG entries are handled one per wave,
 // longer ones by all waves of the workgroup together (entries strided over the waves, partial rows added in wave order).
+// Either way a wave takes its entries CSR_BATCH at a time: their channels, g and W rows are loaded together, then added in list
+// order -- the additions and their order are those of one entry per trip, without a round trip to L2 per entry.
 #define CSR_SPLIT 16
 #define CSR_LONG 8
+#define CSR_BATCH 4
+// acc[u] = fmaf(g[c], W[c][i0 + lane + 64 u], acc[u]) for c = lst[e], e = e_beg, e_beg + stride, ... < e_end, in that order
+// (e_beg, e_end and stride are the same in every lane of the wave)
+static __device__ __forceinline__ void csr_accumulate(const int* lst, const float* __restrict__ gb, const float* __restrict__ W, int ldw,
+                                                      int Cin, int i0, int lane, int e_beg, int e_end, int stride, float (&acc)[4]) {
+    for (int e = e_beg; e < e_end; e += stride * CSR_BATCH) {
+        float wv[CSR_BATCH][4], gv[CSR_BATCH];
+#pragma unroll
+        for (int v = 0; v < CSR_BATCH; ++v) {
+            gv[v] = 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wv[v][u] = 0.f;
+            if (e + stride * v < e_end) {
+                const int c = lst[e + stride * v];
+                gv[v] = gb[c];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    int i = i0 + lane + 64 * u;
+                    if (i < Cin) wv[v][u] = W[(size_t)c * ldw + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < CSR_BATCH; ++v)
+            if (e + stride * v < e_end) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    int i = i0 + lane + 64 * u;
+                    if (i < Cin) acc[u] = fmaf(gv[v], wv[v][u], acc[u]);
+                }
+            }
+    }
+}
 __global__ __launch_bounds__(1024) void colmax_scatter_rows_kernel(const float* __restrict__ g, const int* __restrict__ arg,
                                                                   const float* __restrict__ W, int ldw, int N, int Cout, int Cin,
                                                                   float* __restrict__ dX, int lddx) {
@@ -220,7 +279,7 @@ __global__ __launch_bounds__(1024) void colmax_scatter_rows_kernel(const float* 
     const float* gb = g + (size_t)b * Cout;
     // short lists: one wave per row
     for (int p = p0 + wave; p < p1; p += nw) {
-        const int e0 = off[p], e1 = off[p + 1];
+        const int e0 = __builtin_amdgcn_readfirstlane(off[p]), e1 = __builtin_amdgcn_readfirstlane(off[p + 1]);
         if (e0 == e1 || e1 - e0 > CSR_LONG) continue;
         float* o = dX + ((size_t)b * N + p) * lddx;
         for (int i0 = 0; i0 < Cin; i0 += 256) {
@@ -230,15 +289,7 @@ __global__ __launch_bounds__(1024) void colmax_scatter_rows_kernel(const float* 
                 int i = i0 + lane + 64 * u;
                 acc[u] = i < Cin ? o[i] : 0.f;
             }
-            for (int e = e0; e < e1; ++e) {
-                const int c = lst[e];
-                const float gv = gb[c];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    int i = i0 + lane + 64 * u;
-                    if (i < Cin) acc[u] = fmaf(gv, W[(size_t)c * ldw + i], acc[u]);
-                }
-            }
+            csr_accumulate(lst, gb, W, ldw, Cin, i0, lane, e0, e1, 1, acc);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 int i = i0 + lane + 64 * u;
@@ -248,26 +299,19 @@ __global__ __launch_bounds__(1024) void colmax_scatter_rows_kernel(const float* 
     }
     // long lists: the whole workgroup per row (control flow is uniform: p and the list bounds come from LDS)
     for (int p = p0; p < p1; ++p) {
-        const int e0 = off[p], e1 = off[p + 1];
+        const int e0 = __builtin_amdgcn_readfirstlane(off[p]), e1 = __builtin_amdgcn_readfirstlane(off[p + 1]);
         if (e1 - e0 <= CSR_LONG) continue;
         float* o = dX + ((size_t)b * N + p) * lddx;
         for (int i0 = 0; i0 < Cin; i0 += 256) {
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int e = e0 + wave; e < e1; e += nw) {
-                const int c = lst[e];
-                const float gv = gb[c];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    int i = i0 + lane + 64 * u;
-                    if (i < Cin) acc[u] = fmaf(gv, W[(size_t)c * ldw + i], acc[u]);
-                }
-            }
+            const float was = (tid < 256 && i0 + tid < Cin) ? o[i0 + tid] : 0.f;      // (the row's own value: read with the W loads)
+            csr_accumulate(lst, gb, W, ldw, Cin, i0, lane, e0 + wave, e1, nw, acc);
             __syncthreads();                               // previous slice's readers are done with red
 #pragma unroll
             for (int u = 0; u < 4; ++u) red[wave * 256 + lane + 64 * u] = acc[u];
             __syncthreads();
             if (tid < 256 && i0 + tid < Cin) {
-                float s = o[i0 + tid];
+                float s = was;
                 for (int w = 0; w < nw; ++w) s += red[w * 256 + tid];
                 o[i0 + tid] = s;
             }
@@ -305,7 +349,9 @@ int launch_wt_vec_neg_scale_rows(hipStream_t st, const float* W, int ldw, const 
 }
 int launch_colmax_gather_rows(hipStream_t st, const float* g, const int* arg, const float* X, int ldx, int B, int N, int Cout,
                               int Cin, float* S) {
-    hipLaunchKernelGGL(colmax_gather_rows_kernel, dim3(Cout, (Cin + 255) / 256), dim3(256), 0, st, g, arg, X, ldx, B, N, Cout, Cin, S);
+    const int nchunk = (Cin + ROW_COLS - 1) / ROW_COLS;
+    const long waves = (long)Cout * nchunk;
+    hipLaunchKernelGGL(colmax_gather_rows_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, g, arg, X, ldx, B, N, Cout, Cin, nchunk, S);
     return mlsp_launch_status();
 }
 int launch_colmax_dw(hipStream_t st, const float* S, const float* WG, const float* sx, const float* coef, const float* bn, int Cout,
