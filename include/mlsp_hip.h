@@ -640,6 +640,28 @@ int mlsp_thin_in_bwd_f32(const float* dH, const float* X, int ldx, int M, int Ci
 int mlsp_token_pool_fwd_f32(const float* y, int B, int L, int d, float* out, int32_t* arg, mlsp_stream_t stream);
 int mlsp_token_pool_bwd_f32(const float* dOut, const int32_t* arg, int B, int L, int d, float* dy, mlsp_stream_t stream);
 
+/* The two stages of the Point Transformer models (hengshuang_model.py) that no other entry covers (pyramid.hip).  fp32 rows of C channels;
+ * no atomics, every sum in a fixed order: results are bit-identical run to run.  Limits: C % 4 == 0 and 16-byte-aligned feat / add / out /
+ * dout / dfeat / X / dOut / dX (so 16-byte-aligned rows) -- anything else returns MLSP_ERR_UNSUPPORTED, launches nothing and leaves the
+ * outputs untouched.  No entry reaches a matrix core.
+ *
+ * Upsample-and-add (TransitionUp): out [B][N][C] = add [B][N][C] + sum_{j<3} w_j feat[b][idx[b][n][j]], feat [B][S][C], idx / dist [B][N][3]
+ * as mlsp_knn_query_f32 leaves them (entries in [0, S)), w_j = (1 / (dist_j + 1e-8)) / sum_j' (1 / (dist_j' + 1e-8)) -- the weights and the
+ * summation order of mlsp_interp3_fwd_f32.  S == 1: out = add + feat[b][0], idx / dist may be NULL; S == 2 is MLSP_ERR_UNSUPPORTED.
+ * Backward: dfeat [B][S][C] over the reverse index of idx (mlsp_group_reverse(idx, B, N, S, 3, ...)), one writer per element, list order;
+ * S == 1: the sum of the cloud's rows of dout, accumulated in double, and dist / rev_off / rev_ent may be NULL.  The gradient of `add` is
+ * dout itself. */
+int mlsp_interp3_add_fwd_f32(const float* feat, const int32_t* idx, const float* dist, const float* add, int B, int N, int S, int C, float* out,
+                             mlsp_stream_t stream);
+int mlsp_interp3_add_bwd_f32(const float* dout, const float* dist, const int32_t* rev_off, const int32_t* rev_ent, int B, int N, int S, int C,
+                             float* dfeat, mlsp_stream_t stream);
+
+/* Cloud mean (points.mean(1)): X [B N][C] -> out [B][C] = the mean over the N rows of cloud b.  Every thread adds its rows in double from
+ * the first addition, the partial sums are added in ascending order in double, and the quotient is rounded to fp32 once: the result is
+ * within half an fp32 ulp plus N 2^-53 sum |x| / N of the exact mean.  Backward: dX [B N][C] = dOut[b] / N, written completely. */
+int mlsp_cloud_mean_fwd_f32(const float* X, int B, int N, int C, float* out, mlsp_stream_t stream);
+int mlsp_cloud_mean_bwd_f32(const float* dOut, int B, int N, int C, float* dX, mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1132,4 +1132,23 @@ int mlsp_token_pool_bwd_f32(const float* dOut, const int32_t* arg, int B, int L,
     return launch_token_pool_bwd(st, dOut, arg, B, L, d, dy);
 }
 
+int mlsp_interp3_add_fwd_f32(const float* feat, const int32_t* idx, const float* dist, const float* add, int B, int N, int S, int C, float* out,
+                             mlsp_stream_t st) {
+    if (!feat || !add || !out || (S != 1 && (!idx || !dist)) || B <= 0 || N <= 0 || S <= 0 || C <= 0) return MLSP_ERR_ARG;
+    return launch_interp3_add_fwd(st, feat, idx, dist, add, B, N, S, C, out);
+}
+int mlsp_interp3_add_bwd_f32(const float* dout, const float* dist, const int32_t* rev_off, const int32_t* rev_ent, int B, int N, int S, int C,
+                             float* dfeat, mlsp_stream_t st) {
+    if (!dout || !dfeat || (S != 1 && (!dist || !rev_off || !rev_ent)) || B <= 0 || N <= 0 || S <= 0 || C <= 0) return MLSP_ERR_ARG;
+    return launch_interp3_add_bwd(st, dout, dist, rev_off, rev_ent, B, N, S, C, dfeat);
+}
+int mlsp_cloud_mean_fwd_f32(const float* X, int B, int N, int C, float* out, mlsp_stream_t st) {
+    if (!X || !out || B <= 0 || N <= 0 || C <= 0) return MLSP_ERR_ARG;
+    return launch_cloud_mean_fwd(st, X, B, N, C, out);
+}
+int mlsp_cloud_mean_bwd_f32(const float* dOut, int B, int N, int C, float* dX, mlsp_stream_t st) {
+    if (!dOut || !dX || B <= 0 || N <= 0 || C <= 0) return MLSP_ERR_ARG;
+    return launch_cloud_mean_bwd(st, dOut, B, N, C, dX);
+}
+
 }  // extern "C"

@@ -312,3 +312,12 @@ int launch_thin_in_bwd(hipStream_t st, const float* dH, const float* X, int ldx,
                        float* db, float* dgamma, float* dbeta, Workspace& ws);
 int launch_token_pool_fwd(hipStream_t st, const float* y, int B, int L, int d, float* out, int* arg);
 int launch_token_pool_bwd(hipStream_t st, const float* dOut, const int* arg, int B, int L, int d, float* dy);
+
+// pyramid.hip
+// S == 1: idx / dist / the reverse lists are not read (a broadcast, a cloud sum); S == 2 is refused
+int launch_interp3_add_fwd(hipStream_t st, const float* feat, const int* idx, const float* dist, const float* add, int B, int N, int S, int C,
+                           float* out);
+int launch_interp3_add_bwd(hipStream_t st, const float* dout, const float* dist, const int* rev_off, const int* rev_ent, int B, int N, int S,
+                           int C, float* dfeat);
+int launch_cloud_mean_fwd(hipStream_t st, const float* X, int B, int N, int C, float* out);
+int launch_cloud_mean_bwd(hipStream_t st, const float* dOut, int B, int N, int C, float* dX);

@@ -2405,6 +2405,100 @@ def token_pool(y, B, L):
     return _TokenPool.apply(y, int(B), int(L))
 
 
+def _pyramid_check(rc, what):
+    """MLSP_ERR_UNSUPPORTED and MLSP_ERR_ARG of the pyramid kernels are a MlspLibraryError: there is no other path"""
+    if rc in (-1, -3):
+        raise _lib.MlspLibraryError("%s: %s (interp3_add and cloud_mean need C %% 4 == 0, 16-byte-aligned rows and S == 1 or S >= 3 source "
+                                    "points)" % (what, _lib.load().mlsp_strerror(rc).decode()))
+    _lib.check(rc, what)
+
+
+class _Interp3Add(Function):
+    """add + the inverse-distance interpolation of feat from the three nearest source points (mlsp_interp3_add_*_f32): the interpolated
+    tensor is never built.  S == 1: add + the cloud's one source row.  Saved for the backward: idx32 and dist."""
+
+    @staticmethod
+    def forward(ctx, feat, add, idx32, dist):
+        lib = _lib.load()
+        feat, add = feat.contiguous(), add.contiguous()
+        B, S, C = feat.shape
+        N = add.shape[1]
+        assert add.shape == (B, N, C) and (S == 1 or (idx32.shape == (B, N, 3) and dist.shape == (B, N, 3))), (feat.shape, add.shape)
+        out = torch.empty((B, N, C), dtype=torch.float32, device=feat.device)
+        _pyramid_check(lib.mlsp_interp3_add_fwd_f32(feat.data_ptr(), _lib.ptr(idx32), _lib.ptr(dist), add.data_ptr(), B, N, S, C, out.data_ptr(),
+                                                    _lib.stream()), "mlsp_interp3_add_fwd_f32")
+        ctx.save_for_backward(idx32, dist)
+        ctx.dims = (B, N, S, C)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.load()
+        idx32, dist = ctx.saved_tensors
+        B, N, S, C = ctx.dims
+        dout = dout.contiguous()
+        dev = dout.device
+        dfeat = None
+        if ctx.needs_input_grad[0]:
+            rev_off = rev_ent = None
+            if S > 1:
+                rev_off = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
+                rev_ent = torch.empty((B * N * 3,), dtype=torch.int32, device=dev)
+                _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, N, S, 3, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
+                           "mlsp_group_reverse")
+            dfeat = torch.empty((B, S, C), dtype=torch.float32, device=dev)
+            _pyramid_check(lib.mlsp_interp3_add_bwd_f32(dout.data_ptr(), _lib.ptr(dist), _lib.ptr(rev_off), _lib.ptr(rev_ent), B, N, S, C,
+                                                        dfeat.data_ptr(), _lib.stream()), "mlsp_interp3_add_bwd_f32")
+        return dfeat, (dout if ctx.needs_input_grad[1] else None), None, None
+
+
+def interp3_add(feat, add, idx=None, dist=None):
+    """add [B, N, C] + sum_j w_j feat[b, idx[b, n, j]]: feat [B, S, C], idx int32 [B, N, 3] (entries in [0, S)) and dist float32 [B, N, 3] as
+    knn_point(3, ..., return_dist=True) leaves them, w = 1 / (dist + 1e-8) normalised over the three (pointnet_util.py:287-294 followed by
+    hengshuang_model.py:46) -> [B, N, C].  S == 1: every row receives the cloud's one source row, idx / dist are not read.  Gradients to
+    feat (over the reverse index, no atomics) and add (dout itself)."""
+    _lib.require_gpu(feat, add, idx, dist)
+    if feat.shape[1] != 1:
+        if idx is None or dist is None:
+            raise ValueError("interp3_add needs idx and dist unless there is one source point per cloud")
+        idx, dist = idx.contiguous(), dist.contiguous()
+        assert idx.dtype == torch.int32 and dist.dtype == torch.float32, (idx.dtype, dist.dtype)
+    else:
+        idx = dist = None
+    return _Interp3Add.apply(feat, add, idx, dist)
+
+
+class _CloudMean(Function):
+    @staticmethod
+    def forward(ctx, X, B, N):
+        lib = _lib.load()
+        X = X.contiguous()
+        C = X.shape[1]
+        assert X.shape == (B * N, C), (X.shape, B, N)
+        out = torch.empty((B, C), dtype=torch.float32, device=X.device)
+        _pyramid_check(lib.mlsp_cloud_mean_fwd_f32(X.data_ptr(), B, N, C, out.data_ptr(), _lib.stream()), "mlsp_cloud_mean_fwd_f32")
+        ctx.dims = (B, N, C)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dOut):
+        lib = _lib.load()
+        B, N, C = ctx.dims
+        dOut = dOut.contiguous()
+        dX = torch.empty((B * N, C), dtype=torch.float32, device=dOut.device)
+        _pyramid_check(lib.mlsp_cloud_mean_bwd_f32(dOut.data_ptr(), B, N, C, dX.data_ptr(), _lib.stream()), "mlsp_cloud_mean_bwd_f32")
+        return dX, None, None
+
+
+def cloud_mean(X, B, N):
+    """points.mean(1) on the row matrix X [B*N, C] -> [B, C]: fp64 accumulation in a fixed order, one rounding to fp32.  One HIP launch per
+    direction; the backward writes dX completely."""
+    _lib.require_gpu(X)
+    return _CloudMean.apply(X, int(B), int(N))
+
+
 def gemm(A, B, ta=False, tb=False, bias=None):
     """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests."""
     lib = _lib.load()

@@ -8,7 +8,7 @@ bit-exact indices; the SA-MLP is the fused Linear+BN+ReLU kernel family over the
 per-centre max.  No CPU fallback: every entry point raises MlspLibraryError without the HIP library.
 
 `knn=True` grouping, PointNetSetAbstractionMsg and PointNetFeaturePropagation run on the query-kNN kernel (ref != query,
-mlsp_knn_query_f32) and the 3-NN interpolation kernels.  Not built: gradients with respect to the coordinates (the reference never
+mlsp_knn_query_f32) and the 3-NN interpolation kernels; the Point Transformer models that stand on them are hengshuang_model.py.  Not built: gradients with respect to the coordinates (the reference never
 asks for them: coordinates are inputs).
 """
 import torch
@@ -251,13 +251,28 @@ def _fold_first_layer(xyz, new_xyz, points, idx, W0, conv, bn, training):
     return _SAFold.apply(u, w, idx32, bn.weight, bn.bias, rm, rv, training, bn.momentum, bn.eps, (B, N, S, ns))
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=False, fps_start=None):
+def _pinned(idx, shape, bound, what):
+    """a caller's index tensor in place of a search: int64 on the GPU, the shape the search would give, entries in [0, bound)"""
+    _lib.require_gpu(idx)
+    if tuple(idx.shape) != tuple(shape) or int(idx.min()) < 0 or int(idx.max()) >= bound:
+        raise ValueError("%s: expected %s indices in [0, %d), got shape %s" % (what, tuple(shape), bound, tuple(idx.shape)))
+    return idx.long()
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=False, fps_start=None, fps_idx=None, idx=None, chosen=None):
     """pointnet_util.py:99-136: FPS centres, ball-query neighbourhoods, centred coordinates + features.
-    Returns new_xyz [B,npoint,3], new_points [B,npoint,nsample,3+D] (+ grouped_xyz, fps_idx with returnfps)."""
+    Returns new_xyz [B,npoint,3], new_points [B,npoint,nsample,3+D] (+ grouped_xyz, fps_idx with returnfps).
+    `fps_idx` [B,npoint] / `idx` [B,npoint,nsample] pin the centres / the neighbourhoods instead of searching them; `chosen` (a list)
+    receives (fps_idx, idx) as used."""
     B, N, C = xyz.shape
-    fps_idx = farthest_point_sample(xyz, npoint, start=fps_start)
+    fps_idx = farthest_point_sample(xyz, npoint, start=fps_start) if fps_idx is None else _pinned(fps_idx, (B, npoint), N, "fps_idx")
     new_xyz = index_points(xyz, fps_idx)
-    idx = knn_point(nsample, xyz, new_xyz) if knn else query_ball_point(radius, nsample, xyz, new_xyz)      # :116-120
+    if idx is not None:
+        idx = _pinned(idx, (B, npoint, nsample), N, "idx")
+    else:
+        idx = knn_point(nsample, xyz, new_xyz) if knn else query_ball_point(radius, nsample, xyz, new_xyz)      # :116-120
+    if chosen is not None:
+        chosen.append((fps_idx, idx))
     G = _Group.apply(xyz, new_xyz, points, idx)
     new_points = G.view(B, npoint, nsample, -1)
     if returnfps:
@@ -276,7 +291,8 @@ def sample_and_group_all(xyz, points):
 
 class PointNetSetAbstraction(nn.Module):
     """pointnet_util.py:159-196.  forward(xyz [B,N,3], points [B,N,D] | None) -> new_xyz [B,S,3], new_points [B,S,mlp[-1]].
-    `fps_start` (attribute, optional [B] tensor) pins the first FPS sample for reproducible parity runs."""
+    `fps_start` (attribute, optional [B] tensor) pins the first FPS sample for reproducible parity runs; forward's `fps_idx` [B,S] and
+    `idx` [B,S,nsample] (int64) pin all centres / all neighbourhoods, and `chosen` (a list) receives the (fps_idx, idx) it used."""
 
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, knn=False):
         super(PointNetSetAbstraction, self).__init__()
@@ -297,7 +313,7 @@ class PointNetSetAbstraction(nn.Module):
         self.fuse_max = True            # last conv + BN + ReLU + neighbourhood max in one op (no activated edge tensor); False: separate max
 
     @flushing_forward
-    def forward(self, xyz, points):
+    def forward(self, xyz, points, fps_idx=None, idx=None, chosen=None):
         B = xyz.shape[0]
         if self.group_all:
             new_xyz, new_points = sample_and_group_all(xyz, points)
@@ -306,9 +322,15 @@ class PointNetSetAbstraction(nn.Module):
             # sample_and_group (pointnet_util.py:99-136) without its output tensor: the first conv is folded onto the points (the
             # coordinates' gradient flows through the two K = 3 products u and w of _fold_first_layer, like the features')
             S, ns = self.npoint, self.nsample
-            fps_idx = farthest_point_sample(xyz, S, start=self.fps_start)
+            N = xyz.shape[1]
+            fps_idx = farthest_point_sample(xyz, S, start=self.fps_start) if fps_idx is None else _pinned(fps_idx, (B, S), N, "fps_idx")
             new_xyz = index_points(xyz, fps_idx)
-            idx = knn_point(ns, xyz, new_xyz) if self.knn else query_ball_point(self.radius, ns, xyz, new_xyz)
+            if idx is not None:
+                idx = _pinned(idx, (B, S, ns), N, "idx")
+            else:
+                idx = knn_point(ns, xyz, new_xyz) if self.knn else query_ball_point(self.radius, ns, xyz, new_xyz)
+            if chosen is not None:
+                chosen.append((fps_idx, idx))
             c0 = self.mlp_convs[0]
             X = _fold_first_layer(xyz, new_xyz, points, idx, c0.weight.view(c0.out_channels, c0.in_channels), c0, self.mlp_bns[0],
                                   self.training)
@@ -316,7 +338,7 @@ class PointNetSetAbstraction(nn.Module):
             return new_xyz, (out if self.fuse_max else _neigh_max(out, ns)).view(B, S, -1)
         else:
             new_xyz, new_points = sample_and_group(self.npoint, self.radius, self.nsample, xyz, points, knn=self.knn,
-                                                   fps_start=self.fps_start)
+                                                   fps_start=self.fps_start, fps_idx=fps_idx, idx=idx, chosen=chosen)
             S, ns = self.npoint, self.nsample
         X = new_points.reshape(B * S * ns, new_points.shape[-1])          # edge-major rows (b, centre, slot)
         first_weight = None

@@ -5,8 +5,8 @@ Mirrors PointDA/hengshuang_transformer/transformer.py: same class name, construc
 `w_vs.weight`): the nn.Linear / nn.Sequential members hold the parameters only, the arithmetic is functional.vector_attention
 (csrc/vecattn.hip) between pointmlp GEMMs.  No CPU fallback.
 
-Not built: the models around the block (TransitionDown / TransitionUp / Backbone / PointTransformerCls, Seg, Def of hengshuang_model.py),
-gradients with respect to the coordinates, and a gradient through the returned attention weights.
+The models around the block (TransitionDown / TransitionUp / Backbone / PointTransformerCls, Seg, Def) are mlsp_amd/hengshuang_model.py.
+Not built: gradients with respect to the coordinates, and a gradient through the returned attention weights.
 """
 import torch
 import torch.nn as nn
