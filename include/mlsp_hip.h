@@ -14,8 +14,9 @@
  *     success, a negative MLSP_ERR_* code for bad arguments, or a positive hipError_t.  The compute
  *     entry points keep no mutable state: what a call does is a function of its arguments alone, from any thread, on any stream
  *     (ABI v8: the products of the GEMM family are the per-call `precision` argument below, not a library switch; ABI v13:
- *     mlsp_operand_bounds_next hands ONE following call an optional table through a thread-local slot that the call empties -- an
- *     out-of-band argument of that call, not state).  The only process-wide object is the measurement hook mlsp_profile_begin/_end (HIP events around launches while armed; bench.py only,
+ *     mlsp_operand_bounds_next hands ONE following call an optional table through a thread-local slot -- the library's only one -- that
+ *     the next entry point with a `precision` empties as its first act, a shape query or a call it rejects included: an out-of-band
+ *     argument of that call, not state.  Inside, the call's mode, operand bounds and table travel as one explicit context object).  The only process-wide object is the measurement hook mlsp_profile_begin/_end (HIP events around launches while armed; bench.py only,
  *     never armed in a production step).  The library reads one environment variable, MLSP_PROF_DUMP (a listing of
  *     the profiled launches while the hook is armed); it changes no kernel choice.
  *   - `precision` (every entry point that reaches a matrix-core contraction takes it, just before its workspace):

@@ -43,17 +43,18 @@ size_t mlsp_workspace_bytes(int rows, int cin, int cout) {
                + r * ci * sizeof(float);                                    // a chained layer's activated input, shapes outside the fused path
     size_t parts = (r / 64 + 2) * 2 * co * sizeof(double);                  // stat partials
     size_t wts = 4 * co * ci * sizeof(float) * 2 + 8 * co * sizeof(float);  // Wd, dWd, coefficient vectors
-    return act + parts + wts + SLAB_BOUND_FLOATS * sizeof(float) + (32 << 20) + MLSP_AMAX_TAIL_BYTES;       // + fixed-size per-workgroup partial slabs + the tail PREC_SCOPE reserves
+    return act + parts + wts + SLAB_BOUND_FLOATS * sizeof(float) + (32 << 20) + MLSP_AMAX_TAIL_BYTES;       // + fixed-size per-workgroup partial slabs + the tail of the call's CallCtx
 }
 
 int mlsp_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                   const float* bias, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     Workspace w(ws, ws_bytes);
     GemmOpts o; o.bias = bias;
     take_slab(w, o, gemm_slab_floats(M, N, K));
     if (!o.slab) o.slab_floats = 0;   // launcher falls back to a single pass
-    return launch_gemm(st, ta != 0, tb != 0, M, N, K, A, lda, B, ldb, C, ldc, o);
+    return launch_gemm(st, cx, ta != 0, tb != 0, M, N, K, A, lda, B, ldb, C, ldc, o);
 }
 
 int mlsp_knn_f32(const float* x, int ldx, int B, int N, int C, int k, int32_t* idx, int32_t* rev_off, int32_t* rev_ent,
@@ -183,7 +184,8 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
                           float* run_mean, float* run_var, float momentum, float eps, int act, float slope, int training,
                           int B, int N, int C, int Cout, int k, float* out, int ldo, float* uv, float* msel, uint8_t* argsel,
                           float* s1, float* bn_save, float* Wd_out, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!x || !idx || !W || !gamma || !beta || !out || !uv || !msel || !argsel || !s1 || !bn_save) return MLSP_ERR_ARG;
     if (B <= 0 || N <= 0 || C <= 0 || Cout <= 0 || k <= 0 || k > 255 || ldx < C || ldo < Cout) return MLSP_ERR_ARG;
     const int P = B * N;
@@ -197,8 +199,8 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
     if (!training) {                  // eval mode: the BatchNorm vectors do not depend on the batch -- prepared by the weight-fold launch
         if (!run_mean || !run_var) return MLSP_ERR_ARG;
         CHECK(launch_build_wd_eval(st, W, Cout, C, Wd, Cout, gamma, beta, run_mean, run_var, bn_save, 0, nullptr, nullptr, nullptr, nullptr, nullptr, eps));
-    } else CHECK(launch_build_wd(st, W, Cout, C, Wd, (C >= 128 && C % 32 == 0 && build_wd_leaves_bound(Cout, C)) ? amax_reserve(Wd, 2 * Cout, C, C) : nullptr));   // (mode 3: the fold leaves the bound of what it writes)
-    CHECK(launch_gemm(st, false, true, P, 2 * Cout, C, x, ldx, Wd, C, uv, 2 * Cout, so));
+    } else CHECK(launch_build_wd(st, W, Cout, C, Wd, (C >= 128 && C % 32 == 0 && build_wd_leaves_bound(Cout, C)) ? cx.reserve(Wd, 2 * Cout, C, C) : nullptr));   // (mode 3: the fold leaves the bound of what it writes)
+    CHECK(launch_gemm(st, cx, false, true, P, 2 * Cout, C, x, ldx, Wd, C, uv, 2 * Cout, so));
     {   // the neighbour gather + max/min + BN sums: compulsory bytes = u half + indices in, msel + s1 + arg slot out
         const int tok = prof_cls_begin(st, MLSP_PROF_EDGE_REDUCE);
         const int rc = launch_edge_reduce(st, uv, idx, gamma, P, N, Cout, k, msel, argsel, s1, part, &nparts);
@@ -209,7 +211,7 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
         // (mode 3, the caller offered bounds for `out`: the finalizer leaves |gamma| sqrt(P k) + |beta| per channel -- a bound of the layer's
         // output for the GEMMs that read it, instead of a streaming pass over it)
         CHECK(launch_bn_finalize(st, part, nparts, (double)P * k, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale,
-                                 shift, mean, invstd, amax_offered_output(out, P, Cout, ldo, Cout)));
+                                 shift, mean, invstd, cx.offered_output(out, P, Cout, ldo, Cout)));
     }
     CHECK(launch_edge_select_act(st, msel, uv, P, Cout, scale, shift, act, slope, out, ldo));
     return MLSP_OK;
@@ -220,7 +222,8 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
                           const float* s1, const float* bn_save, const float* Wd_in, int act, float slope, int training, int B, int N, int C,
                           int Cout, int k, float* dx, int lddx, int dx_accumulate, float* dW, float* dgamma, float* dbeta, int precision, void* ws,
                           size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!dOut || !x || !rev_off || !rev_ent || !W || !out || !uv || !msel || !argsel || !s1 || !bn_save || !dW || !dgamma ||
         !dbeta)
         return MLSP_ERR_ARG;
@@ -242,7 +245,7 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
     // below) instead of a measuring pass over the finished tensor
     // (only where those products can take the two-piece kernel at all: C a multiple of its 128-column tile -- conv4 of the DGCNN encoder)
     float* duv_amax = (C % 128 == 0 && edge_bwd_leaves_duv_bound(dOut, out, msel, uv, s1, argsel, Cout, scale, mean, invstd, gz, duv, lddo, ldo))
-                          ? amax_reserve(duv, P, 2 * Cout, 2 * Cout) : nullptr;
+                          ? cx.reserve(duv, P, 2 * Cout, 2 * Cout) : nullptr;
     CHECK(launch_edge_bwd_reduce(st, dOut, out, msel, uv, P, Cout, mean, invstd, act, slope, part, lddo, ldo, duv_amax));
     CHECK(launch_bn_bwd_finalize(st, part, edge_bwd_reduce_parts(P, Cout, dOut, out, msel, uv, mean, invstd, lddo, ldo), (double)P * k, Cout,
                                  dgamma, dbeta, mean_dz, mean_dzy));
@@ -253,10 +256,10 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
     const float* Wdc = Wd_in;
     if (!Wdc && dx) { CHECK(launch_build_wd(st, W, Cout, C, Wd)); Wdc = Wd; }
     GemmOpts od = so; od.accumulate = dx_accumulate != 0;
-    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * Cout, duv, 2 * Cout, Wdc, C, dx, lddx, od));
+    if (dx) CHECK(launch_gemm(st, cx, false, false, P, C, 2 * Cout, duv, 2 * Cout, Wdc, C, dx, lddx, od));
     bool unfolded = false;            // a split-K launch sums its slabs straight into the reference layout (gemm.hip splitk_reduce_unfold_kernel)
     GemmOpts ow = so; ow.unfold_dw = dW; ow.unfolded = &unfolded;
-    CHECK(launch_gemm(st, true, false, 2 * Cout, C, P, duv, 2 * Cout, x, ldx, dWd, C, ow));
+    CHECK(launch_gemm(st, cx, true, false, 2 * Cout, C, P, duv, 2 * Cout, x, ldx, dWd, C, ow));
     if (!unfolded) CHECK(launch_unbuild_wd(st, dWd, Cout, C, dW));
     return MLSP_OK;
 }
@@ -266,7 +269,8 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
                            float* run_mean2, float* run_var2, float momentum, float eps, float slope, int training, int B, int N,
                            int C, int C1, int C2, int k, float* out, float* uv, float* s1, float* bn1_save, float* zsel,
                            uint8_t* argsel, float* bn2_save, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!x || !idx || !W1 || !gamma1 || !beta1 || !W2 || !gamma2 || !beta2 || !out || !uv || !s1 || !bn1_save || !zsel || !argsel ||
         !bn2_save)
         return MLSP_ERR_ARG;
@@ -285,7 +289,7 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
         if (!run_mean1 || !run_var1 || !run_mean2 || !run_var2) return MLSP_ERR_ARG;
         CHECK(launch_build_wd_eval(st, W1, C1, C, Wd, C1, gamma1, beta1, run_mean1, run_var1, bn1_save, C2, gamma2, beta2, run_mean2, run_var2, bn2_save, eps));
     } else CHECK(launch_build_wd(st, W1, C1, C, Wd));
-    CHECK(launch_gemm(st, false, true, P, 2 * C1, C, x, ldx, Wd, C, uv, 2 * C1, so));
+    CHECK(launch_gemm(st, cx, false, true, P, 2 * C1, C, x, ldx, Wd, C, uv, 2 * C1, so));
     CHECK(launch_edge_reduce(st, uv, idx, gamma1, P, N, C1, k, msel, arg1, s1, part, &np1));
     if (training) {
         CHECK(launch_bn_finalize(st, part, np1, (double)P * k, C1, gamma1, beta1, run_mean1, run_var1, momentum, eps, bn1_save,
@@ -293,14 +297,14 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
     }
     {
         const int tok = prof_cls_begin(st, MLSP_PROF_TNET_FWD);
-        const int rc = launch_tnet_edge_fwd(st, uv, idx, bn1_save, W2, gamma2, P, N, k, slope, zsel, argsel, part);
+        const int rc = launch_tnet_edge_fwd(st, cx.mode(), uv, idx, bn1_save, W2, gamma2, P, N, k, slope, zsel, argsel, part);
         prof_cls_end(st, tok, 2.0 * P * (double)k * C1 * C2);                  // the per-edge 64 -> 128 contraction
         if (rc != MLSP_OK) return rc;
     }
     if (training) {
         // (mode 3: the analytic bound of the stage's output, as mlsp_edgeconv_fwd_f32)
         CHECK(launch_bn_finalize(st, part, np2, (double)P * k, C2, gamma2, beta2, run_mean2, run_var2, momentum, eps, bn2_save,
-                                 bn2_save + C2, bn2_save + 2 * C2, bn2_save + 3 * C2, amax_offered_output(out, P, C2, C2, C2)));
+                                 bn2_save + C2, bn2_save + 2 * C2, bn2_save + 3 * C2, cx.offered_output(out, P, C2, C2, C2)));
     }
     CHECK(launch_tnet_out(st, zsel, bn2_save, P, slope, out));
     return MLSP_OK;
@@ -312,7 +316,8 @@ int mlsp_tnet_edge_bwd_f32(const float* dOut, const float* x, int ldx, const int
                            float slope, int training, int B, int N, int C, int C1, int C2, int k, float* dx, float* dW1,
                            float* dgamma1, float* dbeta1, float* dW2, float* dgamma2, float* dbeta2, int precision, void* ws, size_t ws_bytes,
                            mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!dOut || !x || !idx || !W1 || !W2 || !out || !uv || !s1 || !bn1_save || !zsel || !argsel || !bn2_save ||
         !dW1 || !dgamma1 || !dbeta1 || !dW2 || !dgamma2 || !dbeta2)
         return MLSP_ERR_ARG;
@@ -355,7 +360,7 @@ int mlsp_tnet_edge_bwd_f32(const float* dOut, const float* x, int ldx, const int
     int nparts = 0;
     {
         const int tok = prof_cls_begin(st, MLSP_PROF_TNET_BWD);
-        const int rc = launch_tnet_edge_bwd(st, uv, idx, bn1_save, W2, bn2_save, g, argsel, coef, P, N, k, slope, dhp, dW2part, part, dW2, &nparts);
+        const int rc = launch_tnet_edge_bwd(st, cx.mode(), uv, idx, bn1_save, W2, bn2_save, g, argsel, coef, P, N, k, slope, dhp, dW2part, part, dW2, &nparts);
         prof_cls_end(st, tok, 4.0 * P * (double)k * C1 * C2);                  // dgrad + wgrad of that contraction
         if (rc != MLSP_OK) return rc;
     }
@@ -369,8 +374,8 @@ int mlsp_tnet_edge_bwd_f32(const float* dOut, const float* x, int ldx, const int
     }
     CHECK(launch_tnet_edge_bwd2(st, dhp, uv, s1, bn1_save, training ? m1 : nullptr, m2, rev_off, rev_ent, P, N, k, duv));
     CHECK(launch_build_wd(st, W1, C1, C, Wd));
-    if (dx) CHECK(launch_gemm(st, false, false, P, C, 2 * C1, duv, 2 * C1, Wd, C, dx, C, so));
-    CHECK(launch_gemm(st, true, false, 2 * C1, C, P, duv, 2 * C1, x, ldx, dWd, C, so));
+    if (dx) CHECK(launch_gemm(st, cx, false, false, P, C, 2 * C1, duv, 2 * C1, Wd, C, dx, C, so));
+    CHECK(launch_gemm(st, cx, true, false, 2 * C1, C, P, duv, 2 * C1, x, ldx, dWd, C, so));
     CHECK(launch_unbuild_wd(st, dWd, C1, C, dW1));
     return MLSP_OK;
 }
@@ -392,7 +397,7 @@ static GemmXf chain_xf(const mlsp_defer_t& in, int which, int batch_stats) {
 // a LeakyReLU slope outside [0, 1] takes the streaming pass: the fused transform writes the activation as one max
 static bool defer_fusable(const mlsp_defer_t& in) { return !(in.act == 2 && !(in.slope >= 0.f && in.slope <= 1.f)); }
 
-static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const float* W, int ldw, int Cout, const float* bias,
+static int pointmlp_fwd_impl(CallCtx& cx, const float* X, int ldx, int M, int Cin, const float* W, int ldw, int Cout, const float* bias,
                              const float* gbias, int rows_per_group, const float* gamma, const float* beta, float* run_mean,
                              float* run_var, float momentum, float eps, int training, int act, float slope, float p_drop,
                              uint64_t seed, float* Y, float* Z, float* bn_save, void* ws, size_t ws_bytes, mlsp_stream_t st,
@@ -411,7 +416,7 @@ static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const floa
                                            training, act, slope, p_drop, seed, Y, Z, bn_save);
     Workspace w(ws, ws_bytes);
     // BN batch statistics: fused into the GEMM epilogue (one partial per 128-row panel) unless the GEMM splits K
-    const int fused_parts = (gamma && training) ? gemm_stat_parts(M, Cout, Cin) : 0;
+    const int fused_parts = (gamma && training) ? gemm_stat_parts(cx, M, Cout, Cin) : 0;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(M);
     double* part = gamma ? w.take<double>((size_t)nparts * 2 * Cout) : nullptr;
     GemmOpts o; o.bias = bias; o.gbias = gbias; o.rows_per_group = rows_per_group;
@@ -419,7 +424,7 @@ static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const floa
     GemmXf xf_s;
     if (in) {
         xf_s = chain_xf(*in, 1, training);
-        if (defer_fusable(*in) && gemm_xf_supported(false, true, M, Cout, Cin, X, ldx, W, ldw, 1)) o.xf = &xf_s;
+        if (defer_fusable(*in) && gemm_xf_supported(cx, false, true, M, Cout, Cin, X, ldx, W, ldw, 1)) o.xf = &xf_s;
         else {                                             // shape outside the fused path: materialise the activated input once
             float* Xa = w.take<float>((size_t)M * Cin);
             if (!w.ok()) return MLSP_ERR_WORKSPACE;
@@ -431,11 +436,11 @@ static int pointmlp_fwd_impl(const float* X, int ldx, int M, int Cin, const floa
     if (!gamma) {
         // plain Linear: the GEMM writes Z directly.  Every activated layer of the hot path has a BN.
         if (act || p_drop > 0.f) return MLSP_ERR_UNSUPPORTED;
-        return launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Z, Cout, o);
+        return launch_gemm(st, cx, false, true, M, Cout, Cin, X, ldx, W, ldw, Z, Cout, o);
     }
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
     o.stat_part = fused_parts ? part : nullptr;
-    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
+    CHECK(launch_gemm(st, cx, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     const int prow = fused_parts ? M / fused_parts : 0;                    // rows per statistics panel
     const bool gsum_fin = group_ysum && training && fused_parts && M % fused_parts == 0 && rows_per_group % prow == 0;
     if (training) {
@@ -463,8 +468,9 @@ int mlsp_pointmlp_fwd_f32(const float* X, int ldx, int M, int Cin, const float* 
                           float* run_var, float momentum, float eps, int training, int act, float slope, float p_drop,
                           uint64_t seed, float* Y, float* Z, float* bn_save, float* group_ysum, int precision, void* ws, size_t ws_bytes,
                           mlsp_stream_t st) {
-    PREC_SCOPE(precision);
-    return pointmlp_fwd_impl(X, ldx, M, Cin, W, ldw, Cout, bias, gbias, rows_per_group, gamma, beta, run_mean, run_var, momentum, eps,
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
+    return pointmlp_fwd_impl(cx, X, ldx, M, Cin, W, ldw, Cout, bias, gbias, rows_per_group, gamma, beta, run_mean, run_var, momentum, eps,
                              training, act, slope, p_drop, seed, Y, Z, bn_save, ws, ws_bytes, st, nullptr, group_ysum);
 }
 
@@ -473,13 +479,14 @@ int mlsp_pointmlp_fwd_chain_f32(const float* Xpre, int ldx, const mlsp_defer_t* 
                                 float* run_var, float momentum, float eps, int training, int act, float slope, float p_drop,
                                 uint64_t seed, float* Y, float* Z, float* bn_save, float* group_ysum, int precision, void* ws, size_t ws_bytes,
                                 mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!in) return MLSP_ERR_ARG;
-    return pointmlp_fwd_impl(Xpre, ldx, M, Cin, W, ldw, Cout, bias, gbias, rows_per_group, gamma, beta, run_mean, run_var, momentum, eps,
+    return pointmlp_fwd_impl(cx, Xpre, ldx, M, Cin, W, ldw, Cout, bias, gbias, rows_per_group, gamma, beta, run_mean, run_var, momentum, eps,
                              training, act, slope, p_drop, seed, Y, Z, bn_save, ws, ws_bytes, st, in, group_ysum);
 }
 
-static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, int Cin, const float* W, int ldw, int Cout, const float* Y,
+static int pointmlp_bwd_impl(CallCtx& cx, const float* dZ, const float* X, int ldx, int M, int Cin, const float* W, int ldw, int Cout, const float* Y,
                              const float* bn_save, int has_bn, int training, int act, float slope, float p_drop, uint64_t seed,
                              int n_groups, int rows_per_group, float* dX, int lddx, int dx_accumulate, float* dW, float* dbias, float* dgbias,
                              float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mlsp_stream_t st, const mlsp_defer_t* in,
@@ -509,7 +516,7 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
     if (in) {
         if (!defer_ok(in) || in->col + Cin > in->ld || M <= 32) return MLSP_ERR_ARG;
         xf_s = chain_xf(*in, 2, training);
-        if (defer_fusable(*in) && gemm_xf_supported(true, false, Cout, Cin, M, dZ, Cout, X, ldx, 2)) xf = &xf_s;
+        if (defer_fusable(*in) && gemm_xf_supported(cx, true, false, Cout, Cin, M, dZ, Cout, X, ldx, 2)) xf = &xf_s;
         else {
             float* Xa = w.take<float>((size_t)M * Cin);
             if (!w.ok()) return MLSP_ERR_WORKSPACE;
@@ -525,7 +532,7 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
     // from the row-panel sums of d' and the clouds' column sums of y (bn.hip launch_bn_dy_gbias)
     GemmDy dy_s = {Y, coef, Cout, 1}; const GemmDy* dy = nullptr;          // (the finalizers below fill the fourth coefficient row)
     if (has_bn && M > 32 && pre_stats && training && (!in || xf) && M % pre_parts == 0 &&
-        (!dX || gemm_dy_supported(false, false, M, Cin, Cout, dZ, Cout, W, ldw)) && gemm_dy_supported(true, false, Cout, Cin, M, dZ, Cout, X, ldx) &&
+        (!dX || gemm_dy_supported(cx, false, false, M, Cin, Cout, dZ, Cout, W, ldw)) && gemm_dy_supported(cx, true, false, Cout, Cin, M, dZ, Cout, X, ldx) &&
         (!dgbias || (rows_per_group >= 256 && rows_per_group % (M / pre_parts) == 0 && Cout % 4 == 0 && 256 % (Cout / 4) == 0 && Cout <= 1024)))
         dy = &dy_s;
     float* zb = (dbias && has_bn && training) ? dbias : nullptr;   // a bias in front of a batch-statistics BatchNorm: analytically zero gradient,
@@ -562,9 +569,9 @@ static int pointmlp_bwd_impl(const float* dZ, const float* X, int ldx, int M, in
         CHECK(launch_skinny_bwd_pair(st, g, Cout, W, ldw, X, ldx, dX, lddx, dW, M, Cin, Cout, dx_accumulate));
     } else {
     GemmOpts od = so; od.accumulate = dx_accumulate != 0; od.bs = bs; od.dy = dy;
-    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, g, Cout, W, ldw, dX, lddx, od));
+    if (dX) CHECK(launch_gemm(st, cx, false, false, M, Cin, Cout, g, Cout, W, ldw, dX, lddx, od));
     GemmOpts ow = so; ow.xf = xf; ow.dy = dy;
-    CHECK(launch_gemm(st, true, false, Cout, Cin, M, g, Cout, X, ldx, dW, Cin, ow));
+    CHECK(launch_gemm(st, cx, true, false, Cout, Cin, M, g, Cout, X, ldx, dW, Cin, ow));
     }
     if (dbias) {
         if (has_bn && training) {
@@ -589,8 +596,9 @@ int mlsp_pointmlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, int C
                           int n_groups, int rows_per_group, float* dX, int lddx, int dx_accumulate, float* dW, float* dbias, float* dgbias,
                           float* dgamma, float* dbeta, const double* pre_stats, int pre_parts, const float* group_ysum, int precision, void* ws,
                           size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
-    return pointmlp_bwd_impl(dZ, X, ldx, M, Cin, W, ldw, Cout, Y, bn_save, has_bn, training, act, slope, p_drop, seed, n_groups,
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
+    return pointmlp_bwd_impl(cx, dZ, X, ldx, M, Cin, W, ldw, Cout, Y, bn_save, has_bn, training, act, slope, p_drop, seed, n_groups,
                              rows_per_group, dX, lddx, dx_accumulate, dW, dbias, dgbias, dgamma, dbeta, ws, ws_bytes, st, nullptr, nullptr,
                              pre_stats, pre_parts, group_ysum);
 }
@@ -598,10 +606,10 @@ int mlsp_pointmlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, int C
 // Row panels the fused statistics pass of mlsp_pointmlp_bwd_chain_f32(in_stats != NULL) writes for this layer shape (its dgrad
 // dX [M][Cin] = dY [M][Cout] W): M / 128 when the dgrad runs on a kernel with that pass, else 0 (pass in_stats = NULL then).
 int mlsp_pointmlp_bwd_stats_parts(int M, int Cin, int Cout, int ldw, int lddx, int precision) {
-    if (precision < 0 || precision > 3) return 0;
-    GemmPrecisionScope prec_scope_(precision);
+    const CallCtx cx = CallCtx::query(precision);
+    if (!cx.ok()) return 0;
     const int t = thin_bs_parts(M, Cin, Cout);
-    return t ? t : gemm_bs_parts(M, Cin, Cout, Cout, ldw, lddx);
+    return t ? t : gemm_bs_parts(cx, M, Cin, Cout, Cout, ldw, lddx);
 }
 
 int mlsp_pointmlp_bwd_chain_f32(const float* dZ, const float* Xpre, int ldx, const mlsp_defer_t* in, int M, int Cin, const float* W, int ldw, int Cout, const float* Y,
@@ -609,9 +617,10 @@ int mlsp_pointmlp_bwd_chain_f32(const float* dZ, const float* Xpre, int ldx, con
                                 int n_groups, int rows_per_group, float* dX, int lddx, int dx_accumulate, float* dW, float* dbias,
                                 float* dgbias, float* dgamma, float* dbeta, double* in_stats, const double* pre_stats, int pre_parts,
                                 const float* group_ysum, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!in) return MLSP_ERR_ARG;
-    return pointmlp_bwd_impl(dZ, Xpre, ldx, M, Cin, W, ldw, Cout, Y, bn_save, has_bn, training, act, slope, p_drop, seed, n_groups,
+    return pointmlp_bwd_impl(cx, dZ, Xpre, ldx, M, Cin, W, ldw, Cout, Y, bn_save, has_bn, training, act, slope, p_drop, seed, n_groups,
                              rows_per_group, dX, lddx, dx_accumulate, dW, dbias, dgbias, dgamma, dbeta, ws, ws_bytes, st, in, in_stats,
                              pre_stats, pre_parts, group_ysum);
 }
@@ -624,19 +633,20 @@ int mlsp_pointmlp_segmax_fwd_f32(const float* X, int ldx, int M, int Cin, const 
                                  const float* gamma, const float* beta, float* run_mean, float* run_var, float momentum, float eps,
                                  int training, int act, float slope, int k, float* Y, float* out, float* ysel, uint8_t* argk, float* bn_save,
                                  int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!X || !W || !gamma || !beta || !Y || !out || !ysel || !argk || !bn_save || M <= 0 || Cin <= 0 || Cout <= 0 || ldx < Cin || ldw < Cin)
         return MLSP_ERR_ARG;
     if (k < 1 || k > 255 || M % k || Cout % 4) return MLSP_ERR_UNSUPPORTED;
     Workspace w(ws, ws_bytes);
-    const int fused_parts = training ? gemm_stat_parts(M, Cout, Cin) : 0;
+    const int fused_parts = training ? gemm_stat_parts(cx, M, Cout, Cin) : 0;
     int nparts = fused_parts ? fused_parts : bn_stat_parts(M);
     double* part = w.take<double>((size_t)nparts * 2 * Cout);
     GemmOpts o; o.bias = bias; o.stat_part = fused_parts ? part : nullptr;
     take_slab(w, o, gemm_slab_floats(M, Cout, Cin));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
-    CHECK(launch_gemm(st, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
+    CHECK(launch_gemm(st, cx, false, true, M, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     if (training) {
         if (!fused_parts) CHECK(launch_colstats(st, Y, M, Cout, Cout, part));
         CHECK(launch_bn_finalize(st, part, nparts, (double)M, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale, shift, mean, invstd));
@@ -651,7 +661,8 @@ int mlsp_pointmlp_segmax_bwd_f32(const float* dOut, const float* X, int ldx, int
                                  const float* ysel, const uint8_t* argk, const float* bn_save, int training, int act, float slope, int k,
                                  float* dX, int lddx, float* dW, float* dbias, float* dgamma, float* dbeta, int precision, void* ws, size_t ws_bytes,
                                  mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!dOut || !X || !W || !Y || !ysel || !argk || !bn_save || !dW || !dgamma || !dbeta || M <= 0 || Cin <= 0 || Cout <= 0 || ldx < Cin ||
         ldw < Cin) return MLSP_ERR_ARG;
     if (k < 1 || k > 255 || M % k || Cout % 4) return MLSP_ERR_UNSUPPORTED;
@@ -672,8 +683,8 @@ int mlsp_pointmlp_segmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     }
     CHECK(launch_bn_bwd_finalize(st, part, npr, (double)M, Cout, dgamma, dbeta, mean_dz, mean_dzy));
     CHECK(launch_segsel_bwd_apply(st, dOut, Y, ysel, argk, (size_t)M, k, Cout, bn_save, training ? mean_dz : nullptr, mean_dzy, act, slope, dY));
-    if (dX) CHECK(launch_gemm(st, false, false, M, Cin, Cout, dY, Cout, W, ldw, dX, lddx, so));
-    CHECK(launch_gemm(st, true, false, Cout, Cin, M, dY, Cout, X, ldx, dW, Cin, so));
+    if (dX) CHECK(launch_gemm(st, cx, false, false, M, Cin, Cout, dY, Cout, W, ldw, dX, lddx, so));
+    CHECK(launch_gemm(st, cx, true, false, Cout, Cin, M, dY, Cout, X, ldx, dW, Cin, so));
     if (dbias) {
         if (training) {                                        // a bias in front of a batch-statistics BatchNorm: analytically zero gradient
             hipError_t e = hipMemsetAsync(dbias, 0, (size_t)Cout * sizeof(float), st);
@@ -690,32 +701,36 @@ int mlsp_pointmlp_segmax_bwd_f32(const float* dOut, const float* X, int ldx, int
 // out_bf16 how Y, Z (and dZ, dY) are.  Weights, biases, BN parameters / statistics and every weight gradient stay fp32; products are
 // bf16 x bf16 with fp32 accumulation (v_mfma_f32_32x32x16_bf16).  BN layers with fused statistics only (interior GEMM tiles):
 // MLSP_ERR_UNSUPPORTED otherwise -- mlsp_pointmlp_mx_supported() tells the caller beforehand, which then keeps that layer in fp32.
-int mlsp_pointmlp_mx_supported(int M, int Cin, int Cout, int ldx, int x_bf16, int training, int precision) {
-    if (precision < 0 || precision > 3) return 0;
-    GemmPrecisionScope prec_scope_(precision);
+static int pointmlp_mx_supported(const CallCtx& cx, int M, int Cin, int Cout, int ldx, int x_bf16, int training) {
     if (M <= 32 || Cin % 32 || Cout % 128 || M % 128) return 0;
     if (x_bf16 ? (ldx % 8) : (ldx % 4)) return 0;
     if (Cout > 1024 || 256 % (Cout / 4)) return 0;
-    if (training && gemm_stat_parts(M, Cout, Cin) <= 0) return 0;
+    if (training && gemm_stat_parts(cx, M, Cout, Cin) <= 0) return 0;
     if (gemm_slab_floats(M, Cout, Cin) != 0 || gemm_slab_floats(M, Cin, Cout) != 0) return 0;      // forward / dgrad never split K here
     return 1;
+}
+
+int mlsp_pointmlp_mx_supported(int M, int Cin, int Cout, int ldx, int x_bf16, int training, int precision) {
+    const CallCtx cx = CallCtx::query(precision);
+    return cx.ok() ? pointmlp_mx_supported(cx, M, Cin, Cout, ldx, x_bf16, training) : 0;
 }
 
 int mlsp_pointmlp_fwd_mx(const void* X, int x_bf16, int ldx, int M, int Cin, const float* W, int ldw, int Cout, const float* bias,
                          const float* gbias, int rows_per_group, const float* gamma, const float* beta, float* run_mean,
                          float* run_var, float momentum, float eps, int training, int act, float slope, float p_drop, uint64_t seed,
                          void* Y, void* Z, int out_bf16, float* bn_save, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!X || !W || !Y || !Z || !gamma || !beta || !bn_save || ldw < Cin || ldx < Cin) return MLSP_ERR_ARG;
     if (p_drop < 0.f || p_drop >= 1.f) return MLSP_ERR_ARG;
-    if (!mlsp_pointmlp_mx_supported(M, Cin, Cout, ldx, x_bf16, training, precision)) return MLSP_ERR_UNSUPPORTED;
+    if (!pointmlp_mx_supported(cx, M, Cin, Cout, ldx, x_bf16, training)) return MLSP_ERR_UNSUPPORTED;
     Workspace w(ws, ws_bytes);
-    const int fused_parts = training ? gemm_stat_parts(M, Cout, Cin) : 0;
+    const int fused_parts = training ? gemm_stat_parts(cx, M, Cout, Cin) : 0;
     double* part = w.take<double>((size_t)(fused_parts ? fused_parts : 1) * 2 * Cout);
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
     float* scale = bn_save, *shift = bn_save + Cout, *mean = bn_save + 2 * Cout, *invstd = bn_save + 3 * Cout;
     GemmOpts o; o.bias = bias; o.gbias = gbias; o.rows_per_group = rows_per_group; o.stat_part = fused_parts ? part : nullptr;
-    CHECK(launch_gemm_mx(st, false, true, M, Cout, Cin, X, x_bf16, ldx, W, 0, ldw, Y, out_bf16, Cout, o));
+    CHECK(launch_gemm_mx(st, cx, false, true, M, Cout, Cin, X, x_bf16, ldx, W, 0, ldw, Y, out_bf16, Cout, o));
     if (training) {
         CHECK(launch_bn_finalize(st, part, fused_parts, (double)M, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale, shift,
                                  mean, invstd));
@@ -731,10 +746,11 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
                          const void* Y, int out_bf16, const float* bn_save, int training, int act, float slope, float p_drop,
                          uint64_t seed, int n_groups, int rows_per_group, void* dX, int lddx, int dx_accumulate, float* dW, float* dbias,
                          float* dgbias, float* dgamma, float* dbeta, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!dZ || !X || !W || !Y || !bn_save || !dW || !dgamma || !dbeta || ldw < Cin || ldx < Cin) return MLSP_ERR_ARG;
     if (dgbias && (n_groups <= 0 || rows_per_group <= 0 || (long)n_groups * rows_per_group != M)) return MLSP_ERR_ARG;
-    if (!mlsp_pointmlp_mx_supported(M, Cin, Cout, ldx, x_bf16, training, precision)) return MLSP_ERR_UNSUPPORTED;
+    if (!pointmlp_mx_supported(cx, M, Cin, Cout, ldx, x_bf16, training)) return MLSP_ERR_UNSUPPORTED;
     if (dbias && !training) return MLSP_ERR_UNSUPPORTED;
     Workspace w(ws, ws_bytes);
     void* dY = w.take<char>((size_t)M * Cout * (out_bf16 ? 2 : 4));
@@ -753,8 +769,8 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
     else CHECK(launch_bn_act_bwd(st, (const float*)dZ, (const float*)Y, (float*)dY, M, Cout, scale, shift, mean, invstd, training, act, slope,
                                  training ? p_drop : 0.f, seed, part, dgamma, dbeta, mean_dz, mean_dzy, dbias));
     GemmOpts od; od.accumulate = dx_accumulate != 0;
-    if (dX) CHECK(launch_gemm_mx(st, false, false, M, Cin, Cout, dY, out_bf16, Cout, W, 0, ldw, dX, x_bf16, lddx, od));
-    CHECK(launch_gemm_mx(st, true, false, Cout, Cin, M, dY, out_bf16, Cout, X, x_bf16, ldx, dW, 0, Cin, ow));
+    if (dX) CHECK(launch_gemm_mx(st, cx, false, false, M, Cin, Cout, dY, out_bf16, Cout, W, 0, ldw, dX, x_bf16, lddx, od));
+    CHECK(launch_gemm_mx(st, cx, true, false, Cout, Cin, M, dY, out_bf16, Cout, X, x_bf16, ldx, dW, 0, Cin, ow));
     if (dgbias) {
         if (out_bf16) CHECK(launch_colsum_groups_b16(st, dY, n_groups, rows_per_group, Cout, dgbias, gscratch));
         else CHECK(launch_colsum_groups(st, (const float*)dY, n_groups, rows_per_group, Cout, dgbias, gscratch));
@@ -764,32 +780,33 @@ int mlsp_pointmlp_bwd_mx(const void* dZ, const void* X, int x_bf16, int ldx, int
 
 // Panel height of the fused forward of pointmlp_colmax -- statistics AND the per-cloud column extreme out of the GEMM epilogue, Y never
 // written: the GEMM keeps K whole and every cloud is a whole number of its row panels --, or 0: Y is written and colsel_kernel reads it.
-// (under the caller's GemmPrecisionScope: the tile choice depends on the product mode)
-static int colmax_fused_panel_rows(int N, int P, int Cin, int Cout) {
-    const int prow = gemm_panel_rows(P, Cout, Cin);
-    return ((N % prow == 0) && gemm_stat_parts(P, Cout, Cin) > 0) ? prow : 0;
+// (the tile choice depends on the product mode)
+static int colmax_fused_panel_rows(const CallCtx& cx, int N, int P, int Cin, int Cout) {
+    const int prow = gemm_panel_rows(cx, P, Cout, Cin);
+    return ((N % prow == 0) && gemm_stat_parts(cx, P, Cout, Cin) > 0) ? prow : 0;
 }
 
 // Shape query: the row-panel height (64 or 128) mlsp_pointmlp_colmax_fwd_f32 takes its per-panel column extremes at for this shape and
 // product mode (N / rows panels per cloud), or 0 when that forward writes Y and selects in a pass of its own.
 int mlsp_pointmlp_colmax_panel_rows(int B, int N, int Cin, int Cout, int precision) {
-    if (precision < 0 || precision > 3 || B <= 0 || N <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    GemmPrecisionScope prec_scope_(precision);
-    return colmax_fused_panel_rows(N, B * N, Cin, Cout);
+    const CallCtx cx = CallCtx::query(precision);
+    if (!cx.ok() || B <= 0 || N <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    return colmax_fused_panel_rows(cx, N, B * N, Cin, Cout);
 }
 
 int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin, const float* W, int ldw, int Cout,
                                  const float* gamma, const float* beta, float* run_mean, float* run_var, float momentum, float eps,
                                  int training, int act, float slope, float* out, float* ysel, int32_t* arg, float* bn_save, int precision, void* ws,
                                  size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!X || !W || !gamma || !beta || !out || !ysel || !arg || !bn_save) return MLSP_ERR_ARG;
     if (B <= 0 || N <= 0 || Cin <= 0 || Cout <= 0 || ldx < Cin || ldw < Cin) return MLSP_ERR_ARG;
     const int P = B * N;
     Workspace w(ws, ws_bytes);
-    const int fused_parts = training ? gemm_stat_parts(P, Cout, Cin) : 0;
+    const int fused_parts = training ? gemm_stat_parts(cx, P, Cout, Cin) : 0;
     // fully fused path: statistics AND the per-cloud column extreme come out of the GEMM epilogue, Y is never written
-    const int prow = colmax_fused_panel_rows(N, P, Cin, Cout);             // 0: Y is written
+    const int prow = colmax_fused_panel_rows(cx, N, P, Cin, Cout);             // 0: Y is written
     const bool fuse_sel = prow > 0;
     float* Y = fuse_sel ? nullptr : w.take<float>((size_t)P * Cout);
     float* pv = fuse_sel ? w.take<float>((size_t)(P / prow) * Cout) : nullptr;      // (N % prow == 0: P / prow whole panels)
@@ -799,7 +816,7 @@ int mlsp_pointmlp_colmax_fwd_f32(const float* X, int ldx, int B, int N, int Cin,
     GemmOpts o; o.stat_part = fused_parts ? part : nullptr; o.sel_gamma = fuse_sel ? gamma : nullptr; o.sel_val = pv; o.sel_row = pr;
     take_slab(w, o, gemm_slab_floats(P, Cout, Cin));
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
-    CHECK(launch_gemm(st, false, true, P, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
+    CHECK(launch_gemm(st, cx, false, true, P, Cout, Cin, X, ldx, W, ldw, Y, Cout, o));
     if (training) {
         if (!fused_parts) CHECK(launch_colstats(st, Y, P, Cout, Cout, part));
         CHECK(launch_bn_finalize(st, part, nparts, (double)P, Cout, gamma, beta, run_mean, run_var, momentum, eps, bn_save,
@@ -821,7 +838,8 @@ int mlsp_pointmlp_colmax_bwd_f32(const float* dOut, const float* X, int ldx, int
                                  int Cout, const float* out, const float* ysel, const int32_t* arg, const float* bn_save,
                                  int training, int act, float slope, float* dX, int dx_accumulate, float* dW, float* dgamma, float* dbeta,
                                  int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     if (!dOut || !X || !W || !out || !ysel || !arg || !bn_save || !dW || !dgamma || !dbeta) return MLSP_ERR_ARG;
     if (B <= 0 || N <= 0 || Cin <= 0 || Cout <= 0 || ldx != Cin || ldw < Cin) return MLSP_ERR_ARG;
     const int P = B * N;
@@ -844,8 +862,8 @@ int mlsp_pointmlp_colmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     CHECK(launch_colmax_gather_rows(st, g, arg, X, ldx, B, N, Cout, Cin, S));
     if (training) {
         CHECK(launch_colsum(st, X, P, Cin, part, sx));
-        CHECK(launch_gemm(st, true, false, Cin, Cin, P, X, ldx, X, ldx, G, Cin, so));
-        CHECK(launch_gemm(st, false, false, Cout, Cin, Cin, W, ldw, G, Cin, WG, Cin, so));
+        CHECK(launch_gemm(st, cx, true, false, Cin, Cin, P, X, ldx, X, ldx, G, Cin, so));
+        CHECK(launch_gemm(st, cx, false, false, Cout, Cin, Cin, W, ldw, G, Cin, WG, Cin, so));
         CHECK(launch_colmax_dw(st, S, WG, sx, coef, bn_save, Cout, Cin, dW));
     } else {
         hipError_t e = hipMemcpyAsync(dW, S, (size_t)Cout * Cin * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -854,9 +872,9 @@ int mlsp_pointmlp_colmax_bwd_f32(const float* dOut, const float* X, int ldx, int
     if (dX) {
         if (training) {
             CHECK(launch_wt_vec_neg_scale_rows(st, W, ldw, coef + 2 * Cout, coef + 3 * Cout, Cout, Cin, negr, Wb));    // negr; Wb = -Bc * W
-            CHECK(launch_gemm(st, true, false, Cin, Cin, Cout, Wb, Cin, W, ldw, Mneg, Cin, so));
+            CHECK(launch_gemm(st, cx, true, false, Cin, Cin, Cout, Wb, Cin, W, ldw, Mneg, Cin, so));
             GemmOpts od = so; od.bias = negr; od.accumulate = dx_accumulate != 0;
-            CHECK(launch_gemm(st, false, false, P, Cin, Cin, X, ldx, Mneg, Cin, dX, Cin, od));
+            CHECK(launch_gemm(st, cx, false, false, P, Cin, Cin, X, ldx, Mneg, Cin, dX, Cin, od));
         } else if (!dx_accumulate) {
             hipError_t e = hipMemsetAsync(dX, 0, (size_t)P * Cin * sizeof(float), st);
             if (e != hipSuccess) return (int)e;

@@ -25,21 +25,10 @@ enum { MLSP_PROF_GEMM = 0, MLSP_PROF_KNN_C3, MLSP_PROF_KNN_C64, MLSP_PROF_KNN_C1
        MLSP_PROF_TNET_BWD, MLSP_PROF_GEMM_SPLIT /* the subset of class 0 that ran on gemm_split_kernel */, MLSP_PROF_NCLS };
 
 // Products of the GEMM family are a PER-CALL argument of every entry point that reaches it (include/mlsp_hip.h `precision`): 0 f32 MFMA,
-// 1 bf16-rounded operands, 2 fp32-accurate six-product bf16 split.  An entry point opens a GemmPrecisionScope from its argument; the
-// launch helpers below it read gemm_precision_mode().  The value lives in a thread-local for the duration of that one call (restored on
-// exit, so nested / concurrent calls on any threads never see each other's mode): nothing outlives a call, the library keeps no switch.
-#define MLSP_AMAX_TAIL_BYTES 65536
-struct GemmPrecisionScope {
-    int prev;
-    void* prev_tail; void* prev_offered; int prev_noffered;
-    // ws / ws_bytes: the call's workspace -- its last MLSP_AMAX_TAIL_BYTES hold the operand-magnitude partials of the two-piece f16 products
-    // (mode 3; gemm.hip amax_partials); Workspace below never hands that tail out
-    explicit GemmPrecisionScope(int mode, void* ws = nullptr, size_t ws_bytes = 0);
-    ~GemmPrecisionScope();
-    GemmPrecisionScope(const GemmPrecisionScope&) = delete;
-    GemmPrecisionScope& operator=(const GemmPrecisionScope&) = delete;
-};
-#define PREC_SCOPE(mode_) if ((mode_) < 0 || (mode_) > 3) return MLSP_ERR_ARG; GemmPrecisionScope prec_scope_(mode_, ws, ws_bytes)
+// 1 bf16-rounded operands, 2 fp32-accurate six-product bf16 split, 3 the same accuracy on two f16 pieces / three products.  An entry point
+// builds a CallCtx (callctx.h) from its arguments and hands it down; the launch helpers below it take it as a parameter (the dispatch sees
+// mode 3 as 2 plus a flag).  Nothing outlives a call, the library keeps no switch.
+#include "callctx.h"
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -47,7 +36,7 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 struct Workspace {
     char* base;
     size_t size, off;
-    Workspace(void* p, size_t n) : base((char*)p), size(n > MLSP_AMAX_TAIL_BYTES ? n - MLSP_AMAX_TAIL_BYTES : 0), off(0) {}     // (the tail: see PREC_SCOPE)
+    Workspace(void* p, size_t n) : base((char*)p), size(n > MLSP_AMAX_TAIL_BYTES ? n - MLSP_AMAX_TAIL_BYTES : 0), off(0) {}     // (the tail: see callctx.h)
     template <typename T>
     T* take(size_t count) {
         size_t bytes = align_up(count * sizeof(T), 256);

@@ -20,7 +20,7 @@
 #define EDGE_PTS_PER_WAVE 16
 
 // Wd = [Wa ; Wb - Wa]  ([2*Cout, C]) from the reference-layout weight W [Cout, 2C].  amax (nullable, <= 256 workgroups): the 256 partial
-// maxima of |Wd| for the f16x3 product that reads it (gemm.hip amax_reserve) -- one per workgroup, the rest zero.
+// maxima of |Wd| for the f16x3 product that reads it (callctx.h CallCtx::reserve) -- one per workgroup, the rest zero.
 __global__ __launch_bounds__(256) void build_wd_kernel(const float* __restrict__ W, int Cout, int C, float* __restrict__ Wd, float* __restrict__ amax) {
     __shared__ float sm[4];
     int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(NT, 4) void edge_reduce_wide_kernel(const float* __
     }
 }
 
-// By-product bound of duv for the f16x3 products that read it (gemm.hip amax_reserve): every WORKGROUP raises one of 256 partial maxima
+// By-product bound of duv for the f16x3 products that read it (callctx.h CallCtx::reserve): every WORKGROUP raises one of 256 partial maxima
 // (non-negative floats order like their bit patterns; the slot was zeroed by edge_bwd_reduce_vec_kernel, earlier on the stream).  One
 // atomic per workgroup: one per wave -- 32768 of them on 256 addresses -- cost the gather 15 us per launch.  Every thread of the
 // workgroup must call it (barrier inside).

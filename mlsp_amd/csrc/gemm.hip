@@ -1216,23 +1216,10 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmArgs p) {
     gemm_epilogue<WM, true, false, (!TA && !TB && XF == 0 && !DY) || (!TA && !TB && DY)>(p, acc, smem, tm, m0, n0, split, tid, l31, h, wm, wn);
 }
 
-// the calling entry point's `precision` argument for the duration of that call (common.h GemmPrecisionScope): 0: fp32 MFMA (exact fp32
-// products); 1: bf16 operands, fp32 accumulation; 2: fp32-accurate six-product bf16 split (gemm_split_kernel)
-// 3 (MLSP_PREC_F16X3): as 2, with two f16 pieces / three products on the launches gemm_split_kernel<.., NPC = 2> covers (tl_split_half); the
-// rest of the dispatch sees mode 2.
-static thread_local int tl_call_precision = 0;
-static thread_local bool tl_split_half = false;
-int gemm_precision_mode() { return tl_call_precision; }
-
 // ---- operand magnitudes for the two-piece f16 products (mode 3) ------------------------------------------------------------------
 // AMAX_PARTS partial maxima of |X| per operand, written by ONE streaming launch (no atomics, nothing to initialise) into a slot of the
-// call's workspace tail (MLSP_AMAX_TAIL_BYTES, common.h); every workgroup of the consuming GEMM reduces the partials in its prologue.
-// Within one API call an operand is measured once (thread-local cache keyed by pointer and shape: dgrad and weight gradient share dY);
-// the cache and the slot ring die with the call (GemmPrecisionScope).
-#define AMAX_PARTS 256
-#define AMAX_SLOTS ((MLSP_AMAX_TAIL_BYTES - 256) / (AMAX_PARTS * 4))
-struct AmaxOp { const float* X; long rows; int cols, ld; float* out; };
-struct AmaxArgs { AmaxOp op[5]; };
+// call's workspace tail or an entry of the caller's table (callctx.h: the call's CallCtx says where, and measures an operand once per
+// call); every workgroup of the consuming GEMM reduces the partials in its prologue.
 __global__ __launch_bounds__(512) void amax_partials_kernel(AmaxArgs a) {
     const AmaxOp o = a.op[blockIdx.x / AMAX_PARTS];
     const int b = blockIdx.x % AMAX_PARTS, tid = threadIdx.x;
@@ -1264,115 +1251,15 @@ __global__ __launch_bounds__(512) void amax_partials_kernel(AmaxArgs a) {
     __syncthreads();
     if (tid == 0) o.out[b] = fmaxf(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])), fmaxf(fmaxf(sm[4], sm[5]), fmaxf(sm[6], sm[7])));
 }
-static thread_local struct AmaxScratch {
-    float* base = nullptr;          // the workspace tail of the current API call (null: none, mode 3 falls back to the bf16 pieces)
-    int next = 0, ncache = 0;
-    struct { const float* X; long rows; int cols, ld; float* out; } cache[AMAX_SLOTS];
-    // caller-owned bounds of the current call (mlsp_operand_bounds_next): an operand that matches an entry uses the entry's partials --
-    // as they are when `valid`, else this call measures INTO them and sets `valid` (the caller keeps them for later calls: the same
-    // activation read by several layers, a weight read again by its layer's backward)
-    mlsp_bound_t* offered = nullptr; int noffered = 0;
-    mlsp_bound_t* pending = nullptr; int npending = 0;     // set by mlsp_operand_bounds_next, adopted by the next GemmPrecisionScope
-} tl_amax;
+// the ONE out-of-band argument of the ABI: armed here for the next entry point this thread calls, emptied by that call's CallCtx (callctx.h)
 extern "C" int mlsp_operand_bounds_next(mlsp_bound_t* tab, int n) {
     if (n < 0 || (n > 0 && !tab)) return MLSP_ERR_ARG;
-    tl_amax.pending = n ? tab : nullptr; tl_amax.npending = n;
+    tl_pending_bounds.tab = n ? tab : nullptr; tl_pending_bounds.n = n;
     return MLSP_OK;
-}
-// queue of operands to measure with the next launch (launch_gemm batches A and B -- and the groups' B operands -- into one launch)
-struct AmaxBatch { AmaxArgs args; int n = 0; };
-static float* amax_take_slot(const float* X, long rows, int cols, int ld) {
-    const int slot = tl_amax.next;
-    tl_amax.next = (tl_amax.next + 1) % AMAX_SLOTS;
-    float* out = tl_amax.base + (size_t)slot * AMAX_PARTS;
-    int k = 0;                                                   // the slot's previous tenant leaves the cache
-    for (int i = 0; i < tl_amax.ncache; ++i) if (tl_amax.cache[i].out != out) tl_amax.cache[k++] = tl_amax.cache[i];
-    tl_amax.ncache = k;
-    tl_amax.cache[tl_amax.ncache++] = {X, rows, cols, ld, out};
-    return out;
-}
-// -> the partials of X [rows][cols] (pitch ld), measured now (queued into `batch`) or earlier in this API call; null: cannot (no tail,
-// unaligned, the batch is full)
-static float* amax_get(AmaxBatch& batch, const float* X, long rows, int cols, int ld, int* n_out) {
-    *n_out = AMAX_PARTS;
-    if (!tl_amax.base || rows <= 0 || cols <= 0 || (cols & 3) || (ld & 3) || (((uintptr_t)X) & 15)) return nullptr;
-    for (int i = 0; i < tl_amax.noffered; ++i) {
-        mlsp_bound_t& o = tl_amax.offered[i];
-        if (o.ptr != X || o.rows != rows || o.cols != cols || o.ld != ld || !o.partials || o.n < 0 || o.n > 4096) continue;
-        if (!o.valid) {
-            if (o.n != 0 && o.n != AMAX_PARTS) continue;            // (an unfilled OUTPUT-bounds buffer of another size: not ours to measure into)
-            if (batch.n >= 5) return nullptr;
-            batch.args.op[batch.n++] = {X, rows, cols, ld, o.partials};
-            o.valid = 1; o.n = AMAX_PARTS;
-        }
-        *n_out = o.n ? o.n : AMAX_PARTS;
-        return o.partials;
-    }
-    for (int i = 0; i < tl_amax.ncache; ++i) {
-        const auto& c = tl_amax.cache[i];
-        if (c.X == X && c.rows == rows && c.cols == cols && c.ld == ld) return c.out;
-    }
-    if (batch.n >= 5) return nullptr;
-    float* out = amax_take_slot(X, rows, cols, ld);
-    batch.args.op[batch.n++] = {X, rows, cols, ld, out};
-    return out;
-}
-// Is a bound of X at hand (a valid entry of the caller's table, or measured / produced earlier in this API call)?  No side effects.
-static bool amax_at_hand(const float* X, long rows, int cols, int ld) {
-    for (int i = 0; i < tl_amax.noffered; ++i) {
-        const mlsp_bound_t& o = tl_amax.offered[i];
-        if (o.ptr == X && o.rows == rows && o.cols == cols && o.ld == ld && o.partials && o.valid && o.n > 0 && o.n <= 4096) return true;
-    }
-    for (int i = 0; i < tl_amax.ncache; ++i) {
-        const auto& c = tl_amax.cache[i];
-        if (c.X == X && c.rows == rows && c.cols == cols && c.ld == ld) return true;
-    }
-    return false;
-}
-// A slot for the partial maxima of X, FILLED BY THE CALLER's own kernels (the passes that write X, e.g. edge.hip edge_amax_raise) before
-// the product that reads X is launched in this same API call: that product finds the slot like a measured one (an entry of the caller's
-// table for X is filled instead and marked valid: the caller hands it to later calls).  null: no f16x3 scope / X is not an operand the
-// products would look up / the caller's entry is valid already.
-float* amax_reserve(const float* X, long rows, int cols, int ld) {
-    if (!tl_amax.base || !tl_split_half || rows <= 0 || cols <= 0 || (cols & 3) || (ld & 3) || (((uintptr_t)X) & 15)) return nullptr;
-    for (int i = 0; i < tl_amax.noffered; ++i) {                 // the caller's own entry for X: filled there (and handed on by the caller), or already valid
-        mlsp_bound_t& o = tl_amax.offered[i];
-        if (o.ptr != X || o.rows != rows || o.cols != cols || o.ld != ld) continue;
-        if (!o.partials || o.valid || (o.n != 0 && o.n != AMAX_PARTS)) return nullptr;
-        o.valid = 1; o.n = AMAX_PARTS;
-        return o.partials;
-    }
-    return amax_take_slot(X, rows, cols, ld);
-}
-// An entry of the caller's table that describes an OUTPUT of the current call (same pointer / shape, valid == 0, room for `need` floats):
-// the call fills its partials with a bound of what it writes -- e.g. the per-channel analytic bound of a BatchNorm'd layer -- and the
-// caller hands them to the layers that read the tensor.  -> the partials (entry marked valid, n = need), or null.
-float* amax_offered_output(const float* out, long rows, int cols, int ld, int need) {
-    for (int i = 0; i < tl_amax.noffered; ++i) {
-        mlsp_bound_t& o = tl_amax.offered[i];
-        if (o.ptr != out || o.rows != rows || o.cols != cols || o.ld != ld || !o.partials || o.valid || o.n < need) continue;
-        o.valid = 1; o.n = need;
-        return o.partials;
-    }
-    return nullptr;
 }
 static void amax_flush(hipStream_t st, AmaxBatch& batch) {
     if (batch.n) hipLaunchKernelGGL(amax_partials_kernel, dim3(batch.n * AMAX_PARTS), dim3(512), 0, st, batch.args);
     batch.n = 0;
-}
-GemmPrecisionScope::GemmPrecisionScope(int mode, void* ws, size_t ws_bytes) : prev(tl_call_precision | (tl_split_half ? 4 : 0)), prev_tail(tl_amax.base) {
-    tl_split_half = mode == 3; tl_call_precision = mode == 3 ? 2 : mode;
-    tl_amax.base = (mode == 3 && ws && ws_bytes >= 2 * MLSP_AMAX_TAIL_BYTES) ? (float*)((char*)ws + align_up(ws_bytes - MLSP_AMAX_TAIL_BYTES, 256)) : nullptr;
-    tl_amax.next = tl_amax.ncache = 0;
-    // the caller's bounds table is consumed by the OUTERMOST scope of the call (a nested scope -- an entry point asking one of the
-    // shape queries -- leaves it, and the outer scope's measuring state, alone)
-    prev_offered = tl_amax.offered; prev_noffered = tl_amax.noffered;
-    if (tl_amax.pending) { tl_amax.offered = tl_amax.pending; tl_amax.noffered = tl_amax.npending; tl_amax.pending = nullptr; tl_amax.npending = 0; }
-}
-GemmPrecisionScope::~GemmPrecisionScope() {
-    tl_call_precision = prev & 3; tl_split_half = (prev & 4) != 0;
-    tl_amax.base = (float*)prev_tail; tl_amax.next = tl_amax.ncache = 0;
-    tl_amax.offered = (mlsp_bound_t*)prev_offered; tl_amax.noffered = prev_noffered;
 }
 
 // sum the split-K slabs (fixed order -> bitwise reproducible) and apply the epilogue
@@ -1550,18 +1437,18 @@ static int gemm_pick_split(int M, int N, int K) {
 static bool gemm_split_pays(int M, int N, int ktiles) {
     return ktiles >= 8 || (ktiles >= 4 && (N >= 256 || M >= 16384));
 }
-static int gemm_pick_bm(int M, int N, int K) {
+static int gemm_pick_bm(const CallCtx& cx, int M, int N, int K) {
     long tiles128 = (long)((M + 127) / 128) * ((N + BN - 1) / BN);
     // the split kernel amortises its operand split over the tile: 128 rows unless the grid would not fill the 512 workgroup slots
-    const long few = (tl_call_precision == 2 && gemm_split_pays(M, N, (K + BK - 1) / BK)) ? 512 : 1536;
+    const long few = (cx.mode() == 2 && gemm_split_pays(M, N, (K + BK - 1) / BK)) ? 512 : 1536;
     return (gemm_pick_split(M, N, K) == 1 && tiles128 < few && M >= 256) ? 64 : 128;
 }
-int gemm_stat_parts(int M, int N, int K) {
+int gemm_stat_parts(const CallCtx& cx, int M, int N, int K) {
     if (gemm_pick_split(M, N, K) != 1) return 0;
-    int bm = gemm_pick_bm(M, N, K);
+    int bm = gemm_pick_bm(cx, M, N, K);
     return (M + bm - 1) / bm;
 }
-int gemm_panel_rows(int M, int N, int K) { return gemm_pick_bm(M, N, K); }
+int gemm_panel_rows(const CallCtx& cx, int M, int N, int K) { return gemm_pick_bm(cx, M, N, K); }
 
 // A 64 x 64 weight gradient over many rows (dW = dY^T X of a 64 -> 64 layer over the edges of a set-abstraction level): neither the 128-row
 // tile kernels (a quarter of the tile used, predicated path) nor the N = 64 kernel (M % 128) fit it.  With contiguous operands two
@@ -1713,48 +1600,48 @@ extern "C" int mlsp_profile_split_kinds(double* out) {
 // 16-byte loads, fp32 operands, the MFMA tile kernels (not the thin / skinny / N = 64 ones).
 // (mode 2: gemm_split_kernel<.., XF, XD> where the split kernel pays, the fp32 transform kernels on the short-K launches: exact fp32
 // products either way.  On the split kernel the A-side transform keeps the scale / shift of a workgroup's K range in LDS: <= SX_XF_KMAX.)
-bool gemm_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which) {
-    if (tl_call_precision == 1) return false;
+bool gemm_xf_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which) {
+    if (cx.mode() == 1) return false;
     if (thin_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, which)) return true;       // the streaming kernels of thin.hip transform too
     if (which == 1 ? ta : !(ta && !tb)) return false;
     if (M <= 32 || N < 32 || K < 32 || (ta && !tb && K <= 32)) return false;
     const bool vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0) && (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
     int ns = gemm_pick_split(M, N, K);
-    const int bm = (ns == 1) ? gemm_pick_bm(M, N, K) : 128;
+    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
     const int ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
-    if (which == 1 && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && kts * BK > SX_XF_KMAX) return false;
+    if (which == 1 && cx.mode() == 2 && gemm_split_pays(M, N, kts) && kts * BK > SX_XF_KMAX) return false;
     return vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && (long)(ta ? M : K) * lda * 4 < (1L << 30) && (long)K * ldb * 4 < (1L << 30);
 }
 
 // Row panels (of 128 rows) a dgrad dX [M][N] = dY [M][K] W with the fused statistics pass (GemmBs) writes partial sums for; 0: this
 // shape does not take the fused pass (the caller runs the streaming reduction instead).  Split kernel, 128-row interior tiles, one K pass.
-int gemm_bs_parts(int M, int N, int K, int lda, int ldb, int ldc) {
-    if (tl_call_precision != 2 || M % 128 || N % BN || K % BK || lda % 4 || ldb % 4 || ldc % 4) return 0;
-    if (gemm_pick_split(M, N, K) != 1 || gemm_pick_bm(M, N, K) != 128 || !gemm_split_pays(M, N, K / BK)) return 0;
+int gemm_bs_parts(const CallCtx& cx, int M, int N, int K, int lda, int ldb, int ldc) {
+    if (cx.mode() != 2 || M % 128 || N % BN || K % BK || lda % 4 || ldb % 4 || ldc % 4) return 0;
+    if (gemm_pick_split(M, N, K) != 1 || gemm_pick_bm(cx, M, N, K) != 128 || !gemm_split_pays(M, N, K / BK)) return 0;
     return M / 128;
 }
 
 // Can the layer's dgrad (ta = tb = false: dX [M][N] = dY [M][K] W) / weight gradient (ta, !tb: dW [M][N] = dY^T [K][M] X [K][N]) form dY from
 // (d', y) in its A operand loads (GemmDy)?  gemm_split_kernel only: interior tiles, 16-byte loads, the dgrad's K range within SX_XF_KMAX.
-bool gemm_dy_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
-    if (tl_call_precision != 2 || tb) return false;
+bool gemm_dy_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
+    if (cx.mode() != 2 || tb) return false;
     if (M <= 32 || N < 32 || K <= 32) return false;
     const bool vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0) && (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
     const int ns = gemm_pick_split(M, N, K);
-    const int bm = (ns == 1) ? gemm_pick_bm(M, N, K) : 128;
+    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
     const int ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
     if (!gemm_split_pays(M, N, kts) || (!ta && kts * BK > SX_XF_KMAX)) return false;
     return vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && (long)(ta ? K : M) * lda * 4 < (1L << 30) && (long)K * ldb * 4 < (1L << 30);
 }
 
 // will a transform launch of this shape run on gemm_split_kernel (the only kernel that transforms inside a block-diagonal launch)?
-bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which) {
-    if (tl_call_precision != 2) return false;
+bool gemm_xf_on_split(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, int which) {
+    if (cx.mode() != 2) return false;
     const int ns = gemm_pick_split(M, N, K), ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
     return gemm_split_pays(M, N, kts) && (which != 1 || kts * BK <= SX_XF_KMAX);
 }
 
-int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B,
+int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B,
                 int ldb, float* C, int ldc, const GemmOpts& o) {
     const float* const bias = o.bias; const float* const gbias = o.gbias; const int rows_per_group = o.rows_per_group;
     float* const slab = o.slab; const size_t slab_floats = o.slab_floats; double* const stat_part = o.stat_part; const int stat_ld = o.stat_ld;
@@ -1767,18 +1654,18 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     // stat_part points at this slice's first column of the [panels][2][stat_ld] partial rows
     if (M <= 0 || N <= 0 || K <= 0 || !A || !B || (!C && !sel_gamma)) return MLSP_ERR_ARG;
     // one tiny dimension (3 coordinates, 3 / 16 outputs): streaming VALU kernels priced against HBM, not MFMA tiles (thin.hip)
-    if (grp && (grp->G < 2 || grp->G > 4 || sel_gamma || gbias || tl_call_precision == 1 || (ta && tb))) return MLSP_ERR_UNSUPPORTED;
+    if (grp && (grp->G < 2 || grp->G > 4 || sel_gamma || gbias || cx.mode() == 1 || (ta && tb))) return MLSP_ERR_UNSUPPORTED;
     // a transform in a block-diagonal launch: split kernel only; the dropout stream is indexed in 32 bits per aligned quad
     if (xf && ((xf->ld & 3) || (xf->col & 3) || (((uintptr_t)xf->scale | (uintptr_t)xf->shift) & 15) || (double)(xf->which == 1 ? M : K) * xf->ld >= 17179869184.0))
         return MLSP_ERR_UNSUPPORTED;
     if (dy && (!dy->y || !dy->coef || (dy->cld & 3) || (((uintptr_t)dy->y | (uintptr_t)dy->coef) & 15) || gbias || sel_gamma || stat_part ||
-               (xf && xf->which != 2) || !gemm_dy_supported(ta, tb, M, N, K, A, lda, B, ldb)))
+               (xf && xf->which != 2) || !gemm_dy_supported(cx, ta, tb, M, N, K, A, lda, B, ldb)))
         return MLSP_ERR_UNSUPPORTED;                                         // nothing launched: the caller runs the streaming apply pass
-    if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && (!xf || tl_call_precision != 1)) {
+    if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && (!xf || cx.mode() != 1)) {
         const int rc = launch_thin_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, o);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
-    if (xf && !gemm_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, xf->which)) return MLSP_ERR_UNSUPPORTED;   // nothing launched: caller materialises
+    if (xf && !gemm_xf_supported(cx, ta, tb, M, N, K, A, lda, B, ldb, xf->which)) return MLSP_ERR_UNSUPPORTED;   // nothing launched: caller materialises
     if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && !xf && !bs && !bias && C && gemm_fold64(ta, tb, M, N, K, lda, ldb) &&
         (((uintptr_t)A | (uintptr_t)B) & 15) == 0) {
         const size_t inner = gemm_slab_floats(128, 128, K / 2);
@@ -1786,7 +1673,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
             float* C2 = slab + inner;
             const size_t used0 = g_prof.used;
             GemmOpts oi; oi.slab = slab; oi.slab_floats = inner;      // (C2 is not the caller's C: no unfold_dw)
-            const int rc = launch_gemm(st, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, oi);
+            const int rc = launch_gemm(st, cx, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, oi);
             if (rc != MLSP_OK) return rc;
             if (g_prof.used == used0 + 1) {              // the profiler prices the ALGORITHMIC contraction (64 x 64 x K), not the folded one
                 auto& r = g_prof.rec[used0];
@@ -1819,7 +1706,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     p.bs_y = nullptr; p.bs_ldy = 0; p.bs_bn = nullptr; p.bs_bnld = 0; p.bs_slope = 1.f; p.bs_thresh = 0; p.bs_ik = 1.f; p.bs_xH = 0; p.bs_ld4 = 0; p.bs_col = 0;
     if (bs) {
         if (ta || tb || xf || bias || gbias || accumulate || stat_part || sel_gamma || !bs->y || !bs->bn || !bs->part || (bs->ld & 3) || (bs->col & 3) ||
-            gemm_bs_parts(M, N, K, lda, ldb, ldc) == 0 || (double)M * bs->ld >= 17179869184.0)
+            gemm_bs_parts(cx, M, N, K, lda, ldb, ldc) == 0 || (double)M * bs->ld >= 17179869184.0)
             return MLSP_ERR_UNSUPPORTED;
         p.bs_y = bs->y; p.bs_ldy = bs->ldy; p.bs_bn = bs->bn; p.bs_bnld = bs->bnld;
         p.bs_slope = bs->act == 0 ? 1.f : bs->act == 1 ? 0.f : bs->slope; p.bs_thresh = bs->thresh; p.bs_ik = bs->inv_keep;
@@ -1837,7 +1724,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     int ktiles = (K + BK - 1) / BK;
     int kts = (ktiles + ns - 1) / ns;
     ns = (ktiles + kts - 1) / kts;
-    const int bm = (ns == 1) ? gemm_pick_bm(M, N, K) : 128;
+    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
     p.ntm = (M + bm - 1) / bm; p.ntn = (N + BN - 1) / BN;
     p.nsplit = ns; p.ksplit = kts * BK;
     p.a_vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0);
@@ -1857,18 +1744,18 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     if (grp) {
         const int per = (grp->mode == 1 ? N : M) / grp->G;                  // columns (mode 1) / rows (mode 2) of one group
         const int tile = grp->mode == 1 ? BN : bm;
-        bool ok = fast && tl_call_precision != 1 && (grp->mode == 1 || grp->mode == 2) && per * grp->G == (grp->mode == 1 ? N : M) && per % tile == 0;
+        bool ok = fast && cx.mode() != 1 && (grp->mode == 1 || grp->mode == 2) && per * grp->G == (grp->mode == 1 ? N : M) && per % tile == 0;
         for (int g = 0; g < grp->G && ok && grp->mode == 1; ++g) ok = grp->Bg[g] && (((uintptr_t)grp->Bg[g] & 15) == 0);
         if (!ok) return MLSP_ERR_UNSUPPORTED;
         p.gmode = grp->mode; p.gtiles = per / tile; p.a_gs = grp->a_gs; p.b_gs = grp->b_gs;
         for (int g = 0; g < 4; ++g) p.Bg[g] = grp->mode == 1 ? grp->Bg[g < grp->G ? g : 0] : B;
     }
-    const bool xf_split = xf && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && (xf->which != 1 || kts * BK <= SX_XF_KMAX);
+    const bool xf_split = xf && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && (xf->which != 1 || kts * BK <= SX_XF_KMAX);
     if (grp && xf && !xf_split) return MLSP_ERR_UNSUPPORTED;             // (the fp32 transform kernels take no groups: nothing launched)
     // split-K launches of gemm_split_kernel with few row panels (weight gradients): XCD-grouped (split, panel) order, see the kernel
-    const bool xcd2 = !p.xcd_map && ns > 1 && p.ntn > 1 && (p.ntm * ns) % 8 == 0 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) &&
+    const bool xcd2 = !p.xcd_map && ns > 1 && p.ntn > 1 && (p.ntm * ns) % 8 == 0 && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) &&
            (!xf || xf_split);
-    const bool xcd3 = !p.xcd_map && ns > 1 && ns % 8 == 0 && p.ntm > 1 && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && (!xf || xf_split);
+    const bool xcd3 = !p.xcd_map && ns > 1 && ns % 8 == 0 && p.ntm > 1 && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && (!xf || xf_split);
     if (xcd3) { p.xcd_map = 3; grid = dim3(p.ntm * p.ntn * ns, 1); }       // (all tiles of a split on one XCD: see the kernel)
     else if (xcd2) { p.xcd_map = 2; grid = dim3(p.ntm * p.ntn * ns, 1); }
     // (mode 1, N = 64: the bf16 kernel's tiles are 128 columns wide, so these launches used to fall to the bounds-checked f32 kernel at half-empty
@@ -1879,7 +1766,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
     // they lie in memory (measured by ONE streaming launch here, or earlier in this API call), the analytic bound for a transformed one
     // (batch statistics at hand).  Anything missing: the three-piece bf16 products (same kernel family, same accuracy class).
     bool half = false;
-    if (tl_split_half && tl_amax.base && fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split)) {
+    if (cx.split_half() && cx.has_tail() && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split)) {
         AmaxBatch batch;
         bool ok = true;
         // Does MEASURING what is not at hand pay?  The three-product kernel saves about a third of the six-product launch (~150 TF on
@@ -1888,7 +1775,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         // the pass against 70 on six products; configs[3] 3.58 -> 3.46 ms) and stay on the six products unless their bounds are free.
         {
             double mbytes = 0.0;
-            auto need = [&](const float* X, long rows, int cols, int ld) { if (!amax_at_hand(X, rows, cols, ld)) mbytes += (double)rows * cols * 4.0; };
+            auto need = [&](const float* X, long rows, int cols, int ld) { if (!cx.at_hand(X, rows, cols, ld)) mbytes += (double)rows * cols * 4.0; };
             if (!(xf && xf->which == 1) && !(dy && dy->amax))
                 need(A, ta ? K : M, (ta ? M : K) + ((grp && grp->mode == 1) ? (int)((grp->G - 1) * grp->a_gs) : 0), lda);
             if (xf && xf->which == 2) { }
@@ -1902,16 +1789,16 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         else if (dy && dy->amax) { /* bound from the coefficient rows (max |d'| per channel, left by the consumers' dgrads): nothing to measure */ }
         else {
             const int acols = (ta ? M : K) + ((grp && grp->mode == 1) ? (int)((grp->G - 1) * grp->a_gs) : 0);
-            p.a_amax = amax_get(batch, A, ta ? K : M, acols, lda, &p.a_amax_n);
+            p.a_amax = cx.get(batch, A, ta ? K : M, acols, lda, &p.a_amax_n);
             ok = p.a_amax != nullptr;
         }
         if (!ok) { }
         else if (xf && xf->which == 2) ok = ok && xf->mean && xf->invstd;
         else if (grp && grp->mode == 1) {
-            for (int g = 0; g < grp->G && ok; ++g) { p.b_amax[g] = amax_get(batch, grp->Bg[g], tb ? N / grp->G : K, tb ? K : N / grp->G, ldb, &p.b_amax_n[g]); ok = p.b_amax[g] != nullptr; }
+            for (int g = 0; g < grp->G && ok; ++g) { p.b_amax[g] = cx.get(batch, grp->Bg[g], tb ? N / grp->G : K, tb ? K : N / grp->G, ldb, &p.b_amax_n[g]); ok = p.b_amax[g] != nullptr; }
         } else {
             const int bcols = (tb ? K : N) + ((grp && grp->mode == 2) ? (int)((grp->G - 1) * grp->b_gs) : 0);
-            p.b_amax[0] = amax_get(batch, B, tb ? N : K, bcols, ldb, &p.b_amax_n[0]);
+            p.b_amax[0] = cx.get(batch, B, tb ? N : K, bcols, ldb, &p.b_amax_n[0]);
             ok = ok && p.b_amax[0] != nullptr;
         }
         amax_flush(st, batch);                 // (whatever was queued is in the cache: measure it even if this launch ends up on the bf16 pieces)
@@ -1926,9 +1813,9 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         else if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_n64_kernel<false, false>), g64, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_f32_n64_kernel<true, false>), g64, dim3(256), 0, st, p);
     } else
-#define GEMM_GO(TA_, TB_, WM_) do { if (fast && tl_call_precision == 1) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, TB_, WM_, false, false, false>), grid, dim3(256), 0, st, p); \
+#define GEMM_GO(TA_, TB_, WM_) do { if (fast && cx.mode() == 1) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, TB_, WM_, false, false, false>), grid, dim3(256), 0, st, p); \
                                      else if (half) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, WM_, 0, false, false, 2>), grid, dim3(256), 0, st, p); \
-                                     else if (fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts)) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, WM_>), grid, dim3(256), 0, st, p); \
+                                     else if (fast && cx.mode() == 2 && gemm_split_pays(M, N, kts)) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, WM_>), grid, dim3(256), 0, st, p); \
                                      else if (fast) hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_, WM_, true>), grid, dim3(256), 0, st, p); \
                                      else hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_, WM_, false>), grid, dim3(256), 0, st, p); } while (0)
     if (dy) {                                                            // dual A operand (validated above: split kernel, interior tiles)
@@ -1955,7 +1842,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
         else if (xf->which == 2 && ta && !tb && (!grp || grp->mode == 2)) SPLIT_XF_GO(true, false, 2);
         else return MLSP_ERR_UNSUPPORTED;
 #undef SPLIT_XF_GO
-    } else if (grp && tl_call_precision == 2 && gemm_split_pays(M, N, kts)) {   // block-diagonal launch on the split kernel (groups are a run-time argument there)
+    } else if (grp && cx.mode() == 2 && gemm_split_pays(M, N, kts)) {   // block-diagonal launch on the split kernel (groups are a run-time argument there)
         if (grp->mode == 1 && !ta && tb) { if (bm == 128) GEMM_GO(false, true, 2); else GEMM_GO(false, true, 1); }
         else if (grp->mode == 1 && !ta && !tb) { if (bm == 128) GEMM_GO(false, false, 2); else GEMM_GO(false, false, 1); }
         else if (grp->mode == 2 && ta && !tb) { if (bm == 128) GEMM_GO(true, false, 2); else GEMM_GO(true, false, 1); }
@@ -1993,7 +1880,7 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
 #undef GEMM_GO
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
-        const bool on_split = fast && tl_call_precision == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split);
+        const bool on_split = fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split);
         g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (stat_part ? 1 : 0) + (sel_gamma ? 2 : 0), on_split ? (half ? 2 : 1) : 0, (dy ? 1 : 0) + (accumulate ? 2 : 0)};
         g_prof.used++;
         g_prof.flop += 2.0 * M * (double)N * K;
@@ -2010,9 +1897,9 @@ int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const flo
 // accumulation); a bf16 operand is copied to LDS as it is (half the HBM bytes, no conversion), an fp32 one is rounded on the way.
 // Only interior-tile shapes (M % tile, N % 128, K % 32 == 0, 16-byte aligned rows): MLSP_ERR_UNSUPPORTED otherwise, and the caller keeps
 // that layer in fp32.  Same BN-statistics / bias / per-cloud-bias / beta = 1 epilogues; the statistics come from the fp32 accumulators.
-int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16,
+int launch_gemm_mx(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16,
                    int ldb, void* C, int c_bf16, int ldc, const GemmOpts& o) {
-    if (!a_bf16 && !b_bf16 && !c_bf16) return launch_gemm(st, ta, tb, M, N, K, (const float*)A, lda, (const float*)B, ldb, (float*)C, ldc, o);
+    if (!a_bf16 && !b_bf16 && !c_bf16) return launch_gemm(st, cx, ta, tb, M, N, K, (const float*)A, lda, (const float*)B, ldb, (float*)C, ldc, o);
     // what the bf16 path does not implement (nothing launched)
     if (o.sel_gamma || o.sel_val || o.sel_row || o.xf || o.grp || o.bs || o.dy || o.unfold_dw || o.stat_ld) return MLSP_ERR_UNSUPPORTED;
     if (o.unfolded) *o.unfolded = false;
@@ -2031,7 +1918,7 @@ int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const 
     const int ktiles = (K + BK - 1) / BK;
     const int kts = (ktiles + ns - 1) / ns;
     ns = (ktiles + kts - 1) / kts;
-    const int bm = (ns == 1) ? gemm_pick_bm(M, N, K) : 128;
+    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
     p.ntm = (M + bm - 1) / bm; p.ntn = (N + BN - 1) / BN;
     p.nsplit = ns; p.ksplit = kts * BK;
     const bool a_ok = a_bf16 ? (lda % 8 == 0) : (lda % 4 == 0), b_ok = b_bf16 ? (ldb % 8 == 0) : (ldb % 4 == 0);

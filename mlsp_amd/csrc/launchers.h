@@ -10,28 +10,25 @@
 hipError_t mlsp_lds_limit(const void* fn, size_t lds);
 
 // gemm.hip
-int gemm_precision_mode();   // the product mode of the entry point this thread is inside (common.h GemmPrecisionScope)
-// operand-magnitude slots of the f16x3 products: reserve -> partials the CALLER fills for operand X; offered_output -> the caller-table entry
-// of an output of this call with room for `need` floats.  null: nothing to fill
-float* amax_reserve(const float* X, long rows, int cols, int ld);
-float* amax_offered_output(const float* out, long rows, int cols, int ld, int need);
+// cx: the calling entry point's context (callctx.h: product mode, f16x3 operand bounds); no default, a call without one does not compile.
+// The shape queries answer for cx's mode; the launchers also measure into / look up cx's operand bounds.
 // unfold_dw / unfolded (nullable): common.h GemmOpts
 int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int nsplit, float* unfold_dw = nullptr,
                        bool* unfolded = nullptr);
-int gemm_stat_parts(int M, int N, int K);
-int gemm_panel_rows(int M, int N, int K);
-size_t gemm_slab_floats(int M, int N, int K);
+int gemm_stat_parts(const CallCtx& cx, int M, int N, int K);
+int gemm_panel_rows(const CallCtx& cx, int M, int N, int K);
+size_t gemm_slab_floats(int M, int N, int K);   // (the same in every mode)
 int prof_cls_begin(hipStream_t st, int cls);   // cls: common.h MLSP_PROF_*; -> token (< 0: not armed)
 void prof_cls_end(hipStream_t st, int token, double work);
 // which: the operand that takes the transform, 1 = A ([M][K] row-major), 2 = B ([K][N] k-major) (common.h GemmXf)
-bool gemm_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which);
-int gemm_bs_parts(int M, int N, int K, int lda, int ldb, int ldc);
-bool gemm_dy_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb);
-bool gemm_xf_on_split(bool ta, bool tb, int M, int N, int K, int which);
-int launch_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                const GemmOpts& o = GemmOpts());
-int launch_gemm_mx(hipStream_t st, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16, int ldb,
-                   void* C, int c_bf16, int ldc, const GemmOpts& o = GemmOpts());
+bool gemm_xf_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which);
+int gemm_bs_parts(const CallCtx& cx, int M, int N, int K, int lda, int ldb, int ldc);
+bool gemm_dy_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb);
+bool gemm_xf_on_split(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, int which);
+int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
+                int ldc, const GemmOpts& o = GemmOpts());
+int launch_gemm_mx(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16,
+                   int ldb, void* C, int c_bf16, int ldc, const GemmOpts& o = GemmOpts());
 
 // knn.hip
 // xx_ws: [B*N] floats of workspace; planes (nullable): knn6_plane_bytes(B*N, C) bytes of workspace for the v6 kernel's bf16 images
@@ -58,7 +55,7 @@ int bn_stat_parts(int M);
 int bn_parts_max(int M);
 int launch_colstats_n(hipStream_t st, const float* Y, int M, int C, int ld, double* part, int* nparts_out);
 int launch_colstats(hipStream_t st, const float* Y, int M, int C, int ld, double* part);
-// bound_out (nullable, [C]): also write the channels' output bounds |gamma| sqrt(count) + |beta| (a slot of amax_offered_output)
+// bound_out (nullable, [C]): also write the channels' output bounds |gamma| sqrt(count) + |beta| (an entry that CallCtx::offered_output found)
 int launch_bn_finalize(hipStream_t st, const double* part, int nparts, double count, int C, const float* gamma, const float* beta, float* run_mean,
                        float* run_var, float momentum, float eps, float* scale, float* shift, float* save_mean, float* save_invstd,
                        float* bound_out = nullptr);
@@ -155,14 +152,14 @@ int launch_density_loss_bwd(hipStream_t st, const float* pvec, const float* dens
 int tnet_grid(int ntiles);
 int tnet_points_per_tile(int k);
 int tnet_fwd_parts(int B, int N, int k);
-int launch_tnet_edge_fwd(hipStream_t st, const float* uv, const int* idx, const float* bn1, const float* W2, const float* gamma2, int P, int N, int k,
+int launch_tnet_edge_fwd(hipStream_t st, int mode, const float* uv, const int* idx, const float* bn1, const float* W2, const float* gamma2, int P, int N, int k,
                          float slope, float* zsel, uint8_t* argsel, double* part);
 int launch_tnet_out(hipStream_t st, const float* zsel, const float* bn2, int P, float slope, float* out);
 int launch_tnet_bwd_reduce(hipStream_t st, const float* dT, const float* T, const float* zsel, const float* bn2, int P, float slope, double* part);
 int launch_tnet_bwd_g(hipStream_t st, const float* dT, const float* T, const float* bn2, const float* mean_dz, const float* mean_dzy, int P,
                       float slope, float* g, float* coef);
 size_t tnet_bwd_scratch_floats(int ntiles);
-int launch_tnet_edge_bwd(hipStream_t st, const float* uv, const int* idx, const float* bn1, const float* W2, const float* bn2, const float* g,
+int launch_tnet_edge_bwd(hipStream_t st, int mode, const float* uv, const int* idx, const float* bn1, const float* W2, const float* bn2, const float* g,
                          const uint8_t* argsel, const float* coef, int P, int N, int k, float slope, float* dhp, float* scratch, double* part1,
                          float* dW2, int* nparts);
 int launch_tnet_edge_bwd2(hipStream_t st, const float* dhp, const float* uv, const float* s1, const float* bn1, const float* m1, const float* m2,

@@ -249,9 +249,9 @@ static int multi_check(const float* X, int ldx, int M, const mlsp_seg_t* segs, i
 
 // Length of the run of segments starting at s that ONE block-diagonal GEMM launch can take (gemm.hip GemmGroups): same shape and
 // weight pitch, no bias, input slices back to back, widths a multiple of the 128-wide tile, interior 16-byte-aligned operands.
-static int multi_group_run(const float* X, int ldx, int M, const mlsp_seg_t* segs, int nseg, int s, const mlsp_defer_t* in = nullptr) {
+static int multi_group_run(const CallCtx& cx, const float* X, int ldx, int M, const mlsp_seg_t* segs, int nseg, int s, const mlsp_defer_t* in = nullptr) {
     const mlsp_seg_t& a = segs[s];
-    if (gemm_precision_mode() == 1 || a.bias || a.Cin % 128 || a.Cout % 128 || M % 128 || ldx % 4 || a.ldw % 4 || (((uintptr_t)X | (uintptr_t)a.W) & 15)) return 1;
+    if (cx.mode() == 1 || a.bias || a.Cin % 128 || a.Cout % 128 || M % 128 || ldx % 4 || a.ldw % 4 || (((uintptr_t)X | (uintptr_t)a.W) & 15)) return 1;
     int n = 1;
     while (s + n < nseg && n < 4) {
         const mlsp_seg_t& b = segs[s + n];
@@ -262,11 +262,8 @@ static int multi_group_run(const float* X, int ldx, int M, const mlsp_seg_t* seg
     return n;
 }
 
-extern "C" {
-
-int mlsp_multimlp_supported(int M, const mlsp_seg_t* segs, int nseg, int precision) {
-    if (precision < 0 || precision > 3) return 0;
-    GemmPrecisionScope prec_scope_(precision);
+// what mlsp_multimlp_supported answers (the same in every product mode, so it takes no context; the entry points ask it directly)
+static int multi_supported(int M, const mlsp_seg_t* segs, int nseg) {
     int Ctot = 0, xw = 0;
     if (!segs || nseg < 1) return 0;
     int ldx = 0;
@@ -276,15 +273,22 @@ int mlsp_multimlp_supported(int M, const mlsp_seg_t* segs, int nseg, int precisi
     return 1;
 }
 
+extern "C" {
+
+int mlsp_multimlp_supported(int M, const mlsp_seg_t* segs, int nseg, int precision) {
+    return CallCtx::query(precision).ok() ? multi_supported(M, segs, nseg) : 0;
+}
+
 int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs, int nseg, const mlsp_defer_t* in, const float* gamma, const float* beta,
                           float* run_mean, float* run_var, float momentum, float eps, int training, const float* chan, float p_drop,
                           uint64_t seed, float* Y, float* Z, float* bn_save, int precision, void* ws, size_t ws_bytes, mlsp_stream_t st) {
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     int Ctot, xw;
     MCHECK(multi_check(X, ldx, M, segs, nseg, Ctot, xw));
     if (!gamma || !beta || !chan || !Y || !bn_save || p_drop < 0.f || p_drop >= 1.f) return MLSP_ERR_ARG;      // Z == NULL: activation deferred to the consumers
     if (!training && (!run_mean || !run_var)) return MLSP_ERR_ARG;
-    if (!mlsp_multimlp_supported(M, segs, nseg, precision)) return MLSP_ERR_UNSUPPORTED;
+    if (!multi_supported(M, segs, nseg)) return MLSP_ERR_UNSUPPORTED;
     if ((((uintptr_t)Y | (uintptr_t)Z | (uintptr_t)chan | (uintptr_t)bn_save) & 15) != 0) return MLSP_ERR_UNSUPPORTED;
     if (in) for (int s = 0; s < nseg; ++s) if (!multi_defer_ok(in[s], segs[s])) return MLSP_ERR_ARG;
     Workspace w(ws, ws_bytes);
@@ -295,19 +299,19 @@ int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs
     bool fuse[8] = {false, false, false, false, false, false, false, false};    // deferred input: the run's GEMM transforms its A operand itself
     bool any_mat = false;
     for (int s = 0; s < nseg; s += run[s]) {
-        run[s] = multi_group_run(X, ldx, M, segs, nseg, s, in);
+        run[s] = multi_group_run(cx, X, ldx, M, segs, nseg, s, in);
         if (in) {
             const mlsp_seg_t& g = segs[s];
-            if (run[s] > 1 && !gemm_xf_on_split(false, true, M, run[s] * g.Cout, g.Cin, 1)) run[s] = 1;
-            fuse[s] = multi_defer_fusable(in[s]) && gemm_xf_supported(false, true, M, run[s] * g.Cout, g.Cin, X + g.x_col, ldx, g.W, g.ldw, 1);
+            if (run[s] > 1 && !gemm_xf_on_split(cx, false, true, M, run[s] * g.Cout, g.Cin, 1)) run[s] = 1;
+            fuse[s] = multi_defer_fusable(in[s]) && gemm_xf_supported(cx, false, true, M, run[s] * g.Cout, g.Cin, X + g.x_col, ldx, g.W, g.ldw, 1);
             any_mat |= !fuse[s];
         }
         for (int t = 1; t < run[s]; ++t) run[s + t] = 0;
     }
     bool fused = training != 0;
-    const int bm = gemm_panel_rows(M, run[0] * segs[0].Cout, segs[0].Cin);
+    const int bm = gemm_panel_rows(cx, M, run[0] * segs[0].Cout, segs[0].Cin);
     for (int s = 0; s < nseg && fused; s += run[s])
-        fused = gemm_stat_parts(M, run[s] * segs[s].Cout, segs[s].Cin) > 0 && gemm_panel_rows(M, run[s] * segs[s].Cout, segs[s].Cin) == bm;
+        fused = gemm_stat_parts(cx, M, run[s] * segs[s].Cout, segs[s].Cin) > 0 && gemm_panel_rows(cx, M, run[s] * segs[s].Cout, segs[s].Cin) == bm;
     int nparts = fused ? (M + bm - 1) / bm : bn_vec_parts(M);
     const int npmax = nparts > bn_vec_parts(M) ? nparts : bn_vec_parts(M);
     double* part = w.take<double>((size_t)(npmax > (M + 255) / 256 ? npmax : (M + 255) / 256) * 2 * Ctot);
@@ -335,7 +339,7 @@ int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs
             }
         }
         GemmOpts o = so; o.bias = g.bias; o.stat_part = fused ? part + ycol : nullptr; o.stat_ld = Ctot; o.xf = xf; o.grp = run[s] > 1 ? &grp : nullptr;
-        MCHECK(launch_gemm(st, false, true, M, run[s] * g.Cout, g.Cin, Xs + g.x_col, ldx, g.W, g.ldw, Y + ycol, Ctot, o));
+        MCHECK(launch_gemm(st, cx, false, true, M, run[s] * g.Cout, g.Cin, Xs + g.x_col, ldx, g.W, g.ldw, Y + ycol, Ctot, o));
         ycol += run[s] * g.Cout;
     }
     float* scale = bn_save, *shift = bn_save + Ctot, *mean = bn_save + 2 * Ctot, *invstd = bn_save + 3 * Ctot;
@@ -356,19 +360,19 @@ int mlsp_multimlp_fwd_f32(const float* X, int ldx, int M, const mlsp_seg_t* segs
 // Row panels the fused statistics pass of mlsp_multimlp_bwd_f32(in_stats != NULL) writes: M / 128 when EVERY segment's dgrad (single or
 // block-diagonal, as the backward will launch them) runs on a kernel with that pass, else 0.
 int mlsp_multimlp_bwd_stats_parts(int M, const mlsp_seg_t* segs, int nseg, int ldx, int lddx, int precision) {
-    if (precision < 0 || precision > 3 || !segs || nseg < 1 || nseg > 8) return 0;
-    GemmPrecisionScope prec_scope_(precision);
+    const CallCtx cx = CallCtx::query(precision);
+    if (!cx.ok() || !segs || nseg < 1 || nseg > 8) return 0;
     int Ctot = 0;
     for (int s = 0; s < nseg; ++s) Ctot += segs[s].Cout;
     static const float dummy = 0.f;
     int run = 1;
     for (int s = 0; s < nseg; s += run) {
-        run = multi_group_run(&dummy, ldx, M, segs, nseg, s);
+        run = multi_group_run(cx, &dummy, ldx, M, segs, nseg, s);
         for (int t = 0; t < s; ++t)
             if (!(segs[t].x_col + segs[t].Cin <= segs[s].x_col || segs[s].x_col + run * segs[s].Cin <= segs[t].x_col)) return 0;     // overlapping inputs: beta = 1
         // (the backward may launch the run as one block-diagonal product or segment by segment: both shapes must take the pass)
-        if (gemm_bs_parts(M, run * segs[s].Cin, segs[s].Cout, Ctot, segs[s].ldw, lddx) != M / 128 ||
-            gemm_bs_parts(M, segs[s].Cin, segs[s].Cout, Ctot, segs[s].ldw, lddx) != M / 128) return 0;
+        if (gemm_bs_parts(cx, M, run * segs[s].Cin, segs[s].Cout, Ctot, segs[s].ldw, lddx) != M / 128 ||
+            gemm_bs_parts(cx, M, segs[s].Cin, segs[s].Cout, Ctot, segs[s].ldw, lddx) != M / 128) return 0;
     }
     return M / 128;
 }
@@ -382,14 +386,15 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
     // pre_stats (producer role): dZ arrives masked with its sums in pre_stats [pre_parts][2][Ctot]: no reduction pass here.
     // pre_stats == NULL with pre_parts < 0: dZ arrives masked but WITHOUT complete sums (only some of the consumers took part in this
     // backward pass; the other columns are zero): this call reduces them itself and does not apply the mask a second time.
-    PREC_SCOPE(precision);
+    CallCtx cx(precision, ws, ws_bytes);
+    if (!cx.ok()) return MLSP_ERR_ARG;
     int Ctot, xw;
     MCHECK(multi_check(X, ldx, M, segs, nseg, Ctot, xw));
     if (!dZ || !Y || !bn_save || !chan || !dW || !dgamma || !dbeta || (dX && lddx < xw)) return MLSP_ERR_ARG;
     if (in_stats && (!in || !dX)) return MLSP_ERR_ARG;
     if (pre_stats && pre_parts <= 0) return MLSP_ERR_ARG;
     const int premasked = (pre_stats || pre_parts < 0) ? 1 : 0;
-    if (!mlsp_multimlp_supported(M, segs, nseg, precision)) return MLSP_ERR_UNSUPPORTED;
+    if (!multi_supported(M, segs, nseg)) return MLSP_ERR_UNSUPPORTED;
     if ((((uintptr_t)Y | (uintptr_t)dZ | (uintptr_t)chan | (uintptr_t)bn_save) & 15) != 0) return MLSP_ERR_UNSUPPORTED;
     if (in) for (int s = 0; s < nseg; ++s) if (!multi_defer_ok(in[s], segs[s])) return MLSP_ERR_ARG;
     Workspace w(ws, ws_bytes);
@@ -402,13 +407,13 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
     bool fuse[8] = {false, false, false, false, false, false, false, false};    // deferred input: the run's weight-gradient GEMM transforms its B operand (X) itself
     bool any_mat = false;
     for (int s = 0; s < nseg; s += run[s]) {
-        run[s] = multi_group_run(X, ldx, M, segs, nseg, s, in);
+        run[s] = multi_group_run(cx, X, ldx, M, segs, nseg, s, in);
         for (int t = 1; t < run[s]; ++t)
             if (!dW[s + t] || dW[s + t] != dW[s] + (size_t)t * segs[s].Cout * segs[s].Cin) { run[s] = 1; break; }
         if (in) {
             const mlsp_seg_t& g = segs[s];
-            if (run[s] > 1 && !gemm_xf_on_split(true, false, run[s] * g.Cout, g.Cin, M, 2)) run[s] = 1;
-            fuse[s] = multi_defer_fusable(in[s]) && gemm_xf_supported(true, false, run[s] * g.Cout, g.Cin, M, dY, Ctot, X + g.x_col, ldx, 2);
+            if (run[s] > 1 && !gemm_xf_on_split(cx, true, false, run[s] * g.Cout, g.Cin, M, 2)) run[s] = 1;
+            fuse[s] = multi_defer_fusable(in[s]) && gemm_xf_supported(cx, true, false, run[s] * g.Cout, g.Cin, M, dY, Ctot, X + g.x_col, ldx, 2);
             any_mat |= !fuse[s];
         }
         for (int t = 1; t < run[s]; ++t) run[s + t] = 0;
@@ -430,8 +435,8 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
     bool use_dy = pre_stats && training && !any_mat;
     for (int s = 0, yc = 0; s < nseg && use_dy; yc += run[s] * segs[s].Cout, s += run[s]) {
         const mlsp_seg_t& g = segs[s];
-        if (dX) use_dy = gemm_dy_supported(false, false, M, run[s] * g.Cin, g.Cout, dZ + yc, Ctot, g.W, g.ldw);
-        use_dy = use_dy && gemm_dy_supported(true, false, run[s] * g.Cout, g.Cin, M, dZ + yc, Ctot, X + g.x_col, ldx);
+        if (dX) use_dy = gemm_dy_supported(cx, false, false, M, run[s] * g.Cin, g.Cout, dZ + yc, Ctot, g.W, g.ldw);
+        use_dy = use_dy && gemm_dy_supported(cx, true, false, run[s] * g.Cout, g.Cin, M, dZ + yc, Ctot, X + g.x_col, ldx);
     }
     float* zb = (dbias && training) ? dbias : nullptr;      // a bias in front of a batch-statistics BatchNorm: analytically zero gradient, written by the finalizer
     if (use_dy) {
@@ -476,7 +481,7 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
                 for (int t = 1; t < G; ++t) if (!multi_defer_same(in[s], in[s + t])) return MLSP_ERR_UNSUPPORTED;     // (one producer description per launch)
             }
             GemmOpts od = so; od.accumulate = acc; od.grp = G > 1 ? &grp : nullptr; od.bs = bs; od.dy = use_dy ? &dy_s : nullptr;
-            MCHECK(launch_gemm(st, false, false, M, G * g.Cin, g.Cout, gY + ycol, Ctot, g.W, g.ldw, dX + g.x_col, lddx, od));
+            MCHECK(launch_gemm(st, cx, false, false, M, G * g.Cin, g.Cout, gY + ycol, Ctot, g.W, g.ldw, dX + g.x_col, lddx, od));
         }
         const float* Xs = X;
         GemmXf xf_s; const GemmXf* xf = nullptr;
@@ -493,7 +498,7 @@ int mlsp_multimlp_bwd_f32(const float* dZ, const float* X, int ldx, int M, const
         }
         GemmGroups grw = {G, 2, 0, g.Cin, {nullptr, nullptr, nullptr, nullptr}};
         GemmOpts ow = so; ow.xf = xf; ow.grp = G > 1 ? &grw : nullptr; ow.dy = use_dy ? &dy_s : nullptr;
-        MCHECK(launch_gemm(st, true, false, G * g.Cout, g.Cin, M, gY + ycol, Ctot, Xs + g.x_col, ldx, dW[s], g.Cin, ow));
+        MCHECK(launch_gemm(st, cx, true, false, G * g.Cout, g.Cin, M, gY + ycol, Ctot, Xs + g.x_col, ldx, dW[s], g.Cin, ow));
         ycol += G * g.Cout;
     }
     if (dbias && !training) MCHECK(launch_colsum(st, dY, M, Ctot, part, dbias));      // (training: zeroed by the finalizer above)

@@ -1761,7 +1761,7 @@ int tnet_fwd_parts(int B, int N, int k) {
     return tp > 0 ? tnet_grid(B * ((N + tp - 1) / tp)) : 0;
 }
 
-int launch_tnet_edge_fwd(hipStream_t st, const float* uv, const int* idx, const float* bn1, const float* W2, const float* gamma2,
+int launch_tnet_edge_fwd(hipStream_t st, int mode, const float* uv, const int* idx, const float* bn1, const float* W2, const float* gamma2,
                          int P, int N, int k, float slope, float* zsel, uint8_t* argsel, double* part) {
     TnetFwdArgs a;
     a.uv = uv; a.idx = idx; a.bn1 = bn1; a.W2 = W2; a.gamma2 = gamma2; a.zsel = zsel; a.argsel = argsel; a.part = part;
@@ -1775,11 +1775,11 @@ int launch_tnet_edge_fwd(hipStream_t st, const float* uv, const int* idx, const 
         // tests/test_gpu_kernels.py::test_tnet_forward_kernels_vs_float64) whenever the call's `precision` asks for products on
         // the bf16 cores (modes 1 and 2), tnet_edge_fwd2_kernel (f32 MFMA) in mode 0 -- the product mode decides, at every size: B = 32, N = 1024 forward op 222 -> 173 us, B = 8 81 -> 70 us; small
         // launches are enqueue-bound and the two kernels take the same time (tools/time_tnet.py: 88 vs 84 us at B = 4, N = 128).
-        if (gemm_precision_mode() == 0) {
+        if (mode == 0) {
             if (k == 20) hipLaunchKernelGGL((tnet_edge_fwd2_kernel<20>), dim3(grid), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((tnet_edge_fwd2_kernel<40>), dim3(grid), dim3(256), 0, st, a);
         } else {
-            const bool onep = gemm_precision_mode() == 1;
+            const bool onep = mode == 1;
             if (k == 20 && !onep) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<20>), dim3(grid), dim3(256), 0, st, a);
             else if (k == 20) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<20, true>), dim3(grid), dim3(256), 0, st, a);
             else if (!onep) hipLaunchKernelGGL((tnet_edge_fwd3_kernel<40>), dim3(grid), dim3(256), 0, st, a);
@@ -1824,7 +1824,7 @@ size_t tnet_bwd_scratch_floats(int ntiles) {
     return a > b ? a : b;
 }
 // Per-edge backward: dh' [E][64], dW2, and the BN1-backward partial sums part1 [*nparts][2][64].
-int launch_tnet_edge_bwd(hipStream_t st, const float* uv, const int* idx, const float* bn1, const float* W2, const float* bn2,
+int launch_tnet_edge_bwd(hipStream_t st, int mode, const float* uv, const int* idx, const float* bn1, const float* W2, const float* bn2,
                          const float* g, const uint8_t* argsel, const float* coef, int P, int N, int k, float slope, float* dhp,
                          float* scratch, double* part1, float* dW2, int* nparts) {
     const int TP = tnet_points_per_tile(k);
@@ -1838,9 +1838,9 @@ int launch_tnet_edge_bwd(hipStream_t st, const float* uv, const int* idx, const 
         hipLaunchKernelGGL(tnet_bwd_prep_kernel, dim3(TN_C1 / 4 + 1), dim3(256), 0, st, W2, coef, bn2, Mc);
         // products on the bf16 cores (modes 1 and 2): the dense split form (tnet_edge_bwds_kernel); mode 0 keeps exact fp32 products with
         // the register-indexed sparse half.
-        if (gemm_precision_mode() != 0 && k % 2 == 0 && k >= 8 && k <= 64) {
+        if (mode != 0 && k % 2 == 0 && k >= 8 && k <= 64) {
             const size_t lds = sizeof(TnetBwdSLds);
-            auto kern = gemm_precision_mode() == 1 ? tnet_edge_bwds_kernel<true> : tnet_edge_bwds_kernel<false>;
+            auto kern = mode == 1 ? tnet_edge_bwds_kernel<true> : tnet_edge_bwds_kernel<false>;
             hipError_t e = mlsp_lds_limit((const void*)kern, lds);
             if (e != hipSuccess) return (int)e;
             hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, st, uv, idx, bn1, W2, Mc, g, argsel, dhp, slabs, part1, P, N, k, TP, slope);

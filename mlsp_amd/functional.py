@@ -129,9 +129,11 @@ class _PrecisionMeta(type):
 
 class gemm_precision(metaclass=_PrecisionMeta):
     """Which products the GEMM family computes -- the `precision` ARGUMENT of every C entry point that reaches the matrix cores
-    (include/mlsp_hip.h; the library itself keeps no switch).  "bf16x6" (default): fp32-ACCURATE products on the bf16 matrix cores --
-    every operand split exactly into three bf16 pieces, six piece products per multiply, fp32 accumulation; against float64 its error
-    is below the f32-MFMA chain's, and it is 1.55-1.65x faster (DVFS-limited either way: DESIGN.md).  "fp32": the f32 MFMA for every
+    (include/mlsp_hip.h; the library itself keeps no switch).  "f16x3" (default): fp32-ACCURATE products on the f16 matrix cores -- every
+    operand value, times a per-workgroup power of two, split into two f16 pieces, three piece products per multiply, fp32 accumulation.
+    "bf16x6" (the default of rounds 3-5): the same accuracy class on the bf16 matrix cores -- every operand split exactly into three
+    bf16 pieces, six piece products per multiply; against float64 its error is below the f32-MFMA chain's, and it is 1.55-1.65x
+    faster (DVFS-limited either way: DESIGN.md).  "fp32": the f32 MFMA for every
     launch (exact fp32 products).  "bf16": operands ROUNDED to bf16, fp32 accumulation (BASELINE.json configs[4]; reduced precision,
     opt-in).  kNN distances, BatchNorm statistics, reductions and losses are fp32 in every mode (the kNN always exact, canonical order).
 
