@@ -238,7 +238,7 @@ def _serialised(fn):
 def check(rc, what):
     if rc != 0:
         msg = load().mlsp_strerror(rc)
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+        raise MlspLibraryError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
 def ptr(t):
