@@ -273,7 +273,15 @@ int mlsp_colmax_bwd_f32(const float* dOut, const int32_t* arg, int B, int N, int
 
 /* masked symmetric Chamfer (MLSP/mlsp.py:115-182, scaled as calc_loss :222-229):
  * loss = scale * sum_b (A_b + B_b)/cnt_b,  scale = DefRec_weight * DefRec_SCALER / B.
- * pred [B][N][3], gold [B][3][N], mask [B][3][N]; per_cloud [B][3], argA/argB [B][N] saved. */
+ * pred [B][N][3], gold [B][3][N], mask [B][3][N]; per_cloud [B][3], argA/argB [B][N] saved.
+ * Contract of both Chamfer forwards (this one and mlsp_chamfer_dir_fwd_f32):
+ *  - the mask holds 0 or 1 (row 0 of [B][3][N] is read here); any non-zero entry counts as a masked row with no penalty.
+ *  - on every masked row the stored arg-min column is in [0, N), whatever the inputs hold, so the backward never indexes outside
+ *    the cloud.  The lowest column wins ties.
+ *  - a masked point that is NaN or infinite, or coordinates so large that every squared distance of a masked row overflows, leave
+ *    that row with no column below the start value: its minimum is stored as +inf, its arg as column 0, and the loss is non-finite.
+ *  - a non-finite value in an UNMASKED point is not reported: such a column is never the nearest and such a row is never scanned,
+ *    where the reference's 0 * NaN would make the loss NaN.  A known, accepted difference. */
 int mlsp_chamfer_masked_fwd_f32(const float* pred, const float* gold, const float* mask, int B, int N, float scale,
                                 float* per_cloud, int32_t* argA, int32_t* argB, float* loss, mlsp_stream_t stream);
 int mlsp_chamfer_masked_bwd_f32(const float* pred, const float* gold, const float* mask, int B, int N, float scale,
@@ -283,7 +291,8 @@ int mlsp_chamfer_masked_bwd_f32(const float* pred, const float* gold, const floa
 /* ONE direction of the masked Chamfer distance = the reference's chamfer_distance(p1, p2, mask) (MLSP/mlsp.py:115-153):
  * loss = sum_b (sum over the masked rows i of p1 of min_j (|p1_i - p2_j|^2 + 100 [mask_j == 0])) / cnt_b.
  * p1, p2 [B][N][3]; mask_cord [B][N] = mask[:, :, 0]; per_cloud [B][2] = {sum, cnt} and arg [B][N] (arg-min column of every
- * masked row) are saved for the backward, which writes dp1 and / or dp2 [B][N][3] (either may be NULL). */
+ * masked row) are saved for the backward, which writes dp1 and / or dp2 [B][N][3] (either may be NULL).  The mask is 0/1 and arg
+ * is in [0, N) on every masked row; non-finite points as stated for mlsp_chamfer_masked_fwd_f32 above. */
 int mlsp_chamfer_dir_fwd_f32(const float* p1, const float* p2, const float* mask_cord, int B, int N, float* per_cloud, int32_t* arg,
                              float* loss, mlsp_stream_t stream);
 int mlsp_chamfer_dir_bwd_f32(const float* p1, const float* p2, const float* mask_cord, int B, int N, const float* per_cloud,

@@ -12,7 +12,10 @@
 // ---------------------------------------------------------------------------------------------
 // pred [B][N][3] (head output), gold [B][3][N], mask [B][3][N] (row 0 is used, as mlsp.py:141).
 // per_cloud[b] = {sumA, sumB, cnt}: A = rows from gold vs columns of pred, B = the converse.
-// argA/argB [B][N]: arg-min column for every masked row (undefined elsewhere).
+// argA/argB [B][N]: arg-min column for every masked row (undefined elsewhere), always in [0, N): the search starts at
+// (best = +inf, column 0) and takes a column only on d < best, so a row whose every d is NaN or +inf (a non-finite masked point,
+// or coordinates whose squared distances overflow) keeps column 0 and a row minimum of +inf, and the loss comes out non-finite.
+// The backward kernels index the clouds through these arrays without a check of their own.
 __global__ __launch_bounds__(1024) void chamfer_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gold,
                                                            const float* __restrict__ mask, int N,
                                                            float* __restrict__ per_cloud, int* __restrict__ argA,
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(1024) void chamfer_fwd_kernel(const float* __restri
         const float* p2 = dir == 0 ? px : gx;     // columns
         const float ax = p1[i], ay = p1[N + i], az = p1[2 * N + i];
         float best = INFINITY;
-        int bj = 0x7fffffff;
+        int bj = 0;   // in range whatever the inputs hold: a row where no d compares below +inf keeps column 0 and best = +inf
         for (int j = lane; j < N; j += 64) {
             float dx = ax - p2[j], dy = ay - p2[N + j], dz = az - p2[2 * N + j];
             float nrm = sqrtf(dx * dx + dy * dy + dz * dz);     // reference: norm(...)**2  (mlsp.py:138)
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_kernel(const float* __restri
 // ONE direction of the masked Chamfer distance, as the reference's chamfer_distance(p1, p2, mask) (MLSP/mlsp.py:115-153):
 // p1, p2 [B][N][3] point-major, mc [B][N] = mask[:, :, 0].  Rows = the masked points of p1, columns = all points of p2 with a
 // +100 penalty on the unmasked ones.  per_cloud[b] = {sum of the row minima, number of masked rows}; arg [B][N] the arg-min column
-// of every masked row.
+// of every masked row, in [0, N) whatever the inputs hold (as argA / argB above).
 __global__ __launch_bounds__(1024) void chamfer_dir_fwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                                const float* __restrict__ mc, int N, float* __restrict__ per_cloud,
                                                                int* __restrict__ arg) {
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(1024) void chamfer_dir_fwd_kernel(const float* __re
         const int i = rows[r];
         const float ax = a[i * 3], ay = a[i * 3 + 1], az = a[i * 3 + 2];
         float best = INFINITY;
-        int bj = 0x7fffffff;
+        int bj = 0;   // in range whatever the inputs hold: a row where no d compares below +inf keeps column 0 and best = +inf
         for (int j = lane; j < N; j += 64) {
             float dx = ax - cx[j], dy = ay - cx[N + j], dz = az - cx[2 * N + j];
             float nrm = sqrtf(dx * dx + dy * dy + dz * dz);     // norm(...)**2 (mlsp.py:138)

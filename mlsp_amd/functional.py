@@ -1544,11 +1544,20 @@ def compose_linear(Wa, ba, Wb, bb):
     return _ComposeLinear.apply(Wa, ba, Wb, bb)
 
 
+def _f32_grad_input(t, what):
+    """The loss kernels read their differentiable inputs as fp32 and the gradient takes the input's dtype and shape (torch.empty_like),
+    so another dtype would be misread, not converted: refuse it.  Targets, masks and weights carry no gradient and are converted."""
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be torch.float32, got %s (the loss kernels are fp32; convert before the call so that the gradient "
+                        "has the dtype of what autograd sees)" % (what, t.dtype))
+    return t.contiguous()
+
+
 class _Chamfer(Function):
     @staticmethod
     def forward(ctx, pred, gold, mask, scale):
         lib = _lib.load()
-        pred, gold, mask = pred.contiguous(), gold.contiguous().float(), mask.contiguous().float()
+        pred, gold, mask = _f32_grad_input(pred, "chamfer_masked: pred"), gold.contiguous().float(), mask.contiguous().float()
         _lib.require_gpu(pred, gold, mask)
         B, N, _ = pred.shape
         assert gold.shape == (B, 3, N) and mask.shape == (B, 3, N), (pred.shape, gold.shape, mask.shape)
@@ -1628,7 +1637,7 @@ class _NormalLoss(Function):
     @staticmethod
     def forward(ctx, pred, gt, w, weight):
         lib = _lib.load()
-        pred = pred.contiguous()
+        pred = _f32_grad_input(pred, "normal_loss: pred")
         gt = gt.contiguous().float()
         _lib.require_gpu(pred, gt, w)
         P = pred.numel() // 3
@@ -1665,8 +1674,8 @@ class _DensityTail(Function):
     @staticmethod
     def forward(ctx, logits, fc2w):
         lib = _lib.load()
-        logits = logits.contiguous()
-        fc2w = fc2w.contiguous().reshape(-1)
+        logits = _f32_grad_input(logits, "density_tail: logits")
+        fc2w = fc2w.contiguous().float().reshape(-1)
         _lib.require_gpu(logits, fc2w)
         P, nc = logits.shape
         pvec = torch.empty_like(logits)
@@ -1699,7 +1708,7 @@ class _DensityLoss(Function):
     @staticmethod
     def forward(ctx, pvec, dens, tvec, target, mask, dweight):
         lib = _lib.load()
-        pvec, dens = pvec.contiguous(), dens.contiguous()
+        pvec, dens = _f32_grad_input(pvec, "density_loss: pvec"), _f32_grad_input(dens, "density_loss: dens")
         tvec, target = tvec.contiguous().float(), target.contiguous().float()
         _lib.require_gpu(pvec, dens, tvec, target, mask)
         P, nc = pvec.shape
