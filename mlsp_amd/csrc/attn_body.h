@@ -5,18 +5,13 @@
 #pragma once
 #include <math.h>
 #include <stddef.h>
+#include "rowtile.h"
 
-#define AB_HD __host__ __device__ __forceinline__
-#define AB_THREADS 256
 #define AB_WAVES 4
 #define AB_LDS_MAX (160 * 1024)
 #define AB_MAX_DH 128
 #define AB_MAX_L 512
 #define AB_MAX_LDH 16384
-
-typedef float ab_f4 __attribute__((ext_vector_type(4)));
-AB_HD ab_f4 ab_ld(const float* p) { return *(const ab_f4*)p; }
-AB_HD void ab_st(float* p, const ab_f4& v) { *(ab_f4*)p = v; }
 
 // ---------------------------------------------------------------------------------------------
 // Multi-head attention core.  qkv [B L][ld]: q, k, v of head h in columns h dh, d + h dh, 2 d + h dh (d = H dh); out / dout [B L][d];
@@ -27,9 +22,9 @@ struct MhsaGeo {
     int B, L, H, dh, ld, ldd, qb, nqb, kst, lp;
     float scale;
 };
-AB_HD size_t mhsa_lds_floats(const MhsaGeo& g) { return (size_t)2 * g.L * g.kst + (size_t)AB_WAVES * 2 * g.lp + (size_t)AB_WAVES * 2 * g.dh + (size_t)2 * g.lp; }
+RT_HD size_t mhsa_lds_floats(const MhsaGeo& g) { return (size_t)2 * g.L * g.kst + (size_t)AB_WAVES * 2 * g.lp + (size_t)AB_WAVES * 2 * g.dh + (size_t)2 * g.lp; }
 // the geometry of a shape, or false outside the limits: dh % 4 == 0, dh <= 128, L <= 512, L dh <= 16384 (two [L][dh] arrays in LDS)
-AB_HD bool mhsa_geo(int B, int L, int H, int dh, int ld, int ldd, float scale, bool whole_head, MhsaGeo& g) {
+RT_HD bool mhsa_geo(int B, int L, int H, int dh, int ld, int ldd, float scale, bool whole_head, MhsaGeo& g) {
     if (B <= 0 || L <= 0 || H <= 0 || dh <= 0 || dh % 4 || dh > AB_MAX_DH || L > AB_MAX_L || (long long)L * dh > AB_MAX_LDH) return false;
     const long long d = (long long)H * dh;
     if (3 * d > ld || 3 * d > ldd || ld % 4 || ldd % 4 || (long long)B * L > (1LL << 30)) return false;
@@ -45,7 +40,7 @@ AB_HD bool mhsa_geo(int B, int L, int H, int dh, int ld, int ldd, float scale, b
     return (long long)B * H * g.nqb < (1LL << 31);
 }
 struct MhsaLds { float *A0, *A1, *S, *E, *vec, *lse_s, *del_s; };
-AB_HD MhsaLds mhsa_lds(const MhsaGeo& g, float* lds, int w) {
+RT_HD MhsaLds mhsa_lds(const MhsaGeo& g, float* lds, int w) {
     MhsaLds m;
     m.A0 = lds; m.A1 = m.A0 + (size_t)g.L * g.kst;
     float* s = m.A1 + (size_t)g.L * g.kst;
@@ -56,7 +51,7 @@ AB_HD MhsaLds mhsa_lds(const MhsaGeo& g, float* lds, int w) {
     return m;
 }
 struct MhsaWho { int b, h, q0, q1; long long row0; };      // rows [q0, q1) of cloud b; row0 = b L
-AB_HD MhsaWho mhsa_who(const MhsaGeo& g, int bid) {
+RT_HD MhsaWho mhsa_who(const MhsaGeo& g, int bid) {
     MhsaWho o;
     const int qblk = bid % g.nqb, bh = bid / g.nqb;
     o.h = bh % g.H; o.b = bh / g.H;
@@ -64,51 +59,51 @@ AB_HD MhsaWho mhsa_who(const MhsaGeo& g, int bid) {
     o.row0 = (long long)o.b * g.L;
     return o;
 }
-AB_HD int mhsa_steps(const MhsaGeo& g) { return g.qb / AB_WAVES; }
+RT_HD int mhsa_steps(const MhsaGeo& g) { return g.qb / AB_WAVES; }
 // sum_c a[c] b[c], ascending c, one fma per term (the same bits whichever operand sits in `a`)
-AB_HD float mhsa_dot(const float* a, const float* b, int dh) {
+RT_HD float mhsa_dot(const float* a, const float* b, int dh) {
     float acc = 0.f;
     for (int c = 0; c < dh; c += 4) {
-        const ab_f4 x = ab_ld(a + c), y = ab_ld(b + c);
+        const rt_f4 x = rt_ld(a + c), y = rt_ld(b + c);
         acc = fmaf(x.x, y.x, acc); acc = fmaf(x.y, y.y, acc); acc = fmaf(x.z, y.z, acc); acc = fmaf(x.w, y.w, acc);
     }
     return acc;
 }
 // A0 / A1 <- the [L][dh] column slices of X / Y at columns cx / cy (every row of the cloud)
-AB_HD void mhsa_stage(const MhsaGeo& g, const MhsaWho& o, int tid, const float* X, int ldx, int cx, const float* Y, int ldy, int cy, float* lds) {
+RT_HD void mhsa_stage(const MhsaGeo& g, const MhsaWho& o, int tid, const float* X, int ldx, int cx, const float* Y, int ldy, int cy, float* lds) {
     const MhsaLds m = mhsa_lds(g, lds, 0);
     const int dh4 = g.dh / 4;
-    for (int it = tid; it < g.L * dh4; it += AB_THREADS) {
+    for (int it = tid; it < g.L * dh4; it += RT_THREADS) {
         const int j = it / dh4, cq = it - j * dh4;
-        ab_st(m.A0 + (size_t)j * g.kst + cq * 4, ab_ld(X + (o.row0 + j) * ldx + cx + cq * 4));
-        ab_st(m.A1 + (size_t)j * g.kst + cq * 4, ab_ld(Y + (o.row0 + j) * ldy + cy + cq * 4));
+        rt_st(m.A0 + (size_t)j * g.kst + cq * 4, rt_ld(X + (o.row0 + j) * ldx + cx + cq * 4));
+        rt_st(m.A1 + (size_t)j * g.kst + cq * 4, rt_ld(Y + (o.row0 + j) * ldy + cy + cq * 4));
     }
 }
 // vec[w][slot] <- dh floats of row i of X at column cx
-AB_HD void mhsa_vec_load(const MhsaGeo& g, const MhsaWho& o, int lane, int i, const float* X, int ldx, int cx, float* dst) {
-    if (lane < g.dh / 4) ab_st(dst + lane * 4, ab_ld(X + (o.row0 + i) * ldx + cx + lane * 4));
+RT_HD void mhsa_vec_load(const MhsaGeo& g, const MhsaWho& o, int lane, int i, const float* X, int ldx, int cx, float* dst) {
+    if (lane < g.dh / 4) rt_st(dst + lane * 4, rt_ld(X + (o.row0 + i) * ldx + cx + lane * 4));
 }
 
 // forward, row step r.  a: q_i -> vec;  b: S[j] = scale q_i.k_j;  c: E[j] = exp(S[j] - max S);  d: out_i = sum_j E[j] v_j / sum_j E[j], lse
-AB_HD void mhsa_fwd_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, float* lds) {
+RT_HD void mhsa_fwd_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
     mhsa_vec_load(g, o, lane, i, qkv, g.ld, o.h * g.dh, mhsa_lds(g, lds, w).vec);
 }
-AB_HD void mhsa_fwd_b(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
+RT_HD void mhsa_fwd_b(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
     const MhsaLds m = mhsa_lds(g, lds, w);
     for (int j = lane; j < g.L; j += 64) m.S[j] = mhsa_dot(m.vec, m.A0 + (size_t)j * g.kst, g.dh) * g.scale;
 }
-AB_HD float mhsa_row_max(const float* S, int L) {
+RT_HD float mhsa_row_max(const float* S, int L) {
     float mx = S[0];
     for (int j = 1; j < L; ++j) mx = fmaxf(mx, S[j]);
     return mx;
 }
-AB_HD void mhsa_fwd_c(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
+RT_HD void mhsa_fwd_c(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
@@ -116,7 +111,7 @@ AB_HD void mhsa_fwd_c(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
     const float mx = mhsa_row_max(m.S, g.L);
     for (int j = lane; j < g.L; j += 64) m.E[j] = expf(m.S[j] - mx);
 }
-AB_HD void mhsa_fwd_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* out, float* lse) {
+RT_HD void mhsa_fwd_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* out, float* lse) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
@@ -139,7 +134,7 @@ AB_HD void mhsa_fwd_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, flo
 // d: delta_i = sum_j P_ij dP_ij / sum_j P_ij (= dout_i.out_i in exact arithmetic; formed from the very P and dP it is subtracted from, so
 // that sum_j dS_ij carries only their rounding -- the sum that the key bias gradient, exactly 0, is made of), del_s[i] <- delta_i,
 // dq_i = scale sum_j dS_ij k_j, dS_ij = P_ij (dP_ij - delta_i)
-AB_HD void mhsa_bwd_row_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, const float* dout, float* lds) {
+RT_HD void mhsa_bwd_row_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, const float* dout, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
@@ -148,7 +143,7 @@ AB_HD void mhsa_bwd_row_a(const MhsaGeo& g, int bid, int tid, int r, const float
     mhsa_vec_load(g, o, lane, i, qkv, g.ld, o.h * g.dh, vec);
     mhsa_vec_load(g, o, lane, i, dout, d, o.h * g.dh, vec + g.dh);
 }
-AB_HD void mhsa_bwd_row_b(const MhsaGeo& g, int bid, int tid, int r, const float* lse, float* lds) {
+RT_HD void mhsa_bwd_row_b(const MhsaGeo& g, int bid, int tid, int r, const float* lse, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
@@ -161,12 +156,12 @@ AB_HD void mhsa_bwd_row_b(const MhsaGeo& g, int bid, int tid, int r, const float
 }
 // sum_j P[j] dP[j] / sum_j P[j], both sums in fp64 in ascending j (the same in every lane).  P is recomputed from the fp32 lse, so its row sum
 // is 1 only to an ulp of lse; dividing by it makes sum_j P[j] (dP[j] - delta) vanish to the rounding of its terms.
-AB_HD float mhsa_delta(const float* P, const float* dP, int L) {
+RT_HD float mhsa_delta(const float* P, const float* dP, int L) {
     double t = 0.0, n = 0.0;
     for (int j = 0; j < L; ++j) { t = fma((double)P[j], (double)dP[j], t); n += (double)P[j]; }
     return (float)(t / n);
 }
-AB_HD void mhsa_bwd_row_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* dqkv) {
+RT_HD void mhsa_bwd_row_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* dqkv) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, i = o.q0 + r * AB_WAVES + w;
     if (i >= o.q1) return;
@@ -186,12 +181,12 @@ AB_HD void mhsa_bwd_row_d(const MhsaGeo& g, int bid, int tid, int r, float* lds,
 }
 // backward, columns (A0 = Q, A1 = dout, both staged by mhsa_stage).  stats: lse_s[i] for every row of the cloud (del_s: the row phase);
 // a: k_j | v_j -> vec;  b: S[i] = P_ij, E[i] = dS_ij;  d: dk_j = scale sum_i dS_ij q_i, dv_j = sum_i P_ij dout_i
-AB_HD void mhsa_bwd_col_stats(const MhsaGeo& g, int bid, int tid, const float* lse, float* lds) {
+RT_HD void mhsa_bwd_col_stats(const MhsaGeo& g, int bid, int tid, const float* lse, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const MhsaLds m = mhsa_lds(g, lds, 0);
-    for (int i = tid; i < g.L; i += AB_THREADS) m.lse_s[i] = lse[((long long)o.b * g.H + o.h) * g.L + i];
+    for (int i = tid; i < g.L; i += RT_THREADS) m.lse_s[i] = lse[((long long)o.b * g.H + o.h) * g.L + i];
 }
-AB_HD void mhsa_bwd_col_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, float* lds) {
+RT_HD void mhsa_bwd_col_a(const MhsaGeo& g, int bid, int tid, int r, const float* qkv, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, j = o.q0 + r * AB_WAVES + w;
     if (j >= o.q1) return;
@@ -200,7 +195,7 @@ AB_HD void mhsa_bwd_col_a(const MhsaGeo& g, int bid, int tid, int r, const float
     mhsa_vec_load(g, o, lane, j, qkv, g.ld, d + o.h * g.dh, vec);
     mhsa_vec_load(g, o, lane, j, qkv, g.ld, 2 * d + o.h * g.dh, vec + g.dh);
 }
-AB_HD void mhsa_bwd_col_b(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
+RT_HD void mhsa_bwd_col_b(const MhsaGeo& g, int bid, int tid, int r, float* lds) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, j = o.q0 + r * AB_WAVES + w;
     if (j >= o.q1) return;
@@ -211,7 +206,7 @@ AB_HD void mhsa_bwd_col_b(const MhsaGeo& g, int bid, int tid, int r, float* lds)
         m.E[i] = p * (mhsa_dot(m.A1 + (size_t)i * g.kst, m.vec + g.dh, g.dh) - m.del_s[i]);
     }
 }
-AB_HD void mhsa_bwd_col_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* dqkv) {
+RT_HD void mhsa_bwd_col_d(const MhsaGeo& g, int bid, int tid, int r, float* lds, float* dqkv) {
     const MhsaWho o = mhsa_who(g, bid);
     const int w = tid >> 6, lane = tid & 63, j = o.q0 + r * AB_WAVES + w;
     if (j >= o.q1) return;
@@ -237,45 +232,45 @@ struct LnGeo {
     long long rows; int d4, rps; float eps;
     const float *x, *a, *s, *gamma, *beta;
 };
-AB_HD ab_f4 ln_u(const LnGeo& g, long long row, int q) {
-    ab_f4 u = ab_ld(g.x + (row * g.d4 + q) * 4);
+RT_HD rt_f4 ln_u(const LnGeo& g, long long row, int q) {
+    rt_f4 u = rt_ld(g.x + (row * g.d4 + q) * 4);
     if (g.a) {
-        const ab_f4 a = ab_ld(g.a + (row * g.d4 + q) * 4);
+        const rt_f4 a = rt_ld(g.a + (row * g.d4 + q) * 4);
         u = g.s ? u + g.s[row / g.rps] * a : u + a;
     }
     return u;
 }
-AB_HD float ln_sum64(const float* red) {
+RT_HD float ln_sum64(const float* red) {
     float t = 0.f;
     for (int l = 0; l < 64; ++l) t += red[l];
     return t;
 }
 // 1: U <- u (U nullable), red <- the lanes' sums of u;  2: red2 <- the lanes' sums of (u - mean)^2;  3: y, mean, rstd
-AB_HD void ln_fwd_1(const LnGeo& g, long long row0, int tid, float* U, float* lds) {
+RT_HD void ln_fwd_1(const LnGeo& g, long long row0, int tid, float* U, float* lds) {
     const int w = tid >> 6, lane = tid & 63;
     const long long row = row0 + w;
     if (row >= g.rows) return;
     float t = 0.f;
     for (int q = lane; q < g.d4; q += 64) {
-        const ab_f4 u = ln_u(g, row, q);
-        if (U) ab_st(U + (row * g.d4 + q) * 4, u);
+        const rt_f4 u = ln_u(g, row, q);
+        if (U) rt_st(U + (row * g.d4 + q) * 4, u);
         t += (u.x + u.y) + (u.z + u.w);
     }
     lds[w * 64 + lane] = t;
 }
-AB_HD void ln_fwd_2(const LnGeo& g, long long row0, int tid, float* lds) {
+RT_HD void ln_fwd_2(const LnGeo& g, long long row0, int tid, float* lds) {
     const int w = tid >> 6, lane = tid & 63;
     const long long row = row0 + w;
     if (row >= g.rows) return;
     const float mean = ln_sum64(lds + w * 64) / (float)(g.d4 * 4);
     float t = 0.f;
     for (int q = lane; q < g.d4; q += 64) {
-        const ab_f4 c = ln_u(g, row, q) - mean;
+        const rt_f4 c = ln_u(g, row, q) - mean;
         t += (c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w);
     }
     lds[(AB_WAVES + w) * 64 + lane] = t;
 }
-AB_HD void ln_fwd_3(const LnGeo& g, long long row0, int tid, float* lds, float* Y, float* mean_out, float* rstd_out) {
+RT_HD void ln_fwd_3(const LnGeo& g, long long row0, int tid, float* lds, float* Y, float* mean_out, float* rstd_out) {
     const int w = tid >> 6, lane = tid & 63;
     const long long row = row0 + w;
     if (row >= g.rows) return;
@@ -283,27 +278,27 @@ AB_HD void ln_fwd_3(const LnGeo& g, long long row0, int tid, float* lds, float* 
     const float rstd = 1.0f / sqrtf(ln_sum64(lds + (AB_WAVES + w) * 64) / (float)(g.d4 * 4) + g.eps);
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
     for (int q = lane; q < g.d4; q += 64)
-        ab_st(Y + (row * g.d4 + q) * 4, (ln_u(g, row, q) - mean) * rstd * ab_ld(g.gamma + q * 4) + ab_ld(g.beta + q * 4));
+        rt_st(Y + (row * g.d4 + q) * 4, (ln_u(g, row, q) - mean) * rstd * rt_ld(g.gamma + q * 4) + rt_ld(g.beta + q * 4));
 }
 // backward of a row: t = rstd (g - mean(g) - xhat mean(g xhat)) + du, g = dy gamma, xhat = (u - mean) rstd;  dx <- t, da <- s t.
 // dy NULL (the residual add alone): t = du, only da is written.  u: the saved sum (LnGeo.x, with a = NULL).
 struct LnBwd { const float *dy, *du, *mean, *rstd; float *dx, *da; };
-AB_HD void ln_bwd_1(const LnGeo& g, const LnBwd& b, long long row0, int tid, float* lds) {
+RT_HD void ln_bwd_1(const LnGeo& g, const LnBwd& b, long long row0, int tid, float* lds) {
     const int w = tid >> 6, lane = tid & 63;
     const long long row = row0 + w;
     if (row >= g.rows || !b.dy) return;
     const float mean = b.mean[row], rstd = b.rstd[row];
     float t1 = 0.f, t2 = 0.f;
     for (int q = lane; q < g.d4; q += 64) {
-        const ab_f4 xh = (ab_ld(g.x + (row * g.d4 + q) * 4) - mean) * rstd, gg = ab_ld(b.dy + (row * g.d4 + q) * 4) * ab_ld(g.gamma + q * 4);
-        const ab_f4 gx = gg * xh;
+        const rt_f4 xh = (rt_ld(g.x + (row * g.d4 + q) * 4) - mean) * rstd, gg = rt_ld(b.dy + (row * g.d4 + q) * 4) * rt_ld(g.gamma + q * 4);
+        const rt_f4 gx = gg * xh;
         t1 += (gg.x + gg.y) + (gg.z + gg.w);
         t2 += (gx.x + gx.y) + (gx.z + gx.w);
     }
     lds[w * 64 + lane] = t1;
     lds[(AB_WAVES + w) * 64 + lane] = t2;
 }
-AB_HD void ln_bwd_2(const LnGeo& g, const LnBwd& b, long long row0, int tid, float* lds) {
+RT_HD void ln_bwd_2(const LnGeo& g, const LnBwd& b, long long row0, int tid, float* lds) {
     const int w = tid >> 6, lane = tid & 63;
     const long long row = row0 + w;
     if (row >= g.rows) return;
@@ -316,42 +311,42 @@ AB_HD void ln_bwd_2(const LnGeo& g, const LnBwd& b, long long row0, int tid, flo
     }
     for (int q = lane; q < g.d4; q += 64) {
         const long long at = (row * g.d4 + q) * 4;
-        ab_f4 t = ab_f4{0.f, 0.f, 0.f, 0.f};
+        rt_f4 t = rt_f4{0.f, 0.f, 0.f, 0.f};
         if (b.dy) {
-            const ab_f4 xh = (ab_ld(g.x + at) - mean) * rstd, gg = ab_ld(b.dy + at) * ab_ld(g.gamma + q * 4);
+            const rt_f4 xh = (rt_ld(g.x + at) - mean) * rstd, gg = rt_ld(b.dy + at) * rt_ld(g.gamma + q * 4);
             t = ((gg - m1) - xh * m2) * rstd;
         }
-        if (b.du) t = t + ab_ld(b.du + at);
-        if (b.dx) ab_st(b.dx + at, t);
-        if (b.da) ab_st(b.da + at, t * sc);
+        if (b.du) t = t + rt_ld(b.du + at);
+        if (b.dx) rt_st(b.dx + at, t);
+        if (b.da) rt_st(b.da + at, t * sc);
     }
 }
 // dgamma / dbeta partials of the rows [e0, e1): threads are (row lane r < rl, channel quad tc < ct); part[g][cq] = {dgamma quad, dbeta quad}.
 // LDS: sh [256][2] quads.
-AB_HD void ln_par_1(const LnGeo& g, const LnBwd& b, long long e0, long long e1, int cq0, int ct, int rl, int tid, float* lds) {
+RT_HD void ln_par_1(const LnGeo& g, const LnBwd& b, long long e0, long long e1, int cq0, int ct, int rl, int tid, float* lds) {
     const int tc = tid % ct, r = tid / ct, cq = cq0 + tc;
-    ab_f4 ag = ab_f4{0.f, 0.f, 0.f, 0.f}, ab = ab_f4{0.f, 0.f, 0.f, 0.f};
+    rt_f4 ag = rt_f4{0.f, 0.f, 0.f, 0.f}, ab = rt_f4{0.f, 0.f, 0.f, 0.f};
     if (r < rl && cq < g.d4)
         for (long long e = e0 + r; e < e1; e += rl) {
-            const ab_f4 dy = ab_ld(b.dy + (e * g.d4 + cq) * 4);
-            ag += dy * ((ab_ld(g.x + (e * g.d4 + cq) * 4) - b.mean[e]) * b.rstd[e]);
+            const rt_f4 dy = rt_ld(b.dy + (e * g.d4 + cq) * 4);
+            ag += dy * ((rt_ld(g.x + (e * g.d4 + cq) * 4) - b.mean[e]) * b.rstd[e]);
             ab += dy;
         }
-    ab_st(lds + (size_t)tid * 8, ag);
-    ab_st(lds + (size_t)tid * 8 + 4, ab);
+    rt_st(lds + (size_t)tid * 8, ag);
+    rt_st(lds + (size_t)tid * 8 + 4, ab);
 }
-AB_HD void ln_par_2(const LnGeo& g, int bid, int cq0, int ct, int rl, int tid, const float* lds, float* part) {
+RT_HD void ln_par_2(const LnGeo& g, int bid, int cq0, int ct, int rl, int tid, const float* lds, float* part) {
     const int tc = tid % ct, r = tid / ct, cq = cq0 + tc;
     if (r != 0 || cq >= g.d4) return;
-    ab_f4 ag = ab_ld(lds + (size_t)tid * 8), ab = ab_ld(lds + (size_t)tid * 8 + 4);
+    rt_f4 ag = rt_ld(lds + (size_t)tid * 8), ab = rt_ld(lds + (size_t)tid * 8 + 4);
     for (int q = 1; q < rl; ++q) {
-        ag += ab_ld(lds + (size_t)(q * ct + tc) * 8);
-        ab += ab_ld(lds + (size_t)(q * ct + tc) * 8 + 4);
+        ag += rt_ld(lds + (size_t)(q * ct + tc) * 8);
+        ab += rt_ld(lds + (size_t)(q * ct + tc) * 8 + 4);
     }
-    ab_st(part + ((size_t)bid * g.d4 + cq) * 8, ag);
-    ab_st(part + ((size_t)bid * g.d4 + cq) * 8 + 4, ab);
+    rt_st(part + ((size_t)bid * g.d4 + cq) * 8, ag);
+    rt_st(part + ((size_t)bid * g.d4 + cq) * 8 + 4, ab);
 }
-AB_HD void ln_par_fin(const float* part, int nparts, int d, int c, float* dgamma, float* dbeta) {
+RT_HD void ln_par_fin(const float* part, int nparts, int d, int c, float* dgamma, float* dbeta) {
     if (c >= d) return;
     double sg = 0.0, sb = 0.0;
     for (int p = 0; p < nparts; ++p) {
@@ -363,14 +358,14 @@ AB_HD void ln_par_fin(const float* part, int nparts, int d, int c, float* dgamma
 
 // ---------------------------------------------------------------------------------------------
 // GELU, the erf form: y = x Phi(x), Phi(x) = erfc(-x / sqrt 2) / 2 (erfc keeps the negative tail's digits);  dx = dy (Phi(x) + x phi(x))
-AB_HD float gelu_phi_cdf(float x) { return 0.5f * erfcf(-x * 0.70710678118654752440f); }
-AB_HD void gelu_fwd_quad(const float* x, long long t, float* y) {
-    ab_f4 a = ab_ld(x + t * 4);
+RT_HD float gelu_phi_cdf(float x) { return 0.5f * erfcf(-x * 0.70710678118654752440f); }
+RT_HD void gelu_fwd_quad(const float* x, long long t, float* y) {
+    rt_f4 a = rt_ld(x + t * 4);
     a.x *= gelu_phi_cdf(a.x); a.y *= gelu_phi_cdf(a.y); a.z *= gelu_phi_cdf(a.z); a.w *= gelu_phi_cdf(a.w);
-    ab_st(y + t * 4, a);
+    rt_st(y + t * 4, a);
 }
-AB_HD float gelu_grad(float x) { return fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), gelu_phi_cdf(x)); }
-AB_HD void gelu_bwd_quad(const float* dy, const float* x, long long t, float* dx) {
-    const ab_f4 g = ab_ld(dy + t * 4), a = ab_ld(x + t * 4);
-    ab_st(dx + t * 4, ab_f4{g.x * gelu_grad(a.x), g.y * gelu_grad(a.y), g.z * gelu_grad(a.z), g.w * gelu_grad(a.w)});
+RT_HD float gelu_grad(float x) { return fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), gelu_phi_cdf(x)); }
+RT_HD void gelu_bwd_quad(const float* dy, const float* x, long long t, float* dx) {
+    const rt_f4 g = rt_ld(dy + t * 4), a = rt_ld(x + t * 4);
+    rt_st(dx + t * 4, rt_f4{g.x * gelu_grad(a.x), g.y * gelu_grad(a.y), g.z * gelu_grad(a.z), g.w * gelu_grad(a.w)});
 }

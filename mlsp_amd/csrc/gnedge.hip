@@ -16,25 +16,9 @@
 #include "common.h"
 #include "gnedge_body.h"
 
-#define GE_GRID_MAX (1 << 20)
-
-// rows x c4 work items in tiles of `rb` rows: a workgroup strides the tiles, its threads the items of a tile
-struct GeTiles { int rb; long long ntiles; int grid; };
-static inline GeTiles ge_tiles(long long rows, int c4) {
-    GeTiles t;
-    t.rb = c4 >= 1024 ? 1 : 1024 / c4;
-    t.ntiles = (rows + t.rb - 1) / t.rb;
-    t.grid = (int)(t.ntiles < GE_GRID_MAX ? t.ntiles : GE_GRID_MAX);
-    return t;
-}
-#define GE_FOR_ITEMS(rows_, rb_, c4_)                                                                                      \
-    for (long long r0_ = (long long)blockIdx.x * (rb_); r0_ < (rows_); r0_ += (long long)gridDim.x * (rb_))                \
-        for (int it_ = threadIdx.x, n_ = (int)(((rows_) - r0_ < (rb_) ? (rows_) - r0_ : (long long)(rb_)) * (c4_)); it_ < n_; \
-             it_ += GE_THREADS)
-
 // workgroup (p, b) = blockIdx.x % np, blockIdx.x / np
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_stats_kernel(GeGeo g, double* __restrict__ part) {
-    __shared__ double sh[GE_THREADS * 2];
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_stats_kernel(GeGeo g, double* __restrict__ part) {
+    __shared__ double sh[RT_THREADS * 2];
     const int b = blockIdx.x / g.np, p = blockIdx.x - b * g.np;
     for (int cq0 = 0; cq0 < g.c4; cq0 += g.ct) {
         ge_stats_1(g, b, p, cq0, threadIdx.x, sh);
@@ -43,21 +27,21 @@ __global__ __launch_bounds__(GE_THREADS) void gn_edge_stats_kernel(GeGeo g, doub
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_stats_finalize_kernel(GeGeo g, const double* __restrict__ part, float* __restrict__ stats) {
-    ge_stats_fin(g, (long long)blockIdx.x * GE_THREADS + threadIdx.x, part, stats);
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_stats_finalize_kernel(GeGeo g, const double* __restrict__ part, float* __restrict__ stats) {
+    ge_stats_fin(g, (long long)blockIdx.x * RT_THREADS + threadIdx.x, part, stats);
 }
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_apply_kernel(GeGeo g, int rb, const float* __restrict__ stats, float* __restrict__ out,
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_apply_kernel(GeGeo g, int rb, const float* __restrict__ stats, float* __restrict__ out,
                                                                    uint8_t* __restrict__ argk) {
     const long long P = (long long)g.B * g.Nq;
-    GE_FOR_ITEMS(P, rb, g.c4) {
+    RT_FOR_ITEMS(P, rb, g.c4, RT_THREADS) {
         const int lr = it_ / g.c4;
         ge_apply_item(g, r0_ + lr, it_ - lr * g.c4, stats, out, argk);
     }
 }
 
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_bsum_kernel(GeGeo g, const float* __restrict__ stats, const float* __restrict__ dOut,
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_bsum_kernel(GeGeo g, const float* __restrict__ stats, const float* __restrict__ dOut,
                                                                   const uint8_t* __restrict__ argk, float* __restrict__ chpart) {
-    __shared__ __attribute__((aligned(16))) float sh[GE_THREADS * 8];
+    __shared__ __attribute__((aligned(16))) float sh[RT_THREADS * 8];
     const int b = blockIdx.x / g.np, p = blockIdx.x - b * g.np;
     for (int cq0 = 0; cq0 < g.c4; cq0 += g.ct) {
         ge_bsum_1(g, b, p, cq0, threadIdx.x, stats, dOut, argk, sh);
@@ -67,41 +51,40 @@ __global__ __launch_bounds__(GE_THREADS) void gn_edge_bsum_kernel(GeGeo g, const
     }
 }
 // a workgroup per cloud; `cloud` is written in phase 1 and read in phase 2 by other threads of the same workgroup
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_bfin_cloud_kernel(GeGeo g, const float* __restrict__ chpart, double* cloud, float* __restrict__ ab) {
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_bfin_cloud_kernel(GeGeo g, const float* __restrict__ chpart, double* cloud, float* __restrict__ ab) {
     ge_bfin_1(g, blockIdx.x, threadIdx.x, chpart, cloud);
     __threadfence_block();
     __syncthreads();
     ge_bfin_2(g, blockIdx.x, threadIdx.x, cloud, ab);
 }
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_bfin_param_kernel(GeGeo g, const double* __restrict__ cloud, float* __restrict__ dgamma,
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_bfin_param_kernel(GeGeo g, const double* __restrict__ cloud, float* __restrict__ dgamma,
                                                                         float* __restrict__ dbeta) {
-    ge_bfin_param(g, blockIdx.x * GE_THREADS + threadIdx.x, cloud, dgamma, dbeta);
+    ge_bfin_param(g, blockIdx.x * RT_THREADS + threadIdx.x, cloud, dgamma, dbeta);
 }
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_bwd_dw_kernel(GeGeo g, int rb, const float* __restrict__ stats, const float* __restrict__ ab,
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_bwd_dw_kernel(GeGeo g, int rb, const float* __restrict__ stats, const float* __restrict__ ab,
                                                                     const float* __restrict__ dOut, const uint8_t* __restrict__ argk,
                                                                     float* __restrict__ dw) {
     const long long P = (long long)g.B * g.Nq;
-    GE_FOR_ITEMS(P, rb, g.c4) {
+    RT_FOR_ITEMS(P, rb, g.c4, RT_THREADS) {
         const int lr = it_ / g.c4;
         ge_bwd_dw_item(g, r0_ + lr, it_ - lr * g.c4, stats, ab, dOut, argk, dw);
     }
 }
-__global__ __launch_bounds__(GE_THREADS) void gn_edge_bwd_du_kernel(GeGeo g, int rb, const float* __restrict__ stats, const float* __restrict__ ab,
+__global__ __launch_bounds__(RT_THREADS) void gn_edge_bwd_du_kernel(GeGeo g, int rb, const float* __restrict__ stats, const float* __restrict__ ab,
                                                                     const float* __restrict__ dOut, const uint8_t* __restrict__ argk,
                                                                     const int* __restrict__ rev_off, const int* __restrict__ rev_ent,
                                                                     float* __restrict__ du) {
     const long long P = (long long)g.B * g.Nk;
-    GE_FOR_ITEMS(P, rb, g.c4) {
+    RT_FOR_ITEMS(P, rb, g.c4, RT_THREADS) {
         const int lr = it_ / g.c4;
         ge_bwd_du_item(g, r0_ + lr, it_ - lr * g.c4, stats, ab, dOut, argk, rev_off, rev_ent, du);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-static inline bool ge_al(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool ge_setup(const float* u, int ldu, const float* w, int ldw, const int* idx, const float* gamma, const float* beta, int B, int Nk,
                             int Nq, int k, int C, int groups, float eps, float slope, GeGeo& g) {
-    if (!ge_geo(B, Nk, Nq, k, C, groups, ldu, ldw, eps, slope, g) || !ge_al(u) || !ge_al(w) || !ge_al(gamma) || !ge_al(beta)) return false;
+    if (!ge_geo(B, Nk, Nq, k, C, groups, ldu, ldw, eps, slope, g) || !al16(u, w, gamma, beta)) return false;
     g.u = u; g.w = w; g.idx = idx; g.gamma = gamma; g.beta = beta;
     return true;
 }
@@ -117,30 +100,30 @@ int launch_gn_edge_fwd(hipStream_t st, const float* u, int ldu, const float* w, 
                        int B, int Nk, int Nq, int k, int C, int groups, float eps, float slope, float* out, uint8_t* argk, float* stats,
                        Workspace& ws) {
     GeGeo g;
-    if (!ge_setup(u, ldu, w, ldw, idx, gamma, beta, B, Nk, Nq, k, C, groups, eps, slope, g) || !ge_al(out)) return MLSP_ERR_UNSUPPORTED;
+    if (!ge_setup(u, ldu, w, ldw, idx, gamma, beta, B, Nk, Nq, k, C, groups, eps, slope, g) || !al16(out)) return MLSP_ERR_UNSUPPORTED;
     double* part = ws.take<double>(ge_fwd_ws_doubles(g));
     if (!ws.ok()) return MLSP_ERR_WORKSPACE;
-    const GeTiles t = ge_tiles((long long)B * Nq, g.c4);
-    hipLaunchKernelGGL(gn_edge_stats_kernel, dim3(B * g.np), dim3(GE_THREADS), 0, st, g, part);
-    hipLaunchKernelGGL(gn_edge_stats_finalize_kernel, dim3((B * groups + GE_THREADS - 1) / GE_THREADS), dim3(GE_THREADS), 0, st, g, part, stats);
-    hipLaunchKernelGGL(gn_edge_apply_kernel, dim3(t.grid), dim3(GE_THREADS), 0, st, g, t.rb, stats, out, argk);
+    const RowTiles t = row_tiles((long long)B * Nq, g.c4);
+    hipLaunchKernelGGL(gn_edge_stats_kernel, dim3(B * g.np), dim3(RT_THREADS), 0, st, g, part);
+    hipLaunchKernelGGL(gn_edge_stats_finalize_kernel, dim3((B * groups + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, st, g, part, stats);
+    hipLaunchKernelGGL(gn_edge_apply_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, g, t.rb, stats, out, argk);
     return mlsp_launch_status();
 }
 int launch_gn_edge_bwd(hipStream_t st, const float* dOut, const float* u, int ldu, const float* w, int ldw, const int* idx, const uint8_t* argk,
                        const float* stats, const int* rev_off, const int* rev_ent, const float* gamma, const float* beta, int B, int Nk, int Nq,
                        int k, int C, int groups, float slope, float* du, float* dw, float* dgamma, float* dbeta, Workspace& ws) {
     GeGeo g;
-    if (!ge_setup(u, ldu, w, ldw, idx, gamma, beta, B, Nk, Nq, k, C, groups, 0.f, slope, g) || !ge_al(dOut) || !ge_al(du) || !ge_al(dw))
+    if (!ge_setup(u, ldu, w, ldw, idx, gamma, beta, B, Nk, Nq, k, C, groups, 0.f, slope, g) || !al16(dOut, du, dw))
         return MLSP_ERR_UNSUPPORTED;
     float* chpart = ws.take<float>(ge_bwd_ws_floats(g));
     double* cloud = ws.take<double>(ge_bwd_ws_doubles(g));
     float* ab = ws.take<float>((size_t)B * groups * 2);
     if (!ws.ok()) return MLSP_ERR_WORKSPACE;
-    hipLaunchKernelGGL(gn_edge_bsum_kernel, dim3(B * g.np), dim3(GE_THREADS), 0, st, g, stats, dOut, argk, chpart);
-    hipLaunchKernelGGL(gn_edge_bfin_cloud_kernel, dim3(B), dim3(GE_THREADS), 0, st, g, chpart, cloud, ab);
-    hipLaunchKernelGGL(gn_edge_bfin_param_kernel, dim3((C + GE_THREADS - 1) / GE_THREADS), dim3(GE_THREADS), 0, st, g, cloud, dgamma, dbeta);
-    const GeTiles tq = ge_tiles((long long)B * Nq, g.c4), tk = ge_tiles((long long)B * Nk, g.c4);
-    hipLaunchKernelGGL(gn_edge_bwd_dw_kernel, dim3(tq.grid), dim3(GE_THREADS), 0, st, g, tq.rb, stats, ab, dOut, argk, dw);
-    hipLaunchKernelGGL(gn_edge_bwd_du_kernel, dim3(tk.grid), dim3(GE_THREADS), 0, st, g, tk.rb, stats, ab, dOut, argk, rev_off, rev_ent, du);
+    hipLaunchKernelGGL(gn_edge_bsum_kernel, dim3(B * g.np), dim3(RT_THREADS), 0, st, g, stats, dOut, argk, chpart);
+    hipLaunchKernelGGL(gn_edge_bfin_cloud_kernel, dim3(B), dim3(RT_THREADS), 0, st, g, chpart, cloud, ab);
+    hipLaunchKernelGGL(gn_edge_bfin_param_kernel, dim3((C + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, st, g, cloud, dgamma, dbeta);
+    const RowTiles tq = row_tiles((long long)B * Nq, g.c4), tk = row_tiles((long long)B * Nk, g.c4);
+    hipLaunchKernelGGL(gn_edge_bwd_dw_kernel, dim3(tq.grid), dim3(RT_THREADS), 0, st, g, tq.rb, stats, ab, dOut, argk, dw);
+    hipLaunchKernelGGL(gn_edge_bwd_du_kernel, dim3(tk.grid), dim3(RT_THREADS), 0, st, g, tk.rb, stats, ab, dOut, argk, rev_off, rev_ent, du);
     return mlsp_launch_status();
 }

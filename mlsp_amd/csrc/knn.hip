@@ -1589,8 +1589,8 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
     }
 }
 
-static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent, int rank_sort,
-                          int skip_pad = 0, int* rev_cnt = nullptr) {
+static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent, int skip_pad = 0,
+                          int* rev_cnt = nullptr) {
     if (!idx || !rev_off || !rev_ent || B <= 0 || N <= 0 || S <= 0 || k <= 0 || k > 256 || N > (1 << 22) || S > (1 << 22)) return MLSP_ERR_ARG;
     const int nsplit = B * 8 >= 256 || N < 1024 ? 8 : RV_SPLIT_MAX;
     const int dper = (N + nsplit - 1) / nsplit;
@@ -1604,9 +1604,9 @@ static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, i
     return mlsp_launch_status();
 }
 
-// ball-query groups (padded with copies of the first hit): skewed in-degrees -> rank-based ordering
+// ball-query groups (padded with copies of the first hit)
 int launch_group_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent) {
-    return launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, 1);
+    return launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent);
 }
 // the same without the padding slots; pad_cnt [B*S] = number of padding slots of every group (s > 0 with idx[i][s] == idx[i][0])
 __global__ __launch_bounds__(256) void group_pad_count_kernel(const int* __restrict__ idx, int G, int k, int* __restrict__ pad_cnt) {
@@ -1621,11 +1621,11 @@ __global__ __launch_bounds__(256) void group_pad_count_kernel(const int* __restr
 int launch_group_reverse_compact(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_cnt, int* rev_ent,
                                  int* pad_cnt) {
     if (!rev_cnt || !pad_cnt) return MLSP_ERR_ARG;
-    const int rc = launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, 1, 1, rev_cnt);
+    const int rc = launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, 1, rev_cnt);
     if (rc != MLSP_OK) return rc;
     hipLaunchKernelGGL(group_pad_count_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, idx, B * S, k, pad_cnt);
     return mlsp_launch_status();
 }
 int launch_knn_reverse(hipStream_t st, const int* idx, int B, int N, int k, int* rev_off, int* rev_ent) {
-    return launch_reverse(st, idx, B, N, N, k, rev_off, rev_ent, 0);
+    return launch_reverse(st, idx, B, N, N, k, rev_off, rev_ent);
 }

@@ -11,6 +11,7 @@
 //
 // fp32 VALU FMAs: the arithmetic is negligible (<= 16 FMAs per loaded or stored float).
 #include "common.h"
+#include "rowtile.h"
 
 // ---------------------------------------------------------------------------------------------- small K
 // thread = (row, column quad); lanes of a wave cover consecutive quads of a row (16-byte coalesced stores), the K values of the row
@@ -317,7 +318,6 @@ int thin_bs_parts(int M, int N, int K) {
 int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                      int ldc, const GemmOpts& o) {
     const float* const bias = o.bias; float* const slab = o.slab; const size_t slab_floats = o.slab_floats; const GemmXf* const xf = o.xf; const GemmBs* const bs = o.bs;
-    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     XfDev xd = {nullptr, nullptr, 1.f, 1.f, 0u, 0u, 0, 0};
     if (xf) {
         if ((xf->ld & 3) || (xf->col & 3) || !al16(xf->scale) || !al16(xf->shift) || (double)(xf->which == 1 ? M : K) * xf->ld >= 17179869184.0) return MLSP_ERR_UNSUPPORTED;
@@ -394,7 +394,6 @@ int launch_thin_gemm(hipStream_t st, bool ta, bool tb, int M, int N, int K, cons
 // does launch_thin_gemm take this contraction WITH an operand transform on `which` (1: A of the small-N kernel, 2: the wide B of A^T B)?
 // (conditions of the two branches above; the slab is the caller's: gemm_slab_floats covers thin_tn_slab_floats)
 bool thin_xf_supported(bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which) {
-    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     if (which == 1) return !ta && N <= 16 && K % 4 == 0 && K >= 64 && K <= 1024 && M >= 1024 && lda % 4 == 0 && al16(A);
     if (which == 2) return ta && !tb && thin_tn_slab_floats(M, N, K) != 0 && M <= 16 && N % 4 == 0 && N >= 64 && ldb % 4 == 0 && al16(B);
     return false;

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(TK_MOM_THREADS) void thin_in_moments_kernel(TkGeo g
     tk_mom_2(g, blockIdx.x, threadIdx.x, sh, part);
 }
 // one workgroup; xmom / bn_save are written in one phase and read in the next by other threads of the same workgroup
-__global__ __launch_bounds__(TK_THREADS) void thin_in_finalize_kernel(TkGeo g, const double* __restrict__ part, double* xmom, float* bn_save,
+__global__ __launch_bounds__(RT_THREADS) void thin_in_finalize_kernel(TkGeo g, const double* __restrict__ part, double* xmom, float* bn_save,
                                                                       float* run_mean, float* run_var) {
     __shared__ double sh[TK_NMOM];
     tk_fin_1(g, threadIdx.x, part, sh);
@@ -35,50 +35,46 @@ __global__ __launch_bounds__(TK_THREADS) void thin_in_finalize_kernel(TkGeo g, c
     __syncthreads();
     tk_fin_3(g, threadIdx.x, xmom, bn_save, run_mean, run_var);
 }
-__global__ __launch_bounds__(TK_THREADS) void thin_in_running_kernel(TkGeo g, const float* __restrict__ run_mean, const float* __restrict__ run_var,
+__global__ __launch_bounds__(RT_THREADS) void thin_in_running_kernel(TkGeo g, const float* __restrict__ run_mean, const float* __restrict__ run_var,
                                                                      float* __restrict__ bn_save) {
-    tk_running_item(g, blockIdx.x * TK_THREADS + threadIdx.x, run_mean, run_var, bn_save);
+    tk_running_item(g, blockIdx.x * RT_THREADS + threadIdx.x, run_mean, run_var, bn_save);
 }
 template <int KC, int MODE>
-__global__ __launch_bounds__(TK_THREADS) void thin_in_apply_kernel(TkGeo g, const float* __restrict__ bn_save, const double* __restrict__ xmom,
+__global__ __launch_bounds__(RT_THREADS) void thin_in_apply_kernel(TkGeo g, const float* __restrict__ bn_save, const double* __restrict__ xmom,
                                                                    float* __restrict__ H) {
     tk_apply<KC, MODE>(g, blockIdx.x, blockIdx.y * g.ct, threadIdx.x, bn_save, xmom, H);
 }
 template <int KC, int MODE>
-__global__ __launch_bounds__(TK_THREADS) void thin_in_bwd_sums_kernel(TkGeo g, const float* __restrict__ bn_save, const double* __restrict__ xmom,
+__global__ __launch_bounds__(RT_THREADS) void thin_in_bwd_sums_kernel(TkGeo g, const float* __restrict__ bn_save, const double* __restrict__ xmom,
                                                                       const float* __restrict__ dH, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float sh[TK_THREADS * (2 + KC) * 4];
+    __shared__ __attribute__((aligned(16))) float sh[RT_THREADS * (2 + KC) * 4];
     tk_bwd_1<KC, MODE>(g, blockIdx.x, blockIdx.y * g.ct, threadIdx.x, bn_save, xmom, dH, sh);
     __syncthreads();
     tk_bwd_2(g, blockIdx.x, blockIdx.y * g.ct, threadIdx.x, sh, part);
 }
-__global__ __launch_bounds__(TK_THREADS) void thin_in_bwd_finalize_kernel(TkGeo g, const float* __restrict__ part, const float* __restrict__ bn_save,
+__global__ __launch_bounds__(RT_THREADS) void thin_in_bwd_finalize_kernel(TkGeo g, const float* __restrict__ part, const float* __restrict__ bn_save,
                                                                           const double* __restrict__ xmom, float* __restrict__ dW,
                                                                           float* __restrict__ db, float* __restrict__ dgamma,
                                                                           float* __restrict__ dbeta) {
-    tk_bwd_fin(g, blockIdx.x * TK_THREADS + threadIdx.x, part, bn_save, xmom, dW, db, dgamma, dbeta);
+    tk_bwd_fin(g, blockIdx.x * RT_THREADS + threadIdx.x, part, bn_save, xmom, dW, db, dgamma, dbeta);
 }
 
 // workgroup (b, quad block) = blockIdx.x / nqb, blockIdx.x % nqb
-__global__ __launch_bounds__(TK_THREADS) void token_pool_fwd_kernel(TpGeo g, const float* __restrict__ y, float* __restrict__ out,
+__global__ __launch_bounds__(RT_THREADS) void token_pool_fwd_kernel(TpGeo g, const float* __restrict__ y, float* __restrict__ out,
                                                                     int* __restrict__ arg) {
-    __shared__ __attribute__((aligned(16))) float sh_v[TK_THREADS * 4];
-    __shared__ __attribute__((aligned(16))) int sh_a[TK_THREADS * 4];
+    __shared__ __attribute__((aligned(16))) float sh_v[RT_THREADS * 4];
+    __shared__ __attribute__((aligned(16))) int sh_a[RT_THREADS * 4];
     const int b = blockIdx.x / g.nqb, cq0 = (blockIdx.x - b * g.nqb) * g.ct;
     tp_fwd_1(g, b, cq0, threadIdx.x, y, sh_v, sh_a);
     __syncthreads();
     tp_fwd_2(g, b, cq0, threadIdx.x, y, sh_v, sh_a, out, arg);
 }
-// rows x c4 work items in tiles of `rb` rows: a workgroup strides the tiles, its threads the items of a tile
-__global__ __launch_bounds__(TK_THREADS) void token_pool_bwd_kernel(TpGeo g, int rb, const float* __restrict__ dOut, const int* __restrict__ arg,
+__global__ __launch_bounds__(RT_THREADS) void token_pool_bwd_kernel(TpGeo g, int rb, const float* __restrict__ dOut, const int* __restrict__ arg,
                                                                     float* __restrict__ dy) {
     const long long rows = (long long)g.B * g.L;
-    for (long long r0 = (long long)blockIdx.x * rb; r0 < rows; r0 += (long long)gridDim.x * rb) {
-        const int n = (int)((rows - r0 < rb ? rows - r0 : (long long)rb) * g.c4);
-        for (int it = threadIdx.x; it < n; it += TK_THREADS) {
-            const int lr = it / g.c4;
-            tp_bwd_item(g, r0 + lr, it - lr * g.c4, dOut, arg, dy);
-        }
+    RT_FOR_ITEMS(rows, rb, g.c4, RT_THREADS) {
+        const int lr = it_ / g.c4;
+        tp_bwd_item(g, r0_ + lr, it_ - lr * g.c4, dOut, arg, dy);
     }
 }
 
@@ -88,20 +84,19 @@ __global__ __launch_bounds__(TK_THREADS) void token_pool_bwd_kernel(TpGeo g, int
     do {                                                                                                                                  \
         const dim3 grid_((np_), ((g_).c4 + (g_).ct - 1) / (g_).ct);                                                                     \
         if ((g_).kc == 4) {                                                                                                               \
-            if ((g_).mode == TK_MODE_BATCH) hipLaunchKernelGGL((kern_<4, TK_MODE_BATCH>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__);   \
-            else if ((g_).mode == TK_MODE_RUNNING) hipLaunchKernelGGL((kern_<4, TK_MODE_RUNNING>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__); \
-            else hipLaunchKernelGGL((kern_<4, TK_MODE_PLAIN>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__);                              \
+            if ((g_).mode == TK_MODE_BATCH) hipLaunchKernelGGL((kern_<4, TK_MODE_BATCH>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__);   \
+            else if ((g_).mode == TK_MODE_RUNNING) hipLaunchKernelGGL((kern_<4, TK_MODE_RUNNING>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__); \
+            else hipLaunchKernelGGL((kern_<4, TK_MODE_PLAIN>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__);                              \
         } else {                                                                                                                          \
-            if ((g_).mode == TK_MODE_BATCH) hipLaunchKernelGGL((kern_<8, TK_MODE_BATCH>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__);   \
-            else if ((g_).mode == TK_MODE_RUNNING) hipLaunchKernelGGL((kern_<8, TK_MODE_RUNNING>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__); \
-            else hipLaunchKernelGGL((kern_<8, TK_MODE_PLAIN>), grid_, dim3(TK_THREADS), 0, st, __VA_ARGS__);                              \
+            if ((g_).mode == TK_MODE_BATCH) hipLaunchKernelGGL((kern_<8, TK_MODE_BATCH>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__);   \
+            else if ((g_).mode == TK_MODE_RUNNING) hipLaunchKernelGGL((kern_<8, TK_MODE_RUNNING>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__); \
+            else hipLaunchKernelGGL((kern_<8, TK_MODE_PLAIN>), grid_, dim3(RT_THREADS), 0, st, __VA_ARGS__);                              \
         }                                                                                                                                 \
     } while (0)
-static inline bool tk_al(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool tk_setup(const float* X, int ldx, int M, int Cin, const float* W, const float* bias, int C, const float* gamma, const float* beta,
                             int training, int act, float eps, float momentum, TkGeo& g) {
     const int mode = !gamma ? TK_MODE_PLAIN : training ? TK_MODE_BATCH : TK_MODE_RUNNING;
-    if (!tk_geo(M, Cin, C, ldx, act, mode, eps, momentum, g) || !tk_al(bias) || !tk_al(gamma) || !tk_al(beta)) return false;
+    if (!tk_geo(M, Cin, C, ldx, act, mode, eps, momentum, g) || !al16(bias, gamma, beta)) return false;
     g.X = X; g.W = W; g.bias = bias; g.gamma = gamma; g.beta = beta;
     return true;
 }
@@ -115,15 +110,15 @@ int launch_thin_in_fwd(hipStream_t st, const float* X, int ldx, int M, int Cin, 
                        const float* beta, float* run_mean, float* run_var, float momentum, float eps, int training, int act, float* H,
                        float* bn_save, double* xmom, Workspace& ws) {
     TkGeo g;
-    if (!tk_setup(X, ldx, M, Cin, W, bias, C, gamma, beta, training, act, eps, momentum, g) || !tk_al(H) || !tk_al(bn_save)) return MLSP_ERR_UNSUPPORTED;
+    if (!tk_setup(X, ldx, M, Cin, W, bias, C, gamma, beta, training, act, eps, momentum, g) || !al16(H, bn_save)) return MLSP_ERR_UNSUPPORTED;
     if (g.mode == TK_MODE_BATCH) {
         double* part = ws.take<double>(tk_fwd_ws_doubles(g));
         if (!ws.ok()) return MLSP_ERR_WORKSPACE;
         if (g.kc == 4) hipLaunchKernelGGL(thin_in_moments_kernel<4>, dim3(g.m_np), dim3(TK_MOM_THREADS), 0, st, g, part);
         else hipLaunchKernelGGL(thin_in_moments_kernel<8>, dim3(g.m_np), dim3(TK_MOM_THREADS), 0, st, g, part);
-        hipLaunchKernelGGL(thin_in_finalize_kernel, dim3(1), dim3(TK_THREADS), 0, st, g, part, xmom, bn_save, run_mean, run_var);
+        hipLaunchKernelGGL(thin_in_finalize_kernel, dim3(1), dim3(RT_THREADS), 0, st, g, part, xmom, bn_save, run_mean, run_var);
     } else if (g.mode == TK_MODE_RUNNING) {
-        hipLaunchKernelGGL(thin_in_running_kernel, dim3((C + TK_THREADS - 1) / TK_THREADS), dim3(TK_THREADS), 0, st, g, run_mean, run_var, bn_save);
+        hipLaunchKernelGGL(thin_in_running_kernel, dim3((C + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, st, g, run_mean, run_var, bn_save);
     }
     TK_PICK(thin_in_apply_kernel, g, g.a_np, g, bn_save, xmom, H);
     return mlsp_launch_status();
@@ -132,27 +127,25 @@ int launch_thin_in_bwd(hipStream_t st, const float* dH, const float* X, int ldx,
                        const float* gamma, const float* beta, const float* bn_save, const double* xmom, int training, int act, float* dW,
                        float* db, float* dgamma, float* dbeta, Workspace& ws) {
     TkGeo g;
-    if (!tk_setup(X, ldx, M, Cin, W, bias, C, gamma, beta, training, act, 0.f, 0.f, g) || !tk_al(dH) || !tk_al(bn_save)) return MLSP_ERR_UNSUPPORTED;
+    if (!tk_setup(X, ldx, M, Cin, W, bias, C, gamma, beta, training, act, 0.f, 0.f, g) || !al16(dH, bn_save)) return MLSP_ERR_UNSUPPORTED;
     float* part = ws.take<float>(tk_bwd_ws_floats(g));
     if (!ws.ok()) return MLSP_ERR_WORKSPACE;
     TK_PICK(thin_in_bwd_sums_kernel, g, g.b_np, g, bn_save, xmom, dH, part);
-    hipLaunchKernelGGL(thin_in_bwd_finalize_kernel, dim3((C + TK_THREADS - 1) / TK_THREADS), dim3(TK_THREADS), 0, st, g, part, bn_save, xmom, dW, db,
+    hipLaunchKernelGGL(thin_in_bwd_finalize_kernel, dim3((C + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, st, g, part, bn_save, xmom, dW, db,
                        dgamma, dbeta);
     return mlsp_launch_status();
 }
 
-#define TP_GRID_MAX (1 << 20)
 int launch_token_pool_fwd(hipStream_t st, const float* y, int B, int L, int d, float* out, int* arg) {
     TpGeo g;
-    if (!tp_geo(B, L, d, g) || !tk_al(y) || !tk_al(out) || !tk_al(arg)) return MLSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(token_pool_fwd_kernel, dim3(B * g.nqb), dim3(TK_THREADS), 0, st, g, y, out, arg);
+    if (!tp_geo(B, L, d, g) || !al16(y, out, arg)) return MLSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(token_pool_fwd_kernel, dim3(B * g.nqb), dim3(RT_THREADS), 0, st, g, y, out, arg);
     return mlsp_launch_status();
 }
 int launch_token_pool_bwd(hipStream_t st, const float* dOut, const int* arg, int B, int L, int d, float* dy) {
     TpGeo g;
-    if (!tp_geo(B, L, d, g) || !tk_al(dOut) || !tk_al(arg) || !tk_al(dy)) return MLSP_ERR_UNSUPPORTED;
-    const int rb = g.c4 >= 1024 ? 1 : 1024 / g.c4;
-    const long long ntiles = ((long long)B * L + rb - 1) / rb;
-    hipLaunchKernelGGL(token_pool_bwd_kernel, dim3((int)(ntiles < TP_GRID_MAX ? ntiles : TP_GRID_MAX)), dim3(TK_THREADS), 0, st, g, rb, dOut, arg, dy);
+    if (!tp_geo(B, L, d, g) || !al16(dOut, arg, dy)) return MLSP_ERR_UNSUPPORTED;
+    const RowTiles t = row_tiles((long long)B * L, g.c4);
+    hipLaunchKernelGGL(token_pool_bwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, g, t.rb, dOut, arg, dy);
     return mlsp_launch_status();
 }

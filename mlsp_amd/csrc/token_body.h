@@ -10,9 +10,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "rowtile.h"
 
-#define TK_HD __host__ __device__ __forceinline__
-#define TK_THREADS 256
 #define TK_MOM_THREADS 64                                  // the moment pass: 44 fp64 accumulators per thread, one wave per workgroup
 #define TK_MAX_CIN 8
 #define TK_NMOM 44                                         // 8 first + 36 second moments (upper triangle)
@@ -25,10 +24,7 @@
 #define TK_MODE_BATCH 1                                    // BatchNorm on batch statistics (training)
 #define TK_MODE_RUNNING 2                                  // BatchNorm on the running buffers (eval)
 
-typedef float tk_f4 __attribute__((ext_vector_type(4)));
 typedef int tk_i4 __attribute__((ext_vector_type(4)));
-TK_HD tk_f4 tk_ld(const float* p) { return *(const tk_f4*)p; }
-TK_HD void tk_st(float* p, const tk_f4& v) { *(tk_f4*)p = v; }
 
 // Threads of a 256-wide workgroup: (row lane rl < nrl, channel quad tc < ct).  Row chunks: a_* of the apply pass, m_* of the moment
 // pass, b_* of the backward sums.  kc: the compile-time input width the kernels run with (4 or 8).
@@ -38,14 +34,14 @@ struct TkGeo {
     float eps, momentum;
     const float *X, *W, *bias, *gamma, *beta;              // bias nullable; gamma / beta NULL in TK_MODE_PLAIN
 };
-TK_HD int tk_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+RT_HD int tk_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 // the geometry of a shape, or false outside the limits
-TK_HD bool tk_geo(int M, int Cin, int C, int ldx, int act, int mode, float eps, float momentum, TkGeo& g) {
+RT_HD bool tk_geo(int M, int Cin, int C, int ldx, int act, int mode, float eps, float momentum, TkGeo& g) {
     if (M < 1 || M > (1 << 30) || Cin < 1 || Cin > TK_MAX_CIN || ldx < Cin || C < 4 || C % 4 || C > 4096) return false;
     if ((act != TK_ACT_NONE && act != TK_ACT_RELU && act != TK_ACT_GELU) || mode < 0 || mode > 2) return false;
     g.M = M; g.Cin = Cin; g.C = C; g.c4 = C / 4; g.ldx = ldx; g.kc = Cin <= 4 ? 4 : 8; g.act = act; g.mode = mode;
-    g.ct = g.c4 < TK_THREADS ? g.c4 : TK_THREADS;
-    g.nrl = TK_THREADS / g.ct;
+    g.ct = g.c4 < RT_THREADS ? g.c4 : RT_THREADS;
+    g.nrl = RT_THREADS / g.ct;
     // apply: about 1024 workgroups at M = 65,536 x C = 128 (8 rows per thread), one row per thread on small M
     long long per = (long long)M / ((long long)g.nrl * 1024);
     per = per < 1 ? 1 : per > 8 ? 8 : per;
@@ -63,9 +59,9 @@ TK_HD bool tk_geo(int M, int Cin, int C, int ldx, int act, int mode, float eps, 
     return true;
 }
 // workspace: the forward's part [m_np][44] doubles; the backward's part [b_np][c4][2 + kc] quads
-TK_HD size_t tk_fwd_ws_doubles(const TkGeo& g) { return (size_t)g.m_np * TK_NMOM; }
-TK_HD size_t tk_bwd_ws_floats(const TkGeo& g) { return (size_t)g.b_np * g.c4 * (2 + g.kc) * 4; }
-TK_HD int tk_tri(int a, int b) { return TK_MAX_CIN + a * TK_MAX_CIN - a * (a - 1) / 2 + (b - a); }     // a <= b < 8
+RT_HD size_t tk_fwd_ws_doubles(const TkGeo& g) { return (size_t)g.m_np * TK_NMOM; }
+RT_HD size_t tk_bwd_ws_floats(const TkGeo& g) { return (size_t)g.b_np * g.c4 * (2 + g.kc) * 4; }
+RT_HD int tk_tri(int a, int b) { return TK_MAX_CIN + a * TK_MAX_CIN - a * (a - 1) / 2 + (b - a); }     // a <= b < 8
 
 // ---------------------------------------------------------------------------------------------
 // Input moments, in double from the first addition, about the pivot x0 = row 0 (d = x - x0: a constant column gives exact zeros and an
@@ -73,7 +69,7 @@ TK_HD int tk_tri(int a, int b) { return TK_MAX_CIN + a * TK_MAX_CIN - a * (a - 1
 // 1: sh[j][tid] = the thread's sums over its rows (j < 44; entries beyond Cin are 0);  2: thread j < 44 adds the 64 lanes in ascending
 // order -> part[wg][j].  LDS: sh [44][64] doubles.
 template <int KC>
-TK_HD void tk_mom_1(const TkGeo& g, int wg, int tid, double* sh) {
+RT_HD void tk_mom_1(const TkGeo& g, int wg, int tid, double* sh) {
     double s1[KC], s2[KC * (KC + 1) / 2], x0[KC];
 #pragma unroll
     for (int a = 0; a < KC; ++a) { s1[a] = 0.0; x0[a] = a < g.Cin ? (double)g.X[a] : 0.0; }
@@ -102,7 +98,7 @@ TK_HD void tk_mom_1(const TkGeo& g, int wg, int tid, double* sh) {
         for (int b = a; b < KC; ++b) sh[tk_tri(a, b) * TK_MOM_THREADS + tid] = s2[n++];
     }
 }
-TK_HD void tk_mom_2(const TkGeo& g, int wg, int tid, const double* sh, double* part) {
+RT_HD void tk_mom_2(const TkGeo& g, int wg, int tid, const double* sh, double* part) {
     if (tid >= TK_NMOM) return;
     double s = 0.0;
     for (int l = 0; l < TK_MOM_THREADS; ++l) s += sh[tid * TK_MOM_THREADS + l];
@@ -111,13 +107,13 @@ TK_HD void tk_mom_2(const TkGeo& g, int wg, int tid, const double* sh, double* p
 // The finaliser, one workgroup of 256.  1: thread j < 44: the chunks in ascending order -> sh[j];  2: thread t < 72: xmom = mu | Sigma;
 // 3: per channel, mean_c = w_c mu + b_c, var_c = w_c^T Sigma w_c -> bn_save = scale | shift | mean | invstd and the running buffers
 // (biased variance to normalise, unbiased for run_var).  LDS: sh [44] doubles.
-TK_HD void tk_fin_1(const TkGeo& g, int tid, const double* part, double* sh) {
+RT_HD void tk_fin_1(const TkGeo& g, int tid, const double* part, double* sh) {
     if (tid >= TK_NMOM) return;
     double s = 0.0;
     for (int p = 0; p < g.m_np; ++p) s += part[(size_t)p * TK_NMOM + tid];
     sh[tid] = s;
 }
-TK_HD void tk_fin_2(const TkGeo& g, int tid, const double* sh, double* xmom) {
+RT_HD void tk_fin_2(const TkGeo& g, int tid, const double* sh, double* xmom) {
     if (tid >= TK_XMOM) return;
     const double inv = 1.0 / (double)g.M;
     if (tid < TK_MAX_CIN) {
@@ -127,8 +123,8 @@ TK_HD void tk_fin_2(const TkGeo& g, int tid, const double* sh, double* xmom) {
     const int a = (tid - TK_MAX_CIN) / TK_MAX_CIN, b = (tid - TK_MAX_CIN) % TK_MAX_CIN, lo = a < b ? a : b, hi = a < b ? b : a;
     xmom[tid] = sh[tk_tri(lo, hi)] * inv - (sh[lo] * inv) * (sh[hi] * inv);
 }
-TK_HD void tk_fin_3(const TkGeo& g, int tid, const double* xmom, float* bn_save, float* run_mean, float* run_var) {
-    for (int c = tid; c < g.C; c += TK_THREADS) {
+RT_HD void tk_fin_3(const TkGeo& g, int tid, const double* xmom, float* bn_save, float* run_mean, float* run_var) {
+    for (int c = tid; c < g.C; c += RT_THREADS) {
         const float* w = g.W + (size_t)c * g.Cin;
         double mean = g.bias ? (double)g.bias[c] : 0.0, var = 0.0;
         for (int a = 0; a < g.Cin; ++a) {
@@ -148,7 +144,7 @@ TK_HD void tk_fin_3(const TkGeo& g, int tid, const double* xmom, float* bn_save,
     }
 }
 // eval mode: bn_save from the running buffers, item c
-TK_HD void tk_running_item(const TkGeo& g, int c, const float* run_mean, const float* run_var, float* bn_save) {
+RT_HD void tk_running_item(const TkGeo& g, int c, const float* run_mean, const float* run_var, float* bn_save) {
     if (c >= g.C) return;
     const double invstd = 1.0 / sqrt((double)run_var[c] + (double)g.eps), scale = (double)g.gamma[c] * invstd;
     bn_save[c] = (float)scale;
@@ -164,10 +160,10 @@ TK_HD void tk_running_item(const TkGeo& g, int c, const float* run_mean, const f
 //   running: A = scale, B = shift, bp = bias, mc = running mean, is = invstd;   plain: A = 1, B = 0, bp = bias
 // MODE is a template argument of everything that runs per row: the three variants differ in which pointers they read at all.
 template <int KC>
-struct TkCh { float w[4][KC], mh[KC], ml[KC]; tk_f4 A, B, bp, mc, is; };
+struct TkCh { float w[4][KC], mh[KC], ml[KC]; rt_f4 A, B, bp, mc, is; };
 template <int KC, int MODE>
-TK_HD void tk_load_ch(const TkGeo& g, int cq, const float* bn_save, const double* xmom, TkCh<KC>& k) {
-    const tk_f4 zero = tk_f4{0.f, 0.f, 0.f, 0.f}, one = tk_f4{1.f, 1.f, 1.f, 1.f};
+RT_HD void tk_load_ch(const TkGeo& g, int cq, const float* bn_save, const double* xmom, TkCh<KC>& k) {
+    const rt_f4 zero = rt_f4{0.f, 0.f, 0.f, 0.f}, one = rt_f4{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -178,22 +174,22 @@ TK_HD void tk_load_ch(const TkGeo& g, int cq, const float* bn_save, const double
         k.mh[a] = (float)mu;
         k.ml[a] = (float)(mu - (double)k.mh[a]);
     }
-    const tk_f4 bias = g.bias ? tk_ld(g.bias + cq * 4) : zero;
+    const rt_f4 bias = g.bias ? rt_ld(g.bias + cq * 4) : zero;
     if (MODE == TK_MODE_BATCH) {
-        k.A = tk_ld(bn_save + cq * 4); k.B = tk_ld(g.beta + cq * 4); k.bp = zero; k.mc = zero; k.is = tk_ld(bn_save + 3 * (size_t)g.C + cq * 4);
+        k.A = rt_ld(bn_save + cq * 4); k.B = rt_ld(g.beta + cq * 4); k.bp = zero; k.mc = zero; k.is = rt_ld(bn_save + 3 * (size_t)g.C + cq * 4);
     } else if (MODE == TK_MODE_RUNNING) {
-        k.A = tk_ld(bn_save + cq * 4); k.B = tk_ld(bn_save + (size_t)g.C + cq * 4); k.bp = bias;
-        k.mc = tk_ld(bn_save + 2 * (size_t)g.C + cq * 4); k.is = tk_ld(bn_save + 3 * (size_t)g.C + cq * 4);
+        k.A = rt_ld(bn_save + cq * 4); k.B = rt_ld(bn_save + (size_t)g.C + cq * 4); k.bp = bias;
+        k.mc = rt_ld(bn_save + 2 * (size_t)g.C + cq * 4); k.is = rt_ld(bn_save + 3 * (size_t)g.C + cq * 4);
     } else {
         k.A = one; k.B = zero; k.bp = bias; k.mc = zero; k.is = zero;
     }
 }
 template <int KC>
-TK_HD tk_f4 tk_u(const TkGeo& g, const TkCh<KC>& k, long long r, float (&xc)[KC]) {
+RT_HD rt_f4 tk_u(const TkGeo& g, const TkCh<KC>& k, long long r, float (&xc)[KC]) {
     const float* p = g.X + r * g.ldx;
 #pragma unroll
     for (int a = 0; a < KC; ++a) xc[a] = a < g.Cin ? (p[a] - k.mh[a]) - k.ml[a] : 0.f;
-    tk_f4 u;
+    rt_f4 u;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         float t = k.w[e][0] * xc[0];
@@ -204,13 +200,13 @@ TK_HD tk_f4 tk_u(const TkGeo& g, const TkCh<KC>& k, long long r, float (&xc)[KC]
     return u;
 }
 // GELU, the erf form of gelu_fwd_kernel: z Phi(z), Phi(z) = erfc(-z / sqrt 2) / 2;  derivative Phi(z) + z phi(z)
-TK_HD float tk_cdf(float z) { return 0.5f * erfcf(-z * 0.70710678118654752440f); }
-TK_HD float tk_act(float z, int act) {
+RT_HD float tk_cdf(float z) { return 0.5f * erfcf(-z * 0.70710678118654752440f); }
+RT_HD float tk_act(float z, int act) {
     if (act == TK_ACT_RELU) return z < 0.f ? 0.f : z;
     if (act == TK_ACT_GELU) return z * tk_cdf(z);
     return z;
 }
-TK_HD float tk_dact(float z, int act) {
+RT_HD float tk_dact(float z, int act) {
     if (act == TK_ACT_RELU) return z > 0.f ? 1.f : 0.f;
     if (act == TK_ACT_GELU) return fmaf(z * 0.39894228040143267794f, expf(-0.5f * z * z), tk_cdf(z));
     return 1.f;
@@ -218,7 +214,7 @@ TK_HD float tk_dact(float z, int act) {
 
 // The apply pass: workgroup wg owns the rows [wg a_chunk, + a_chunk), thread (rl, tc) the quad cq0 + tc of every nrl-th of them.
 template <int KC, int MODE>
-TK_HD void tk_apply(const TkGeo& g, int wg, int cq0, int tid, const float* bn_save, const double* xmom, float* H) {
+RT_HD void tk_apply(const TkGeo& g, int wg, int cq0, int tid, const float* bn_save, const double* xmom, float* H) {
     const int tc = tid % g.ct, rl = tid / g.ct, cq = cq0 + tc;
     if (rl >= g.nrl || cq >= g.c4) return;
     TkCh<KC> k;
@@ -226,11 +222,11 @@ TK_HD void tk_apply(const TkGeo& g, int wg, int cq0, int tid, const float* bn_sa
     const long long r0 = (long long)wg * g.a_chunk, r1 = r0 + g.a_chunk < g.M ? r0 + g.a_chunk : g.M;
     for (long long r = r0 + rl; r < r1; r += g.nrl) {
         float xc[KC];
-        const tk_f4 u = tk_u<KC>(g, k, r, xc);
-        tk_f4 o;
+        const rt_f4 u = tk_u<KC>(g, k, r, xc);
+        rt_f4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = tk_act(u[e] * k.A[e] + k.B[e], g.act);
-        tk_st(H + r * g.C + cq * 4, o);
+        rt_st(H + r * g.C + cq * 4, o);
     }
 }
 
@@ -238,20 +234,20 @@ TK_HD void tk_apply(const TkGeo& g, int wg, int cq0, int tid, const float* bn_sa
 // Backward sums per channel over the rows, y recomputed from X: dz = dH act'(z);  S0 = sum dz, S1 = sum dz yhat, S2[a] = sum dz xc[a].
 // 1: sh[tid][2 + KC] quads = the thread's fp32 sums over its rows;  2: the row lanes in ascending order -> part[wg][cq][2 + KC] quads.
 template <int KC, int MODE>
-TK_HD void tk_bwd_1(const TkGeo& g, int wg, int cq0, int tid, const float* bn_save, const double* xmom, const float* dH, float* sh) {
+RT_HD void tk_bwd_1(const TkGeo& g, int wg, int cq0, int tid, const float* bn_save, const double* xmom, const float* dH, float* sh) {
     const int tc = tid % g.ct, rl = tid / g.ct, cq = cq0 + tc;
     if (rl >= g.nrl || cq >= g.c4) return;
     TkCh<KC> k;
     tk_load_ch<KC, MODE>(g, cq, bn_save, xmom, k);
-    const tk_f4 zero = tk_f4{0.f, 0.f, 0.f, 0.f};
-    tk_f4 s0 = zero, s1 = zero, s2[KC];
+    const rt_f4 zero = rt_f4{0.f, 0.f, 0.f, 0.f};
+    rt_f4 s0 = zero, s1 = zero, s2[KC];
 #pragma unroll
     for (int a = 0; a < KC; ++a) s2[a] = zero;
     const long long r0 = (long long)wg * g.b_chunk, r1 = r0 + g.b_chunk < g.M ? r0 + g.b_chunk : g.M;
     for (long long r = r0 + rl; r < r1; r += g.nrl) {
         float xc[KC];
-        const tk_f4 u = tk_u<KC>(g, k, r, xc), d = tk_ld(dH + r * g.C + cq * 4);
-        tk_f4 dz;
+        const rt_f4 u = tk_u<KC>(g, k, r, xc), d = rt_ld(dH + r * g.C + cq * 4);
+        rt_f4 dz;
 #pragma unroll
         for (int e = 0; e < 4; ++e) dz[e] = d[e] * tk_dact(u[e] * k.A[e] + k.B[e], g.act);
         s0 += dz;
@@ -260,21 +256,21 @@ TK_HD void tk_bwd_1(const TkGeo& g, int wg, int cq0, int tid, const float* bn_sa
         for (int a = 0; a < KC; ++a) s2[a] += dz * xc[a];
     }
     float* dst = sh + (size_t)tid * (2 + KC) * 4;
-    tk_st(dst, s0); tk_st(dst + 4, s1);
+    rt_st(dst, s0); rt_st(dst + 4, s1);
 #pragma unroll
-    for (int a = 0; a < KC; ++a) tk_st(dst + 8 + a * 4, s2[a]);
+    for (int a = 0; a < KC; ++a) rt_st(dst + 8 + a * 4, s2[a]);
 }
-TK_HD void tk_bwd_2(const TkGeo& g, int wg, int cq0, int tid, const float* sh, float* part) {
+RT_HD void tk_bwd_2(const TkGeo& g, int wg, int cq0, int tid, const float* sh, float* part) {
     const int tc = tid % g.ct, rl = tid / g.ct, cq = cq0 + tc, nq = 2 + g.kc;
     if (rl != 0 || cq >= g.c4) return;
     float* dst = part + ((size_t)wg * g.c4 + cq) * nq * 4;
     for (int j = 0; j < nq; ++j) {
-        tk_f4 s = tk_ld(sh + ((size_t)tid * nq + j) * 4);
-        for (int q = 1; q < g.nrl; ++q) s += tk_ld(sh + ((size_t)(q * g.ct + tc) * nq + j) * 4);
-        tk_st(dst + j * 4, s);
+        rt_f4 s = rt_ld(sh + ((size_t)tid * nq + j) * 4);
+        for (int q = 1; q < g.nrl; ++q) s += rt_ld(sh + ((size_t)(q * g.ct + tc) * nq + j) * 4);
+        rt_st(dst + j * 4, s);
     }
 }
-TK_HD double tk_part_sum(const TkGeo& g, const float* part, int c, int j) {          // the chunks in ascending order, in double
+RT_HD double tk_part_sum(const TkGeo& g, const float* part, int c, int j) {          // the chunks in ascending order, in double
     const int nq = 2 + g.kc;
     double s = 0.0;
     for (int p = 0; p < g.b_np; ++p) s += (double)part[(((size_t)p * g.c4 + c / 4) * nq + j) * 4 + c % 4];
@@ -283,7 +279,7 @@ TK_HD double tk_part_sum(const TkGeo& g, const float* part, int c, int j) {     
 // item c.  batch: with dy_i = scale (dz_i - S0 / M - yhat_i S1 / M) and sum_i yhat_i (x_i - mu) = M invstd Sigma w_c,
 //   dW_c = scale (S2 - S1 invstd Sigma w_c), db_c = 0 exactly, dgamma = S1, dbeta = S0;
 // running: dW_c = scale S2, db_c = scale S0;   plain: dW_c = S2, db_c = S0.   db / dgamma / dbeta nullable.
-TK_HD void tk_bwd_fin(const TkGeo& g, int c, const float* part, const float* bn_save, const double* xmom, float* dW, float* db, float* dgamma,
+RT_HD void tk_bwd_fin(const TkGeo& g, int c, const float* part, const float* bn_save, const double* xmom, float* dW, float* db, float* dgamma,
                       float* dbeta) {
     if (c >= g.C) return;
     const double S0 = tk_part_sum(g, part, c, 0), S1 = tk_part_sum(g, part, c, 1);
@@ -312,61 +308,61 @@ TK_HD void tk_bwd_fin(const TkGeo& g, int c, const float* part, const float* bn_
 // Workgroup (cloud b, quad block cq0); thread (rl, tc): 1: its rows 1 + rl, 1 + rl + nrl, ... -> sh_v / sh_a[tid] (arg 0: no row);
 // 2: row lane 0 folds the lanes and writes both halves of out.  LDS: 256 value quads + 256 index quads.
 struct TpGeo { int B, L, d, c4, ct, nrl, nqb; };          // nqb: quad blocks of ct per row
-TK_HD bool tp_geo(int B, int L, int d, TpGeo& g) {
+RT_HD bool tp_geo(int B, int L, int d, TpGeo& g) {
     if (B < 1 || L < 2 || d < 4 || d % 4 || d > (1 << 20) || L > (1 << 24) || (long long)B * L > (1LL << 30)) return false;
     g.B = B; g.L = L; g.d = d; g.c4 = d / 4;
-    g.ct = g.c4 < TK_THREADS ? g.c4 : TK_THREADS;
-    g.nrl = TK_THREADS / g.ct;
+    g.ct = g.c4 < RT_THREADS ? g.c4 : RT_THREADS;
+    g.nrl = RT_THREADS / g.ct;
     g.nqb = (g.c4 + g.ct - 1) / g.ct;
     return (long long)B * g.nqb < (1LL << 31);
 }
-TK_HD bool tp_better(float v, int l, float best, int arg) {             // (v, l) replaces (best, arg)
+RT_HD bool tp_better(float v, int l, float best, int arg) {             // (v, l) replaces (best, arg)
     if (arg == 0) return true;
     return v > best || (best != best && v == v) || (v == best && l < arg) || (v != v && best != best && l < arg);
 }
-TK_HD void tp_fwd_1(const TpGeo& g, int b, int cq0, int tid, const float* y, float* sh_v, int* sh_a) {
+RT_HD void tp_fwd_1(const TpGeo& g, int b, int cq0, int tid, const float* y, float* sh_v, int* sh_a) {
     const int tc = tid % g.ct, rl = tid / g.ct, cq = cq0 + tc;
     if (rl >= g.nrl || cq >= g.c4) return;
-    tk_f4 best = tk_f4{0.f, 0.f, 0.f, 0.f};
+    rt_f4 best = rt_f4{0.f, 0.f, 0.f, 0.f};
     tk_i4 arg = tk_i4{0, 0, 0, 0};
     for (int l = 1 + rl; l < g.L; l += g.nrl) {
-        const tk_f4 v = tk_ld(y + ((long long)b * g.L + l) * g.d + cq * 4);
+        const rt_f4 v = rt_ld(y + ((long long)b * g.L + l) * g.d + cq * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (tp_better(v[e], l, best[e], arg[e])) { best[e] = v[e]; arg[e] = l; }
     }
-    tk_st(sh_v + (size_t)tid * 4, best);
+    rt_st(sh_v + (size_t)tid * 4, best);
     *(tk_i4*)(sh_a + (size_t)tid * 4) = arg;
 }
-TK_HD void tp_fwd_2(const TpGeo& g, int b, int cq0, int tid, const float* y, const float* sh_v, const int* sh_a, float* out, int* arg) {
+RT_HD void tp_fwd_2(const TpGeo& g, int b, int cq0, int tid, const float* y, const float* sh_v, const int* sh_a, float* out, int* arg) {
     const int tc = tid % g.ct, rl = tid / g.ct, cq = cq0 + tc;
     if (rl != 0 || cq >= g.c4) return;
-    tk_f4 best = tk_ld(sh_v + (size_t)tid * 4);
+    rt_f4 best = rt_ld(sh_v + (size_t)tid * 4);
     tk_i4 a = *(const tk_i4*)(sh_a + (size_t)tid * 4);    // (row lane 0 always has row 1)
     for (int q = 1; q < g.nrl; ++q) {
-        const tk_f4 v = tk_ld(sh_v + (size_t)(q * g.ct + tc) * 4);
+        const rt_f4 v = rt_ld(sh_v + (size_t)(q * g.ct + tc) * 4);
         const tk_i4 l = *(const tk_i4*)(sh_a + (size_t)(q * g.ct + tc) * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (l[e] != 0 && tp_better(v[e], l[e], best[e], a[e])) { best[e] = v[e]; a[e] = l[e]; }
     }
     float* o = out + (size_t)b * 2 * g.d;
-    tk_st(o + cq * 4, tk_ld(y + (long long)b * g.L * g.d + cq * 4));
-    tk_st(o + g.d + cq * 4, best);
+    rt_st(o + cq * 4, rt_ld(y + (long long)b * g.L * g.d + cq * 4));
+    rt_st(o + g.d + cq * 4, best);
     *(tk_i4*)(arg + (size_t)b * g.d + cq * 4) = a;
 }
 // dy[r][c]: row 0 of a cloud = the cls half of dOut, row arg = the max half, 0 elsewhere.  Item (row r of B L, quad cq): one writer each.
-TK_HD void tp_bwd_item(const TpGeo& g, long long r, int cq, const float* dOut, const int* arg, float* dy) {
+RT_HD void tp_bwd_item(const TpGeo& g, long long r, int cq, const float* dOut, const int* arg, float* dy) {
     const long long b = r / g.L;
     const int l = (int)(r - b * g.L);
-    tk_f4 o;
+    rt_f4 o;
     if (l == 0) {
-        o = tk_ld(dOut + b * 2 * g.d + cq * 4);
+        o = rt_ld(dOut + b * 2 * g.d + cq * 4);
     } else {
-        const tk_f4 m = tk_ld(dOut + b * 2 * g.d + g.d + cq * 4);
+        const rt_f4 m = rt_ld(dOut + b * 2 * g.d + g.d + cq * 4);
         const tk_i4 a = *(const tk_i4*)(arg + b * g.d + cq * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = a[e] == l ? m[e] : 0.f;
     }
-    tk_st(dy + r * g.d + cq * 4, o);
+    rt_st(dy + r * g.d + cq * 4, o);
 }

@@ -12,42 +12,24 @@
 // Bounds: d % 4 == 0, 1 <= k <= VA_MAX_K, 16-byte-aligned pointers and row pitches.  An index outside [0, N) is read as 0 (never
 // dereferenced out of the cloud).
 #include "common.h"
+#include "rowtile.h"
 #include <math.h>
 
 #define VA_MAX_K 64
-#define VA_THREADS 256
 #define VA_PARTS_MAX 1024
-#define VA_GRID_MAX (1 << 20)
-
-// rows x (d / 4) work items in tiles of `rb` rows: a workgroup strides the tiles, its threads the items of a tile (32-bit arithmetic
-// inside a tile, 64-bit row numbers)
-struct VaTiles { int rb; long long ntiles; int grid; };
-static inline VaTiles va_tiles(long long rows, int d4) {
-    VaTiles t;
-    t.rb = d4 >= 1024 ? 1 : 1024 / d4;
-    t.ntiles = (rows + t.rb - 1) / t.rb;
-    t.grid = (int)(t.ntiles < VA_GRID_MAX ? t.ntiles : VA_GRID_MAX);
-    return t;
-}
-#define VA_FOR_ITEMS(rows_, rb_, d4_)                                                                                      \
-    for (long long r0_ = (long long)blockIdx.x * (rb_); r0_ < (rows_); r0_ += (long long)gridDim.x * (rb_))                \
-        for (int it_ = threadIdx.x, n_ = (int)(((rows_) - r0_ < (rb_) ? (rows_) - r0_ : (long long)(rb_)) * (d4_)); it_ < n_; \
-             it_ += VA_THREADS)
 
 __device__ __forceinline__ int va_nbr(const int* __restrict__ idx, long long e, int N) {
     const int j = idx[e];
     return (unsigned)j < (unsigned)N ? j : 0;
 }
-__device__ __forceinline__ f32x4 va_ld(const float* p) { return *(const f32x4*)p; }
-__device__ __forceinline__ void va_st(float* p, const f32x4& v) { *(f32x4*)p = v; }
 
 // ---------------------------------------------------------------------------------------------
 // H1[e][c] = relu(((r0 W[c][0] + r1 W[c][1]) + r2 W[c][2]) + b[c]) as an fma chain, r = xyz_i - xyz_j subtracted first (:37).
 // Traffic per edge and channel: 4 B written (the coordinates and the 16 d bytes of weights stay in cache).
-__global__ __launch_bounds__(VA_THREADS) void vecattn_delta_fwd_kernel(const float* __restrict__ xyz, int ldx, const int* __restrict__ idx,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_delta_fwd_kernel(const float* __restrict__ xyz, int ldx, const int* __restrict__ idx,
                                                                        const float* __restrict__ Wd1, const float* __restrict__ bd1, int N,
                                                                        int k, int d4, long long E, int rb, float* __restrict__ H1) {
-    VA_FOR_ITEMS(E, rb, d4) {
+    RT_FOR_ITEMS(E, rb, d4, RT_THREADS) {
         const int lr = it_ / d4, cq = it_ - lr * d4;
         const long long e = r0_ + lr, i = e / k, cloud = i / N;
         const long long j = cloud * N + va_nbr(idx, e, N);
@@ -55,14 +37,14 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_delta_fwd_kernel(const flo
         const float* pj = xyz + j * ldx;
         const float r0 = pi[0] - pj[0], r1 = pi[1] - pj[1], r2 = pi[2] - pj[2];
         const float* w = Wd1 + (size_t)cq * 12;         // rows 4 cq .. 4 cq + 3 of [d][3]: 12 contiguous floats
-        const f32x4 w0 = va_ld(w), w1 = va_ld(w + 4), w2 = va_ld(w + 8), b = va_ld(bd1 + cq * 4);
+        const f32x4 w0 = rt_ld(w), w1 = rt_ld(w + 4), w2 = rt_ld(w + 8), b = rt_ld(bd1 + cq * 4);
         f32x4 h;
         h.x = fmaf(r2, w0.z, fmaf(r1, w0.y, r0 * w0.x)) + b.x;
         h.y = fmaf(r2, w1.y, fmaf(r1, w1.x, r0 * w0.w)) + b.y;
         h.z = fmaf(r2, w2.x, fmaf(r1, w1.w, r0 * w1.z)) + b.z;
         h.w = fmaf(r2, w2.w, fmaf(r1, w2.z, r0 * w2.y)) + b.w;
         h.x = fmaxf(h.x, 0.f); h.y = fmaxf(h.y, 0.f); h.z = fmaxf(h.z, 0.f); h.w = fmaxf(h.w, 0.f);
-        va_st(H1 + (e * d4 + cq) * 4, h);
+        rt_st(H1 + (e * d4 + cq) * 4, h);
     }
 }
 
@@ -70,11 +52,11 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_delta_fwd_kernel(const flo
 // its threads are (row lane, channel quad), a thread keeps 4 channels x {r0, r1, r2, 1} in registers over every rl-th edge, the row lanes
 // are summed through LDS in ascending lane order and part[g][c] = {dW[c][0..2], db[c]} is written; the finalising pass sums the parts in
 // ascending g in fp64.  Traffic per edge and channel: 8 B read.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_delta_bwd_kernel(const float* __restrict__ dH1, const float* __restrict__ H1,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_delta_bwd_kernel(const float* __restrict__ dH1, const float* __restrict__ H1,
                                                                        const float* __restrict__ xyz, int ldx, const int* __restrict__ idx,
                                                                        int N, int k, int d4, long long E, long long chunk, int ct, int rl,
                                                                        f32x4* __restrict__ part) {
-    __shared__ f32x4 sh[VA_THREADS * 4];
+    __shared__ f32x4 sh[RT_THREADS * 4];
     const int tid = threadIdx.x, tc = tid % ct, r = tid / ct;
     const long long e0 = (long long)blockIdx.x * chunk, e1 = e0 + chunk < E ? e0 + chunk : E;
     for (int cq0 = 0; cq0 < d4; cq0 += ct) {
@@ -90,7 +72,7 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_delta_bwd_kernel(const flo
                 const float* pi = xyz + i * ldx;
                 const float* pj = xyz + j * ldx;
                 const float r0 = pi[0] - pj[0], r1 = pi[1] - pj[1], r2 = pi[2] - pj[2];
-                const f32x4 g = va_ld(dH1 + (e * d4 + cq) * 4), h = va_ld(H1 + (e * d4 + cq) * 4);
+                const f32x4 g = rt_ld(dH1 + (e * d4 + cq) * 4), h = rt_ld(H1 + (e * d4 + cq) * 4);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const float m = h[u] > 0.f ? g[u] : 0.f;
@@ -110,9 +92,9 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_delta_bwd_kernel(const flo
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(VA_THREADS) void vecattn_delta_bwd_finalize_kernel(const f32x4* __restrict__ part, int nparts, int d,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_delta_bwd_finalize_kernel(const f32x4* __restrict__ part, int nparts, int d,
                                                                                 float* __restrict__ dWd1, float* __restrict__ dbd1) {
-    const int c = blockIdx.x * VA_THREADS + threadIdx.x;
+    const int c = blockIdx.x * RT_THREADS + threadIdx.x;
     if (c >= d) return;
     double x = 0.0, y = 0.0, z = 0.0, w = 0.0;
     for (int g = 0; g < nparts; ++g) {
@@ -125,27 +107,27 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_delta_bwd_finalize_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // T[e] = (q_i - kk_j) + pos[e] (:39).  Traffic per edge and channel: 4 B read (pos) + 4 B written; the q / kk rows come from cache.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_mix_fwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kk, int ldk,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_mix_fwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kk, int ldk,
                                                                      const float* __restrict__ pos, const int* __restrict__ idx, int N, int k,
                                                                      int d4, long long E, int rb, float* __restrict__ T) {
-    VA_FOR_ITEMS(E, rb, d4) {
+    RT_FOR_ITEMS(E, rb, d4, RT_THREADS) {
         const int lr = it_ / d4, cq = it_ - lr * d4;
         const long long e = r0_ + lr, i = e / k, cloud = i / N;
         const long long j = cloud * N + va_nbr(idx, e, N);
-        const f32x4 a = va_ld(q + i * ldq + cq * 4), b = va_ld(kk + j * ldk + cq * 4), p = va_ld(pos + (e * d4 + cq) * 4);
-        va_st(T + (e * d4 + cq) * 4, (a - b) + p);
+        const f32x4 a = rt_ld(q + i * ldq + cq * 4), b = rt_ld(kk + j * ldk + cq * 4), p = rt_ld(pos + (e * d4 + cq) * 4);
+        rt_st(T + (e * d4 + cq) * 4, (a - b) + p);
     }
 }
 // dq_i = sum_s dT[i][s] in ascending s.  Traffic per edge and channel: 4 B read.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_mix_bwd_kernel(const float* __restrict__ dT, int k, int d4, long long P, int rb,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_mix_bwd_kernel(const float* __restrict__ dT, int k, int d4, long long P, int rb,
                                                                      float* __restrict__ dq) {
-    VA_FOR_ITEMS(P, rb, d4) {
+    RT_FOR_ITEMS(P, rb, d4, RT_THREADS) {
         const int lr = it_ / d4, cq = it_ - lr * d4;
         const long long i = r0_ + lr;
         const float* g = dT + (i * k * d4 + cq) * 4;
-        f32x4 s = va_ld(g);
-        for (int u = 1; u < k; ++u) s += va_ld(g + (size_t)u * d4 * 4);
-        va_st(dq + (i * d4 + cq) * 4, s);
+        f32x4 s = rt_ld(g);
+        for (int u = 1; u < k; ++u) s += rt_ld(g + (size_t)u * d4 * 4);
+        rt_st(dq + (i * d4 + cq) * 4, s);
     }
 }
 
@@ -154,17 +136,17 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_mix_bwd_kernel(const float
 // sum of exp(x - max) rescaled whenever the maximum moves (registers only); second walk: attn = exp(x - max) / sum, written, and
 // res += attn * (v_j + pos).  Traffic per edge and channel: 4 B (A) + 4 B (pos) read, 4 B (attn) written; A's second read comes
 // from L2 (a tile's k rows were just read), the v rows from cache.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_aggregate_fwd_kernel(const float* __restrict__ A, const float* __restrict__ v, int ldv,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_aggregate_fwd_kernel(const float* __restrict__ A, const float* __restrict__ v, int ldv,
                                                                            const float* __restrict__ pos, const int* __restrict__ idx, int N,
                                                                            int k, int d4, long long P, int rb, float sq,
                                                                            float* __restrict__ attn, float* __restrict__ res) {
-    VA_FOR_ITEMS(P, rb, d4) {
+    RT_FOR_ITEMS(P, rb, d4, RT_THREADS) {
         const int lr = it_ / d4, cq = it_ - lr * d4;
         const long long i = r0_ + lr, cloud = i / N, e0 = i * k;
         const float* a = A + (e0 * d4 + cq) * 4;
-        f32x4 m = va_ld(a) / sq, l = f32x4{1.f, 1.f, 1.f, 1.f};
+        f32x4 m = rt_ld(a) / sq, l = f32x4{1.f, 1.f, 1.f, 1.f};
         for (int s = 1; s < k; ++s) {
-            const f32x4 x = va_ld(a + (size_t)s * d4 * 4) / sq;
+            const f32x4 x = rt_ld(a + (size_t)s * d4 * 4) / sq;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float mn = fmaxf(m[u], x[u]);
@@ -175,72 +157,71 @@ __global__ __launch_bounds__(VA_THREADS) void vecattn_aggregate_fwd_kernel(const
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < k; ++s) {
             const long long e = e0 + s, j = cloud * N + va_nbr(idx, e, N);
-            const f32x4 x = va_ld(a + (size_t)s * d4 * 4) / sq;
-            const f32x4 vp = va_ld(v + j * ldv + cq * 4) + va_ld(pos + (e * d4 + cq) * 4);
+            const f32x4 x = rt_ld(a + (size_t)s * d4 * 4) / sq;
+            const f32x4 vp = rt_ld(v + j * ldv + cq * 4) + rt_ld(pos + (e * d4 + cq) * 4);
             f32x4 w;
 #pragma unroll
             for (int u = 0; u < 4; ++u) w[u] = expf(x[u] - m[u]) / l[u];
-            va_st(attn + (e * d4 + cq) * 4, w);
+            rt_st(attn + (e * d4 + cq) * 4, w);
             acc += w * vp;
         }
-        va_st(res + (i * d4 + cq) * 4, acc);
+        rt_st(res + (i * d4 + cq) * 4, acc);
     }
 }
 // dVP[e] = attn[e] * dres_i;  dA[e] = attn[e] * (g[e] - sum_s attn[i,s] g[i,s]) / sqrt(d),  g[e] = dres_i * (v_j + pos[e]).
 // First walk: dVP and the sum; second walk: dA.  Traffic per edge and channel: 8 B read (attn, pos) + 8 B written; the second reads
 // of attn and pos come from L2.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_aggregate_bwd_kernel(const float* __restrict__ dres, const float* __restrict__ attn,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_aggregate_bwd_kernel(const float* __restrict__ dres, const float* __restrict__ attn,
                                                                            const float* __restrict__ v, int ldv, const float* __restrict__ pos,
                                                                            const int* __restrict__ idx, int N, int k, int d4, long long P, int rb,
                                                                            float sq, float* __restrict__ dVP, float* __restrict__ dA) {
-    VA_FOR_ITEMS(P, rb, d4) {
+    RT_FOR_ITEMS(P, rb, d4, RT_THREADS) {
         const int lr = it_ / d4, cq = it_ - lr * d4;
         const long long i = r0_ + lr, cloud = i / N, e0 = i * k;
-        const f32x4 dr = va_ld(dres + (i * d4 + cq) * 4);
+        const f32x4 dr = rt_ld(dres + (i * d4 + cq) * 4);
         f32x4 dot = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < k; ++s) {
             const long long e = e0 + s, j = cloud * N + va_nbr(idx, e, N);
-            const f32x4 w = va_ld(attn + (e * d4 + cq) * 4);
-            const f32x4 vp = va_ld(v + j * ldv + cq * 4) + va_ld(pos + (e * d4 + cq) * 4);
-            va_st(dVP + (e * d4 + cq) * 4, w * dr);
+            const f32x4 w = rt_ld(attn + (e * d4 + cq) * 4);
+            const f32x4 vp = rt_ld(v + j * ldv + cq * 4) + rt_ld(pos + (e * d4 + cq) * 4);
+            rt_st(dVP + (e * d4 + cq) * 4, w * dr);
             dot += w * (dr * vp);
         }
         for (int s = 0; s < k; ++s) {
             const long long e = e0 + s, j = cloud * N + va_nbr(idx, e, N);
-            const f32x4 w = va_ld(attn + (e * d4 + cq) * 4);
-            const f32x4 vp = va_ld(v + j * ldv + cq * 4) + va_ld(pos + (e * d4 + cq) * 4);
-            va_st(dA + (e * d4 + cq) * 4, w * (dr * vp - dot) / sq);
+            const f32x4 w = rt_ld(attn + (e * d4 + cq) * 4);
+            const f32x4 vp = rt_ld(v + j * ldv + cq * 4) + rt_ld(pos + (e * d4 + cq) * 4);
+            rt_st(dA + (e * d4 + cq) * 4, w * (dr * vp - dot) / sq);
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // y = max(x, 0) (y may be x);  dx = dy where y > 0, else 0.  n4 quads.  8 B / 12 B per element.
-__global__ __launch_bounds__(VA_THREADS) void vecattn_relu_fwd_kernel(const float* __restrict__ x, long long n4, float* __restrict__ y) {
-    for (long long t = (long long)blockIdx.x * VA_THREADS + threadIdx.x; t < n4; t += (long long)gridDim.x * VA_THREADS) {
-        f32x4 a = va_ld(x + t * 4);
+__global__ __launch_bounds__(RT_THREADS) void vecattn_relu_fwd_kernel(const float* __restrict__ x, long long n4, float* __restrict__ y) {
+    for (long long t = (long long)blockIdx.x * RT_THREADS + threadIdx.x; t < n4; t += (long long)gridDim.x * RT_THREADS) {
+        f32x4 a = rt_ld(x + t * 4);
         a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
-        va_st(y + t * 4, a);
+        rt_st(y + t * 4, a);
     }
 }
-__global__ __launch_bounds__(VA_THREADS) void vecattn_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, long long n4,
+__global__ __launch_bounds__(RT_THREADS) void vecattn_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, long long n4,
                                                                       float* __restrict__ dx) {
-    for (long long t = (long long)blockIdx.x * VA_THREADS + threadIdx.x; t < n4; t += (long long)gridDim.x * VA_THREADS) {
-        const f32x4 g = va_ld(dy + t * 4), a = va_ld(y + t * 4);
-        va_st(dx + t * 4, f32x4{a.x > 0.f ? g.x : 0.f, a.y > 0.f ? g.y : 0.f, a.z > 0.f ? g.z : 0.f, a.w > 0.f ? g.w : 0.f});
+    for (long long t = (long long)blockIdx.x * RT_THREADS + threadIdx.x; t < n4; t += (long long)gridDim.x * RT_THREADS) {
+        const f32x4 g = rt_ld(dy + t * 4), a = rt_ld(y + t * 4);
+        rt_st(dx + t * 4, f32x4{a.x > 0.f ? g.x : 0.f, a.y > 0.f ? g.y : 0.f, a.z > 0.f ? g.z : 0.f, a.w > 0.f ? g.w : 0.f});
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-static inline bool va_al(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool va_shape_ok(int B, int N, int k, int d) {
     return d % 4 == 0 && k >= 1 && k <= VA_MAX_K && (long long)B * N <= (1LL << 30);
 }
 // delta_bwd's split of the E edges: (channel threads, row lanes, workgroups)
 static inline void va_delta_bwd_plan(long long E, int d, int& ct, int& rl, int& nparts) {
     const int d4 = d / 4;
-    ct = d4 < VA_THREADS ? d4 : VA_THREADS;
-    rl = VA_THREADS / ct;
+    ct = d4 < RT_THREADS ? d4 : RT_THREADS;
+    rl = RT_THREADS / ct;
     const long long want = (E + (long long)rl * 8 - 1) / ((long long)rl * 8);
     nparts = (int)(want < 1 ? 1 : want > VA_PARTS_MAX ? VA_PARTS_MAX : want);
 }
@@ -252,74 +233,74 @@ size_t vecattn_delta_bwd_ws_floats(int B, int N, int k, int d) {
 
 int launch_vecattn_delta_fwd(hipStream_t st, const float* xyz, int ldx, const int* idx, const float* Wd1, const float* bd1, int B, int N, int k,
                              int d, float* H1) {
-    if (!va_shape_ok(B, N, k, d) || ldx < 3 || !va_al(Wd1) || !va_al(bd1) || !va_al(H1)) return MLSP_ERR_UNSUPPORTED;
+    if (!va_shape_ok(B, N, k, d) || ldx < 3 || !al16(Wd1, bd1, H1)) return MLSP_ERR_UNSUPPORTED;
     const long long E = (long long)B * N * k;
-    const VaTiles t = va_tiles(E, d / 4);
-    hipLaunchKernelGGL(vecattn_delta_fwd_kernel, dim3(t.grid), dim3(VA_THREADS), 0, st, xyz, ldx, idx, Wd1, bd1, N, k, d / 4, E, t.rb, H1);
+    const RowTiles t = row_tiles(E, d / 4);
+    hipLaunchKernelGGL(vecattn_delta_fwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, xyz, ldx, idx, Wd1, bd1, N, k, d / 4, E, t.rb, H1);
     return mlsp_launch_status();
 }
 int launch_vecattn_delta_bwd(hipStream_t st, const float* dH1, const float* H1, const float* xyz, int ldx, const int* idx, int B, int N, int k,
                              int d, float* part, float* dWd1, float* dbd1) {
-    if (!va_shape_ok(B, N, k, d) || ldx < 3 || !va_al(dH1) || !va_al(H1) || !va_al(part)) return MLSP_ERR_UNSUPPORTED;
+    if (!va_shape_ok(B, N, k, d) || ldx < 3 || !al16(dH1, H1, part)) return MLSP_ERR_UNSUPPORTED;
     const long long E = (long long)B * N * k;
     int ct, rl, nparts;
     va_delta_bwd_plan(E, d, ct, rl, nparts);
     const long long chunk = (E + nparts - 1) / nparts;
-    hipLaunchKernelGGL(vecattn_delta_bwd_kernel, dim3(nparts), dim3(VA_THREADS), 0, st, dH1, H1, xyz, ldx, idx, N, k, d / 4, E, chunk, ct, rl,
+    hipLaunchKernelGGL(vecattn_delta_bwd_kernel, dim3(nparts), dim3(RT_THREADS), 0, st, dH1, H1, xyz, ldx, idx, N, k, d / 4, E, chunk, ct, rl,
                        (f32x4*)part);
-    hipLaunchKernelGGL(vecattn_delta_bwd_finalize_kernel, dim3((d + VA_THREADS - 1) / VA_THREADS), dim3(VA_THREADS), 0, st,
+    hipLaunchKernelGGL(vecattn_delta_bwd_finalize_kernel, dim3((d + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, st,
                        (const f32x4*)part, nparts, d, dWd1, dbd1);
     return mlsp_launch_status();
 }
 int launch_vecattn_mix_fwd(hipStream_t st, const float* q, int ldq, const float* kk, int ldk, const float* pos, const int* idx, int B, int N, int k,
                            int d, float* T) {
-    if (!va_shape_ok(B, N, k, d) || ldq < d || ldk < d || ldq % 4 || ldk % 4 || !va_al(q) || !va_al(kk) || !va_al(pos) || !va_al(T))
+    if (!va_shape_ok(B, N, k, d) || ldq < d || ldk < d || ldq % 4 || ldk % 4 || !al16(q, kk, pos, T))
         return MLSP_ERR_UNSUPPORTED;
     const long long E = (long long)B * N * k;
-    const VaTiles t = va_tiles(E, d / 4);
-    hipLaunchKernelGGL(vecattn_mix_fwd_kernel, dim3(t.grid), dim3(VA_THREADS), 0, st, q, ldq, kk, ldk, pos, idx, N, k, d / 4, E, t.rb, T);
+    const RowTiles t = row_tiles(E, d / 4);
+    hipLaunchKernelGGL(vecattn_mix_fwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, q, ldq, kk, ldk, pos, idx, N, k, d / 4, E, t.rb, T);
     return mlsp_launch_status();
 }
 int launch_vecattn_mix_bwd(hipStream_t st, const float* dT, int B, int N, int k, int d, float* dq) {
-    if (!va_shape_ok(B, N, k, d) || !va_al(dT) || !va_al(dq)) return MLSP_ERR_UNSUPPORTED;
+    if (!va_shape_ok(B, N, k, d) || !al16(dT, dq)) return MLSP_ERR_UNSUPPORTED;
     const long long P = (long long)B * N;
-    const VaTiles t = va_tiles(P, d / 4);
-    hipLaunchKernelGGL(vecattn_mix_bwd_kernel, dim3(t.grid), dim3(VA_THREADS), 0, st, dT, k, d / 4, P, t.rb, dq);
+    const RowTiles t = row_tiles(P, d / 4);
+    hipLaunchKernelGGL(vecattn_mix_bwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, dT, k, d / 4, P, t.rb, dq);
     return mlsp_launch_status();
 }
 int launch_vecattn_aggregate_fwd(hipStream_t st, const float* A, const float* v, int ldv, const float* pos, const int* idx, int B, int N, int k,
                                  int d, float* attn, float* res) {
-    if (!va_shape_ok(B, N, k, d) || ldv < d || ldv % 4 || !va_al(A) || !va_al(v) || !va_al(pos) || !va_al(attn) || !va_al(res))
+    if (!va_shape_ok(B, N, k, d) || ldv < d || ldv % 4 || !al16(A, v, pos, attn, res))
         return MLSP_ERR_UNSUPPORTED;
     const long long P = (long long)B * N;
-    const VaTiles t = va_tiles(P, d / 4);
-    hipLaunchKernelGGL(vecattn_aggregate_fwd_kernel, dim3(t.grid), dim3(VA_THREADS), 0, st, A, v, ldv, pos, idx, N, k, d / 4, P, t.rb,
+    const RowTiles t = row_tiles(P, d / 4);
+    hipLaunchKernelGGL(vecattn_aggregate_fwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, A, v, ldv, pos, idx, N, k, d / 4, P, t.rb,
                        sqrtf((float)d), attn, res);
     return mlsp_launch_status();
 }
 int launch_vecattn_aggregate_bwd(hipStream_t st, const float* dres, const float* attn, const float* v, int ldv, const float* pos, const int* idx,
                                  int B, int N, int k, int d, float* dVP, float* dA) {
-    if (!va_shape_ok(B, N, k, d) || ldv < d || ldv % 4 || !va_al(dres) || !va_al(attn) || !va_al(v) || !va_al(pos) || !va_al(dVP) || !va_al(dA))
+    if (!va_shape_ok(B, N, k, d) || ldv < d || ldv % 4 || !al16(dres, attn, v, pos, dVP, dA))
         return MLSP_ERR_UNSUPPORTED;
     const long long P = (long long)B * N;
-    const VaTiles t = va_tiles(P, d / 4);
-    hipLaunchKernelGGL(vecattn_aggregate_bwd_kernel, dim3(t.grid), dim3(VA_THREADS), 0, st, dres, attn, v, ldv, pos, idx, N, k, d / 4, P, t.rb,
+    const RowTiles t = row_tiles(P, d / 4);
+    hipLaunchKernelGGL(vecattn_aggregate_bwd_kernel, dim3(t.grid), dim3(RT_THREADS), 0, st, dres, attn, v, ldv, pos, idx, N, k, d / 4, P, t.rb,
                        sqrtf((float)d), dVP, dA);
     return mlsp_launch_status();
 }
 static inline int va_flat_grid(long long n4) {
-    const long long b = (n4 + VA_THREADS - 1) / VA_THREADS;
+    const long long b = (n4 + RT_THREADS - 1) / RT_THREADS;
     return (int)(b < 1 ? 1 : b > 65536 ? 65536 : b);
 }
 int launch_vecattn_relu_fwd(hipStream_t st, const float* x, long long rows, int d, float* y) {
-    if (rows <= 0 || d <= 0 || d % 4 || !va_al(x) || !va_al(y)) return MLSP_ERR_UNSUPPORTED;
+    if (rows <= 0 || d <= 0 || d % 4 || !al16(x, y)) return MLSP_ERR_UNSUPPORTED;
     const long long n4 = rows * (d / 4);
-    hipLaunchKernelGGL(vecattn_relu_fwd_kernel, dim3(va_flat_grid(n4)), dim3(VA_THREADS), 0, st, x, n4, y);
+    hipLaunchKernelGGL(vecattn_relu_fwd_kernel, dim3(va_flat_grid(n4)), dim3(RT_THREADS), 0, st, x, n4, y);
     return mlsp_launch_status();
 }
 int launch_vecattn_relu_bwd(hipStream_t st, const float* dy, const float* y, long long rows, int d, float* dx) {
-    if (rows <= 0 || d <= 0 || d % 4 || !va_al(dy) || !va_al(y) || !va_al(dx)) return MLSP_ERR_UNSUPPORTED;
+    if (rows <= 0 || d <= 0 || d % 4 || !al16(dy, y, dx)) return MLSP_ERR_UNSUPPORTED;
     const long long n4 = rows * (d / 4);
-    hipLaunchKernelGGL(vecattn_relu_bwd_kernel, dim3(va_flat_grid(n4)), dim3(VA_THREADS), 0, st, dy, y, n4, dx);
+    hipLaunchKernelGGL(vecattn_relu_bwd_kernel, dim3(va_flat_grid(n4)), dim3(RT_THREADS), 0, st, dy, y, n4, dx);
     return mlsp_launch_status();
 }

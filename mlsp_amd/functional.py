@@ -1897,36 +1897,53 @@ def gather_rows(x, index):
     return _GatherRows.apply(x, index)
 
 
-def _va_check(rc, what):
-    """MLSP_ERR_UNSUPPORTED of the vector-attention kernels (d % 4, k > 64, alignment) is a MlspLibraryError: there is no other path"""
-    if rc == -3:
-        raise _lib.MlspLibraryError("%s: %s (needs d %% 4 == 0, 1 <= k <= 64, 16-byte-aligned rows)"
-                                    % (what, _lib.load().mlsp_strerror(rc).decode()))
+def _check_supported(rc, what, needs, codes=(-3,)):
+    """A kernel family's refusal of a shape (MLSP_ERR_UNSUPPORTED; with codes=_ARG_TOO also MLSP_ERR_ARG) is a MlspLibraryError that says
+    what the family needs: there is no other path"""
+    if rc in codes:
+        raise _lib.MlspLibraryError("%s: %s (%s)" % (what, _lib.load().mlsp_strerror(rc).decode(), needs))
     _lib.check(rc, what)
 
 
-class _EdgeIndex:
-    """idx int32 [B,N,k] of a vector-attention call and, from the first backward that needs it, its reverse index (every edge that names
-    point j, in a fixed order: mlsp_group_reverse) -- shared by the two scatters of the call."""
-    __slots__ = ("idx", "B", "N", "k", "rev")
+_ARG_TOO = (-1, -3)
+_VA_NEEDS = "needs d % 4 == 0, 1 <= k <= 64, 16-byte-aligned rows"
+_GN_NEEDS = "needs C % (4 groups) == 0, 1 <= k <= 64, 16-byte-aligned rows"
+_ATTN_NEEDS = ("needs channel counts % 4 == 0 and 16-byte-aligned rows; the attention core head_dim <= 128, L <= 512 and "
+               "L * head_dim <= 16384")
+_TOKEN_NEEDS = ("thin_in needs Cin <= 8, C % 4 == 0, C <= 4096 and at least 2 rows in training with BatchNorm; token_pool needs L >= 2 "
+                "and d % 4 == 0")
+_PYRAMID_NEEDS = "interp3_add and cloud_mean need C % 4 == 0, 16-byte-aligned rows and S == 1 or S >= 3 source points"
 
-    def __init__(self, idx32):
-        self.idx, (self.B, self.N, self.k), self.rev = idx32, idx32.shape, None
 
-    def scatter(self, dG):
-        """[E][d] edge rows -> [P][d]: out[j] = sum of the rows of the edges (i, s) with idx[i][s] == j"""
-        lib = _lib.load()
-        B, N, k, dev = self.B, self.N, self.k, dG.device
-        if self.rev is None:
-            rev_off = torch.empty((B * N + 1,), dtype=torch.int32, device=dev)
-            rev_ent = torch.empty((B * N * k,), dtype=torch.int32, device=dev)
-            _lib.check(lib.mlsp_group_reverse(self.idx.data_ptr(), B, N, N, k, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
-                       "mlsp_group_reverse")
-            self.rev = (rev_off, rev_ent)
-        d = dG.shape[1]
-        out = torch.empty((B * N, d), dtype=torch.float32, device=dev)
-        _lib.check(lib.mlsp_sa_group_bwd_f32(dG.data_ptr(), d, 0, d, self.rev[0].data_ptr(), self.rev[1].data_ptr(), B, N, N, k,
-                                             out.data_ptr(), _lib.stream()), "mlsp_sa_group_bwd_f32")
+class ReverseIndex:
+    """idx32 int32 [B, Nq, k] (entries local to the cloud, in [0, Nk)) and, from the first request on, its reverse index: for every source
+    row j the edges (i, s) with idx[i][s] == j in a fixed order (mlsp_group_reverse: rev_off [B*Nk + 1], rev_ent [B*Nq*k] = i << 8 | s).
+    Built once per object and kept: every scatter of a call, and every backward over a retained graph, reads the same lists.
+    Two users of reverse lists stay outside: KnnGraph (mlsp_knn_f32 builds its lists in the call that searches, and its rev_off / rev_ent
+    are read by name) and pointnet2._SAFold (the compact variant with rev_cnt / pad_cnt: mlsp_group_reverse_compact)."""
+    __slots__ = ("idx", "B", "Nq", "k", "Nk", "_rev")
+
+    def __init__(self, idx32, Nk):
+        self.idx, (self.B, self.Nq, self.k), self.Nk, self._rev = idx32, idx32.shape, int(Nk), None
+
+    def lists(self):
+        """(rev_off, rev_ent)"""
+        if self._rev is None:
+            B, Nq, k, Nk, dev = self.B, self.Nq, self.k, self.Nk, self.idx.device
+            rev_off = torch.empty((B * Nk + 1,), dtype=torch.int32, device=dev)
+            rev_ent = torch.empty((B * Nq * k,), dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().mlsp_group_reverse(self.idx.data_ptr(), B, Nq, Nk, k, rev_off.data_ptr(), rev_ent.data_ptr(),
+                                                      _lib.stream()), "mlsp_group_reverse")
+            self._rev = (rev_off, rev_ent)
+        return self._rev
+
+    def scatter(self, dG, ld, col, width):
+        """columns [col, col + width) of the [B*Nq*k] edge rows dG (pitch ld) -> [B*Nk, width]: out[j] = the sum of the rows of the edges
+        (i, s) with idx[i][s] == j, in list order"""
+        rev_off, rev_ent = self.lists()
+        out = torch.empty((self.B * self.Nk, width), dtype=torch.float32, device=dG.device)
+        _lib.check(_lib.load().mlsp_sa_group_bwd_f32(dG.data_ptr(), ld, col, width, rev_off.data_ptr(), rev_ent.data_ptr(), self.B, self.Nk,
+                                                     self.Nq, self.k, out.data_ptr(), _lib.stream()), "mlsp_sa_group_bwd_f32")
         return out
 
 
@@ -1936,13 +1953,13 @@ class _VaDelta(Function):
     @staticmethod
     def forward(ctx, xyz, Wd1, bd1, eidx):
         lib = _lib.load()
-        B, N, k = eidx.B, eidx.N, eidx.k
+        B, N, k = eidx.B, eidx.Nq, eidx.k
         Wd1, bd1 = Wd1.contiguous(), bd1.contiguous()
         d = Wd1.shape[0]
         assert xyz.shape[0] == B * N and Wd1.shape == (d, 3) and bd1.shape == (d,), (xyz.shape, Wd1.shape, bd1.shape)
         H1 = torch.empty((B * N * k, d), dtype=torch.float32, device=xyz.device)
-        _va_check(lib.mlsp_vecattn_delta_fwd_f32(xyz.data_ptr(), xyz.stride(0), eidx.idx.data_ptr(), Wd1.data_ptr(), bd1.data_ptr(), B, N, k,
-                                                 d, H1.data_ptr(), _lib.stream()), "mlsp_vecattn_delta_fwd_f32")
+        _check_supported(lib.mlsp_vecattn_delta_fwd_f32(xyz.data_ptr(), xyz.stride(0), eidx.idx.data_ptr(), Wd1.data_ptr(), bd1.data_ptr(), B, N, k,
+                                                        d, H1.data_ptr(), _lib.stream()), "mlsp_vecattn_delta_fwd_f32", _VA_NEEDS)
         ctx.save_for_backward(xyz, H1)
         ctx.eidx = eidx
         return H1
@@ -1958,8 +1975,9 @@ class _VaDelta(Function):
         dW = torch.empty((d, 3), dtype=torch.float32, device=dH1.device)
         db = torch.empty((d,), dtype=torch.float32, device=dH1.device)
         ws, wsn = _lib.workspace(dH1.device, 4096, d, 4)
-        _va_check(lib.mlsp_vecattn_delta_bwd_f32(dH1.data_ptr(), H1.data_ptr(), xyz.data_ptr(), xyz.stride(0), e.idx.data_ptr(), e.B, e.N,
-                                                 e.k, d, dW.data_ptr(), db.data_ptr(), ws, wsn, _lib.stream()), "mlsp_vecattn_delta_bwd_f32")
+        _check_supported(lib.mlsp_vecattn_delta_bwd_f32(dH1.data_ptr(), H1.data_ptr(), xyz.data_ptr(), xyz.stride(0), e.idx.data_ptr(), e.B, e.Nq,
+                                                        e.k, d, dW.data_ptr(), db.data_ptr(), ws, wsn, _lib.stream()),
+                         "mlsp_vecattn_delta_bwd_f32", _VA_NEEDS)
         return None, dW, db, None
 
 
@@ -1970,12 +1988,12 @@ class _VaMix(Function):
     def forward(ctx, q, kk, pos, eidx):
         lib = _lib.load()
         q, kk, pos = _rows(q), _rows(kk), pos.contiguous()
-        B, N, k = eidx.B, eidx.N, eidx.k
+        B, N, k = eidx.B, eidx.Nq, eidx.k
         d = q.shape[1]
         assert q.shape == (B * N, d) and kk.shape == (B * N, d) and pos.shape == (B * N * k, d), (q.shape, kk.shape, pos.shape)
         T = torch.empty_like(pos)
-        _va_check(lib.mlsp_vecattn_mix_fwd_f32(q.data_ptr(), q.stride(0), kk.data_ptr(), kk.stride(0), pos.data_ptr(), eidx.idx.data_ptr(),
-                                               B, N, k, d, T.data_ptr(), _lib.stream()), "mlsp_vecattn_mix_fwd_f32")
+        _check_supported(lib.mlsp_vecattn_mix_fwd_f32(q.data_ptr(), q.stride(0), kk.data_ptr(), kk.stride(0), pos.data_ptr(), eidx.idx.data_ptr(),
+                                                      B, N, k, d, T.data_ptr(), _lib.stream()), "mlsp_vecattn_mix_fwd_f32", _VA_NEEDS)
         ctx.eidx = eidx
         return T
 
@@ -1988,10 +2006,11 @@ class _VaMix(Function):
         d = dT.shape[1]
         dq = dkk = None
         if ctx.needs_input_grad[0]:
-            dq = torch.empty((e.B * e.N, d), dtype=torch.float32, device=dT.device)
-            _va_check(lib.mlsp_vecattn_mix_bwd_f32(dT.data_ptr(), e.B, e.N, e.k, d, dq.data_ptr(), _lib.stream()), "mlsp_vecattn_mix_bwd_f32")
+            dq = torch.empty((e.B * e.Nq, d), dtype=torch.float32, device=dT.device)
+            _check_supported(lib.mlsp_vecattn_mix_bwd_f32(dT.data_ptr(), e.B, e.Nq, e.k, d, dq.data_ptr(), _lib.stream()),
+                             "mlsp_vecattn_mix_bwd_f32", _VA_NEEDS)
         if ctx.needs_input_grad[1]:
-            dkk = e.scatter(dT).neg_()
+            dkk = e.scatter(dT, d, 0, d).neg_()
         return dq, dkk, dT, None
 
 
@@ -2003,7 +2022,8 @@ class _VaRelu(Function):
         lib = _lib.load()
         x = x.contiguous()
         y = torch.empty_like(x)
-        _va_check(lib.mlsp_vecattn_relu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()), "mlsp_vecattn_relu_fwd_f32")
+        _check_supported(lib.mlsp_vecattn_relu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()),
+                         "mlsp_vecattn_relu_fwd_f32", _VA_NEEDS)
         ctx.save_for_backward(y)
         return y
 
@@ -2014,8 +2034,8 @@ class _VaRelu(Function):
         y, = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        _va_check(lib.mlsp_vecattn_relu_bwd_f32(dy.data_ptr(), y.data_ptr(), y.shape[0], y.shape[1], dx.data_ptr(), _lib.stream()),
-                  "mlsp_vecattn_relu_bwd_f32")
+        _check_supported(lib.mlsp_vecattn_relu_bwd_f32(dy.data_ptr(), y.data_ptr(), y.shape[0], y.shape[1], dx.data_ptr(), _lib.stream()),
+                         "mlsp_vecattn_relu_bwd_f32", _VA_NEEDS)
         return dx
 
 
@@ -2027,13 +2047,14 @@ class _VaAggregate(Function):
     def forward(ctx, A, v, pos, eidx):
         lib = _lib.load()
         A, v, pos = A.contiguous(), _rows(v), pos.contiguous()
-        B, N, k = eidx.B, eidx.N, eidx.k
+        B, N, k = eidx.B, eidx.Nq, eidx.k
         d = v.shape[1]
         assert A.shape == (B * N * k, d) and pos.shape == A.shape and v.shape[0] == B * N, (A.shape, v.shape, pos.shape)
         attn = torch.empty_like(A)
         res = torch.empty((B * N, d), dtype=torch.float32, device=A.device)
-        _va_check(lib.mlsp_vecattn_aggregate_fwd_f32(A.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(), eidx.idx.data_ptr(), B, N, k, d,
-                                                     attn.data_ptr(), res.data_ptr(), _lib.stream()), "mlsp_vecattn_aggregate_fwd_f32")
+        _check_supported(lib.mlsp_vecattn_aggregate_fwd_f32(A.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(), eidx.idx.data_ptr(), B, N, k, d,
+                                                            attn.data_ptr(), res.data_ptr(), _lib.stream()),
+                         "mlsp_vecattn_aggregate_fwd_f32", _VA_NEEDS)
         ctx.save_for_backward(attn, v, pos)
         ctx.eidx = eidx
         ctx.mark_non_differentiable(attn)
@@ -2048,10 +2069,10 @@ class _VaAggregate(Function):
         d = v.shape[1]
         dres = dres.contiguous()
         dVP, dA = torch.empty_like(attn), torch.empty_like(attn)
-        _va_check(lib.mlsp_vecattn_aggregate_bwd_f32(dres.data_ptr(), attn.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(),
-                                                     e.idx.data_ptr(), e.B, e.N, e.k, d, dVP.data_ptr(), dA.data_ptr(), _lib.stream()),
-                  "mlsp_vecattn_aggregate_bwd_f32")
-        dv = e.scatter(dVP) if ctx.needs_input_grad[1] else None
+        _check_supported(lib.mlsp_vecattn_aggregate_bwd_f32(dres.data_ptr(), attn.data_ptr(), v.data_ptr(), v.stride(0), pos.data_ptr(),
+                                                            e.idx.data_ptr(), e.B, e.Nq, e.k, d, dVP.data_ptr(), dA.data_ptr(), _lib.stream()),
+                         "mlsp_vecattn_aggregate_bwd_f32", _VA_NEEDS)
+        dv = e.scatter(dVP, d, 0, d) if ctx.needs_input_grad[1] else None
         return dA, dv, dVP, None
 
 
@@ -2068,7 +2089,7 @@ def vector_attention(xyz_rows, idx32, q, kk, v, delta_w1, delta_b1, delta_w2, de
     xyz_rows = xyz_rows.detach()
     if xyz_rows.stride(1) != 1:
         xyz_rows = xyz_rows.contiguous()
-    eidx = _EdgeIndex(idx32.contiguous())
+    eidx = ReverseIndex(idx32.contiguous(), idx32.shape[1])
     H1 = _VaDelta.apply(xyz_rows, delta_w1, delta_b1, eidx)
     pos = pointmlp(H1, delta_w2, bias=delta_b2)
     T = _VaMix.apply(q, kk, pos, eidx)
@@ -2077,68 +2098,52 @@ def vector_attention(xyz_rows, idx32, q, kk, v, delta_w1, delta_b1, delta_w2, de
     return _VaAggregate.apply(A, v, pos, eidx)
 
 
-def _gn_check(rc, what):
-    """MLSP_ERR_UNSUPPORTED of the GroupNorm edge kernels is a MlspLibraryError: there is no other path"""
-    if rc == -3:
-        raise _lib.MlspLibraryError("%s: %s (needs C %% (4 groups) == 0, 1 <= k <= 64, 16-byte-aligned rows)"
-                                    % (what, _lib.load().mlsp_strerror(rc).decode()))
-    _lib.check(rc, what)
-
-
 class _GnEdgeMax(Function):
     """out[i] = max_s lrelu(GroupNorm(u[idx[i][s]] + w[i]))  (mlsp_gn_edge_*_f32): the edge tensor and its gradient are never materialised.
-    `rev`: an empty list that the first backward fills with the reverse index of idx32 (as _EdgeIndex does)."""
+    `rev`: the ReverseIndex of idx32 over the Nk source rows; the first backward builds its lists."""
 
     @staticmethod
-    def forward(ctx, u, w, idx32, gamma, beta, groups, eps, slope, rev):
+    def forward(ctx, u, w, rev, gamma, beta, groups, eps, slope):
         lib = _lib.load()
         u, w = _rows(u), _rows(w)
         gamma, beta = gamma.contiguous(), beta.contiguous()
-        B, Nq, k = idx32.shape
+        idx32, B, Nq, k, Nk = rev.idx, rev.B, rev.Nq, rev.k, rev.Nk
         C = u.shape[1]
-        Nk = u.shape[0] // B
         assert u.shape[0] == B * Nk and w.shape == (B * Nq, C) and gamma.shape == (C,) and beta.shape == (C,), (u.shape, w.shape, idx32.shape)
         dev = u.device
         out = torch.empty((B * Nq, C), dtype=torch.float32, device=dev)
         argk = torch.empty((B * Nq, C), dtype=torch.uint8, device=dev)
         stats = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
         ws, wsn = _lib.workspace_of(dev, lib.mlsp_gn_edge_workspace_bytes(B, Nk, Nq, k, C, groups))
-        _gn_check(lib.mlsp_gn_edge_fwd_f32(u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(), gamma.data_ptr(),
-                                           beta.data_ptr(), B, Nk, Nq, k, C, groups, eps, slope, out.data_ptr(), argk.data_ptr(),
-                                           stats.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_fwd_f32")
+        _check_supported(lib.mlsp_gn_edge_fwd_f32(u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(), gamma.data_ptr(),
+                                                  beta.data_ptr(), B, Nk, Nq, k, C, groups, eps, slope, out.data_ptr(), argk.data_ptr(),
+                                                  stats.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_fwd_f32", _GN_NEEDS)
         if _sel_record is not None or _sel_forced is not None:
             _selection_hook(argk)              # test hooks: the slot the backward routes each entry's gradient to (it reads nothing else of the choice)
-        ctx.save_for_backward(u, w, idx32, gamma, beta, argk, stats)
-        ctx.cfg = (int(groups), float(slope), rev)
+        ctx.save_for_backward(u, w, gamma, beta, argk, stats)
+        ctx.cfg = (int(groups), float(slope), rev)           # idx32 rides in `rev`, as in _Va*: not a saved tensor, so no in-place check
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dOut):
         lib = _lib.load()
-        u, w, idx32, gamma, beta, argk, stats = ctx.saved_tensors
+        u, w, gamma, beta, argk, stats = ctx.saved_tensors
         groups, slope, rev = ctx.cfg
-        B, Nq, k = idx32.shape
+        idx32, B, Nq, k, Nk = rev.idx, rev.B, rev.Nq, rev.k, rev.Nk
         C = u.shape[1]
-        Nk = u.shape[0] // B
         dev = dOut.device
         dOut = dOut.contiguous()
-        if not rev:
-            rev_off = torch.empty((B * Nk + 1,), dtype=torch.int32, device=dev)
-            rev_ent = torch.empty((B * Nq * k,), dtype=torch.int32, device=dev)
-            _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, Nq, Nk, k, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
-                       "mlsp_group_reverse")
-            rev.append((rev_off, rev_ent))
-        rev_off, rev_ent = rev[0]
+        rev_off, rev_ent = rev.lists()
         du = torch.empty((B * Nk, C), dtype=torch.float32, device=dev)
         dw = torch.empty((B * Nq, C), dtype=torch.float32, device=dev)
         dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2))
         ws, wsn = _lib.workspace_of(dev, lib.mlsp_gn_edge_workspace_bytes(B, Nk, Nq, k, C, groups))
-        _gn_check(lib.mlsp_gn_edge_bwd_f32(dOut.data_ptr(), u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(),
-                                           argk.data_ptr(), stats.data_ptr(), rev_off.data_ptr(), rev_ent.data_ptr(), gamma.data_ptr(),
-                                           beta.data_ptr(), B, Nk, Nq, k, C, groups, slope, du.data_ptr(), dw.data_ptr(), dgamma.data_ptr(),
-                                           dbeta.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_bwd_f32")
-        return du, dw, None, dgamma, dbeta, None, None, None, None
+        _check_supported(lib.mlsp_gn_edge_bwd_f32(dOut.data_ptr(), u.data_ptr(), u.stride(0), w.data_ptr(), w.stride(0), idx32.data_ptr(),
+                                                  argk.data_ptr(), stats.data_ptr(), rev_off.data_ptr(), rev_ent.data_ptr(), gamma.data_ptr(),
+                                                  beta.data_ptr(), B, Nk, Nq, k, C, groups, slope, du.data_ptr(), dw.data_ptr(), dgamma.data_ptr(),
+                                                  dbeta.data_ptr(), ws, wsn, _lib.stream()), "mlsp_gn_edge_bwd_f32", _GN_NEEDS)
+        return du, dw, None, dgamma, dbeta, None, None, None
 
 
 def gn_edge_max(u, w, idx32, gamma, beta, groups, eps=1e-5, slope=0.2):
@@ -2148,15 +2153,8 @@ def gn_edge_max(u, w, idx32, gamma, beta, groups, eps=1e-5, slope=0.2):
     backward of a call builds the reverse index of idx (mlsp_group_reverse) and keeps it for the next."""
     _lib.require_gpu(u, w, idx32, gamma, beta)
     assert idx32.dtype == torch.int32 and idx32.dim() == 3, (idx32.dtype, idx32.shape)
-    return _GnEdgeMax.apply(u, w, idx32.contiguous(), gamma, beta, int(groups), float(eps), float(slope), [])
-
-
-def _attn_check(rc, what):
-    """MLSP_ERR_UNSUPPORTED of the attention / LayerNorm / GELU kernels is a MlspLibraryError: there is no other path"""
-    if rc == -3:
-        raise _lib.MlspLibraryError("%s: %s (needs channel counts %% 4 == 0 and 16-byte-aligned rows; the attention core head_dim <= 128, "
-                                    "L <= 512 and L * head_dim <= 16384)" % (what, _lib.load().mlsp_strerror(rc).decode()))
-    _lib.check(rc, what)
+    return _GnEdgeMax.apply(u, w, ReverseIndex(idx32.contiguous(), u.shape[0] // idx32.shape[0]), gamma, beta, int(groups), float(eps),
+                            float(slope))
 
 
 class _Mhsa(Function):
@@ -2172,8 +2170,8 @@ class _Mhsa(Function):
         assert qkv.shape == (B * L, 3 * d) and d % H == 0, (qkv.shape, B, L, H)
         out = torch.empty((B * L, d), dtype=torch.float32, device=qkv.device)
         lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-        _attn_check(lib.mlsp_mhsa_fwd_f32(qkv.data_ptr(), qkv.stride(0), B, L, H, d // H, scale, out.data_ptr(), lse.data_ptr(), _lib.stream()),
-                    "mlsp_mhsa_fwd_f32")
+        _check_supported(lib.mlsp_mhsa_fwd_f32(qkv.data_ptr(), qkv.stride(0), B, L, H, d // H, scale, out.data_ptr(), lse.data_ptr(), _lib.stream()),
+                         "mlsp_mhsa_fwd_f32", _ATTN_NEEDS)
         ctx.save_for_backward(qkv, lse)
         ctx.dims = (B, L, H, d // H, scale)
         ctx.mark_non_differentiable(lse)
@@ -2187,8 +2185,8 @@ class _Mhsa(Function):
         B, L, H, dh, scale = ctx.dims
         dout = dout.contiguous()
         dqkv = torch.empty((B * L, 3 * H * dh), dtype=torch.float32, device=dout.device)
-        _attn_check(lib.mlsp_mhsa_bwd_f32(qkv.data_ptr(), qkv.stride(0), lse.data_ptr(), dout.data_ptr(), B, L, H, dh, scale,
-                                          dqkv.data_ptr(), dqkv.stride(0), _lib.stream()), "mlsp_mhsa_bwd_f32")
+        _check_supported(lib.mlsp_mhsa_bwd_f32(qkv.data_ptr(), qkv.stride(0), lse.data_ptr(), dout.data_ptr(), B, L, H, dh, scale,
+                                               dqkv.data_ptr(), dqkv.stride(0), _lib.stream()), "mlsp_mhsa_bwd_f32", _ATTN_NEEDS)
         return dqkv, None, None, None, None
 
 
@@ -2224,9 +2222,9 @@ class _LayerNorm(Function):
             mean, rstd = (torch.empty((rows,), dtype=torch.float32, device=dev) for _ in range(2))
         else:
             assert add is not None, "layernorm without weight is the residual add: it needs `add`"
-        _attn_check(lib.mlsp_layernorm_fwd_f32(x.data_ptr(), _lib.ptr(add), _lib.ptr(sample_scale), rows_per_sample, _lib.ptr(weight), _lib.ptr(bias),
-                                               rows, d, eps, u.data_ptr() if add is not None else None, _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd),
-                                               _lib.stream()), "mlsp_layernorm_fwd_f32")
+        _check_supported(lib.mlsp_layernorm_fwd_f32(x.data_ptr(), _lib.ptr(add), _lib.ptr(sample_scale), rows_per_sample, _lib.ptr(weight), _lib.ptr(bias),
+                                                    rows, d, eps, u.data_ptr() if add is not None else None, _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd),
+                                                    _lib.stream()), "mlsp_layernorm_fwd_f32", _ATTN_NEEDS)
         ctx.has_add, ctx.rps, ctx.has_ln = add is not None, rows_per_sample, weight is not None
         if weight is not None:
             ctx.save_for_backward(u, weight, mean, rstd, sample_scale)
@@ -2258,8 +2256,8 @@ class _LayerNorm(Function):
             if want_add and s is not None:
                 da = torch.empty_like(du)
                 ws, wsn = _lib.workspace(du.device, 4096, d, 4)
-                _attn_check(lib.mlsp_layernorm_bwd_f32(None, du.data_ptr(), None, s.data_ptr(), ctx.rps, None, None, None, rows, d, None,
-                                                       da.data_ptr(), None, None, ws, wsn, _lib.stream()), "mlsp_layernorm_bwd_f32")
+                _check_supported(lib.mlsp_layernorm_bwd_f32(None, du.data_ptr(), None, s.data_ptr(), ctx.rps, None, None, None, rows, d, None,
+                                                            da.data_ptr(), None, None, ws, wsn, _lib.stream()), "mlsp_layernorm_bwd_f32", _ATTN_NEEDS)
             return dx, None, None, None, da, None, None
         dx = torch.empty_like(dy)
         da = None
@@ -2267,10 +2265,10 @@ class _LayerNorm(Function):
             da = torch.empty_like(dy) if s is not None else dx
         dw, db = (torch.empty((d,), dtype=torch.float32, device=dy.device) for _ in range(2))
         ws, wsn = _lib.workspace(dy.device, 4096, d, 4)
-        _attn_check(lib.mlsp_layernorm_bwd_f32(dy.data_ptr(), _lib.ptr(du), u.data_ptr(), _lib.ptr(s) if want_add else None, ctx.rps, weight.data_ptr(),
-                                               mean.data_ptr(), rstd.data_ptr(), rows, d, dx.data_ptr(),
-                                               da.data_ptr() if (want_add and s is not None) else None, dw.data_ptr(), db.data_ptr(), ws, wsn,
-                                               _lib.stream()), "mlsp_layernorm_bwd_f32")
+        _check_supported(lib.mlsp_layernorm_bwd_f32(dy.data_ptr(), _lib.ptr(du), u.data_ptr(), _lib.ptr(s) if want_add else None, ctx.rps, weight.data_ptr(),
+                                                    mean.data_ptr(), rstd.data_ptr(), rows, d, dx.data_ptr(),
+                                                    da.data_ptr() if (want_add and s is not None) else None, dw.data_ptr(), db.data_ptr(), ws, wsn,
+                                                    _lib.stream()), "mlsp_layernorm_bwd_f32", _ATTN_NEEDS)
         return dx, dw, db, None, da, None, None
 
 
@@ -2290,7 +2288,7 @@ class _Gelu(Function):
         lib = _lib.load()
         x = x.contiguous()
         y = torch.empty_like(x)
-        _attn_check(lib.mlsp_gelu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()), "mlsp_gelu_fwd_f32")
+        _check_supported(lib.mlsp_gelu_fwd_f32(x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), _lib.stream()), "mlsp_gelu_fwd_f32", _ATTN_NEEDS)
         ctx.save_for_backward(x)
         return y
 
@@ -2301,7 +2299,8 @@ class _Gelu(Function):
         x, = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        _attn_check(lib.mlsp_gelu_bwd_f32(dy.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1], dx.data_ptr(), _lib.stream()), "mlsp_gelu_bwd_f32")
+        _check_supported(lib.mlsp_gelu_bwd_f32(dy.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1], dx.data_ptr(), _lib.stream()),
+                         "mlsp_gelu_bwd_f32", _ATTN_NEEDS)
         return dx
 
 
@@ -2309,14 +2308,6 @@ def gelu(x):
     """nn.GELU()'s default (erf) form on [rows, d] float32"""
     _lib.require_gpu(x)
     return _Gelu.apply(x)
-
-
-def _token_check(rc, what):
-    """MLSP_ERR_UNSUPPORTED and MLSP_ERR_ARG of the token kernels are a MlspLibraryError: there is no other path"""
-    if rc in (-1, -3):
-        raise _lib.MlspLibraryError("%s: %s (thin_in needs Cin <= 8, C %% 4 == 0, C <= 4096 and at least 2 rows in training with BatchNorm; "
-                                    "token_pool needs L >= 2 and d %% 4 == 0)" % (what, _lib.load().mlsp_strerror(rc).decode()))
-    _lib.check(rc, what)
 
 
 class _ThinIn(Function):
@@ -2338,9 +2329,10 @@ class _ThinIn(Function):
         bn_save = torch.empty((4, C), dtype=torch.float32, device=dev) if bn else None
         xmom = torch.empty((72,), dtype=torch.float64, device=dev) if bn and training else None
         ws, wsn = _lib.workspace_of(dev, lib.mlsp_thin_in_workspace_bytes(M, Cin, C))
-        _token_check(lib.mlsp_thin_in_fwd_f32(X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma), _lib.ptr(beta),
-                                              _lib.ptr(run_mean), _lib.ptr(run_var), float(momentum), float(eps), int(training), int(act),
-                                              H.data_ptr(), _lib.ptr(bn_save), _lib.ptr(xmom), ws, wsn, _lib.stream()), "mlsp_thin_in_fwd_f32")
+        _check_supported(lib.mlsp_thin_in_fwd_f32(X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma), _lib.ptr(beta),
+                                                  _lib.ptr(run_mean), _lib.ptr(run_var), float(momentum), float(eps), int(training), int(act),
+                                                  H.data_ptr(), _lib.ptr(bn_save), _lib.ptr(xmom), ws, wsn, _lib.stream()),
+                         "mlsp_thin_in_fwd_f32", _TOKEN_NEEDS, _ARG_TOO)
         ctx.save_for_backward(X, W, bias, gamma, beta, bn_save, xmom)
         ctx.cfg = (bool(training), int(act))
         if bn:
@@ -2362,9 +2354,10 @@ class _ThinIn(Function):
         db = torch.empty((C,), dtype=torch.float32, device=dev) if bias is not None else None
         dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2)) if bn else (None, None)
         ws, wsn = _lib.workspace_of(dev, lib.mlsp_thin_in_workspace_bytes(M, Cin, C))
-        _token_check(lib.mlsp_thin_in_bwd_f32(dH.data_ptr(), X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma),
-                                              _lib.ptr(beta), _lib.ptr(bn_save), _lib.ptr(xmom), int(training), act, dW.data_ptr(), _lib.ptr(db),
-                                              _lib.ptr(dgamma), _lib.ptr(dbeta), ws, wsn, _lib.stream()), "mlsp_thin_in_bwd_f32")
+        _check_supported(lib.mlsp_thin_in_bwd_f32(dH.data_ptr(), X.data_ptr(), X.stride(0), M, Cin, W.data_ptr(), _lib.ptr(bias), C, _lib.ptr(gamma),
+                                                  _lib.ptr(beta), _lib.ptr(bn_save), _lib.ptr(xmom), int(training), act, dW.data_ptr(), _lib.ptr(db),
+                                                  _lib.ptr(dgamma), _lib.ptr(dbeta), ws, wsn, _lib.stream()),
+                         "mlsp_thin_in_bwd_f32", _TOKEN_NEEDS, _ARG_TOO)
         return None, dW, db, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -2390,7 +2383,8 @@ class _TokenPool(Function):
         assert y.shape == (B * L, d), (y.shape, B, L)
         out = torch.empty((B, 2 * d), dtype=torch.float32, device=y.device)
         arg = torch.empty((B, d), dtype=torch.int32, device=y.device)
-        _token_check(lib.mlsp_token_pool_fwd_f32(y.data_ptr(), B, L, d, out.data_ptr(), arg.data_ptr(), _lib.stream()), "mlsp_token_pool_fwd_f32")
+        _check_supported(lib.mlsp_token_pool_fwd_f32(y.data_ptr(), B, L, d, out.data_ptr(), arg.data_ptr(), _lib.stream()),
+                         "mlsp_token_pool_fwd_f32", _TOKEN_NEEDS, _ARG_TOO)
         if _sel_record is not None or _sel_forced is not None:
             _selection_hook(arg)               # test hooks: the row the backward routes each column's gradient to
         ctx.save_for_backward(arg)
@@ -2405,7 +2399,8 @@ class _TokenPool(Function):
         B, L, d = ctx.dims
         dOut = dOut.contiguous()
         dy = torch.empty((B * L, d), dtype=torch.float32, device=dOut.device)
-        _token_check(lib.mlsp_token_pool_bwd_f32(dOut.data_ptr(), arg.data_ptr(), B, L, d, dy.data_ptr(), _lib.stream()), "mlsp_token_pool_bwd_f32")
+        _check_supported(lib.mlsp_token_pool_bwd_f32(dOut.data_ptr(), arg.data_ptr(), B, L, d, dy.data_ptr(), _lib.stream()),
+                         "mlsp_token_pool_bwd_f32", _TOKEN_NEEDS, _ARG_TOO)
         return dy, None, None
 
 
@@ -2414,14 +2409,6 @@ def token_pool(y, B, L):
     lowest row wins ties and a NaN row is never chosen while a number exists.  One HIP launch per direction."""
     _lib.require_gpu(y)
     return _TokenPool.apply(y, int(B), int(L))
-
-
-def _pyramid_check(rc, what):
-    """MLSP_ERR_UNSUPPORTED and MLSP_ERR_ARG of the pyramid kernels are a MlspLibraryError: there is no other path"""
-    if rc in (-1, -3):
-        raise _lib.MlspLibraryError("%s: %s (interp3_add and cloud_mean need C %% 4 == 0, 16-byte-aligned rows and S == 1 or S >= 3 source "
-                                    "points)" % (what, _lib.load().mlsp_strerror(rc).decode()))
-    _lib.check(rc, what)
 
 
 class _Interp3Add(Function):
@@ -2436,8 +2423,8 @@ class _Interp3Add(Function):
         N = add.shape[1]
         assert add.shape == (B, N, C) and (S == 1 or (idx32.shape == (B, N, 3) and dist.shape == (B, N, 3))), (feat.shape, add.shape)
         out = torch.empty((B, N, C), dtype=torch.float32, device=feat.device)
-        _pyramid_check(lib.mlsp_interp3_add_fwd_f32(feat.data_ptr(), _lib.ptr(idx32), _lib.ptr(dist), add.data_ptr(), B, N, S, C, out.data_ptr(),
-                                                    _lib.stream()), "mlsp_interp3_add_fwd_f32")
+        _check_supported(lib.mlsp_interp3_add_fwd_f32(feat.data_ptr(), _lib.ptr(idx32), _lib.ptr(dist), add.data_ptr(), B, N, S, C, out.data_ptr(),
+                                                      _lib.stream()), "mlsp_interp3_add_fwd_f32", _PYRAMID_NEEDS, _ARG_TOO)
         ctx.save_for_backward(idx32, dist)
         ctx.dims = (B, N, S, C)
         return out
@@ -2452,15 +2439,10 @@ class _Interp3Add(Function):
         dev = dout.device
         dfeat = None
         if ctx.needs_input_grad[0]:
-            rev_off = rev_ent = None
-            if S > 1:
-                rev_off = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
-                rev_ent = torch.empty((B * N * 3,), dtype=torch.int32, device=dev)
-                _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, N, S, 3, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
-                           "mlsp_group_reverse")
+            rev_off, rev_ent = ReverseIndex(idx32, S).lists() if S > 1 else (None, None)
             dfeat = torch.empty((B, S, C), dtype=torch.float32, device=dev)
-            _pyramid_check(lib.mlsp_interp3_add_bwd_f32(dout.data_ptr(), _lib.ptr(dist), _lib.ptr(rev_off), _lib.ptr(rev_ent), B, N, S, C,
-                                                        dfeat.data_ptr(), _lib.stream()), "mlsp_interp3_add_bwd_f32")
+            _check_supported(lib.mlsp_interp3_add_bwd_f32(dout.data_ptr(), _lib.ptr(dist), _lib.ptr(rev_off), _lib.ptr(rev_ent), B, N, S, C,
+                                                          dfeat.data_ptr(), _lib.stream()), "mlsp_interp3_add_bwd_f32", _PYRAMID_NEEDS, _ARG_TOO)
         return dfeat, (dout if ctx.needs_input_grad[1] else None), None, None
 
 
@@ -2488,7 +2470,8 @@ class _CloudMean(Function):
         C = X.shape[1]
         assert X.shape == (B * N, C), (X.shape, B, N)
         out = torch.empty((B, C), dtype=torch.float32, device=X.device)
-        _pyramid_check(lib.mlsp_cloud_mean_fwd_f32(X.data_ptr(), B, N, C, out.data_ptr(), _lib.stream()), "mlsp_cloud_mean_fwd_f32")
+        _check_supported(lib.mlsp_cloud_mean_fwd_f32(X.data_ptr(), B, N, C, out.data_ptr(), _lib.stream()),
+                         "mlsp_cloud_mean_fwd_f32", _PYRAMID_NEEDS, _ARG_TOO)
         ctx.dims = (B, N, C)
         return out
 
@@ -2499,7 +2482,8 @@ class _CloudMean(Function):
         B, N, C = ctx.dims
         dOut = dOut.contiguous()
         dX = torch.empty((B * N, C), dtype=torch.float32, device=dOut.device)
-        _pyramid_check(lib.mlsp_cloud_mean_bwd_f32(dOut.data_ptr(), B, N, C, dX.data_ptr(), _lib.stream()), "mlsp_cloud_mean_bwd_f32")
+        _check_supported(lib.mlsp_cloud_mean_bwd_f32(dOut.data_ptr(), B, N, C, dX.data_ptr(), _lib.stream()),
+                         "mlsp_cloud_mean_bwd_f32", _PYRAMID_NEEDS, _ARG_TOO)
         return dX, None, None
 
 

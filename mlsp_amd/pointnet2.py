@@ -113,10 +113,7 @@ class _Interp3(Function):
         B, N, S, D = ctx.dims
         dout = dout.contiguous()
         dev = dout.device
-        rev_off = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
-        rev_ent = torch.empty((B * N * 3,), dtype=torch.int32, device=dev)
-        _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, N, S, 3, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
-                   "mlsp_group_reverse")
+        rev_off, rev_ent = Fh.ReverseIndex(idx32, S).lists()
         dfeat = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         _lib.check(lib.mlsp_interp3_bwd_f32(dout.data_ptr(), dist.data_ptr(), rev_off.data_ptr(), rev_ent.data_ptr(), B, N, S, D,
                                             dfeat.data_ptr(), _lib.stream()), "mlsp_interp3_bwd_f32")
@@ -149,29 +146,19 @@ class _Group(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dG):
-        lib = _lib.load()
         (idx32,) = ctx.saved_tensors
         B, N, S, ns, D, Cx, Cq = ctx.dims
         need_x, need_q, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1], D > 0 and ctx.needs_input_grad[2]
         if not (need_x or need_q or need_f):
             return None, None, None, None
         dG = dG.contiguous()
-        dev = dG.device
         dxyz = dq = dfeat = None
-        if need_x or need_f:
-            rev_off = torch.empty((B * N + 1,), dtype=torch.int32, device=dev)
-            rev_ent = torch.empty((B * S * ns,), dtype=torch.int32, device=dev)
-            _lib.check(lib.mlsp_group_reverse(idx32.data_ptr(), B, S, N, ns, rev_off.data_ptr(), rev_ent.data_ptr(), _lib.stream()),
-                       "mlsp_group_reverse")
+        rev = Fh.ReverseIndex(idx32, N)                       # one index for both gathers; built by the first that runs
         if need_f:
-            dfeat = torch.empty((B, N, D), dtype=torch.float32, device=dev)
-            _lib.check(lib.mlsp_sa_group_bwd_f32(dG.data_ptr(), 3 + D, 3, D, rev_off.data_ptr(), rev_ent.data_ptr(), B, N, S, ns,
-                                                 dfeat.data_ptr(), _lib.stream()), "mlsp_sa_group_bwd_f32")
+            dfeat = rev.scatter(dG, 3 + D, 3, D).view(B, N, D)
         if need_x:
             # d xyz_j = sum of the coordinate columns over the groups j sits in: the same reverse-index gather on columns 0..2 of dG, in place
-            dxyz = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-            _lib.check(lib.mlsp_sa_group_bwd_f32(dG.data_ptr(), 3 + D, 0, 3, rev_off.data_ptr(), rev_ent.data_ptr(), B, N, S, ns,
-                                                 dxyz.data_ptr(), _lib.stream()), "mlsp_sa_group_bwd_f32")
+            dxyz = rev.scatter(dG, 3 + D, 0, 3).view(B, N, 3)
         if need_q:
             dq = -dG[:, :3].reshape(B, S, ns, 3).sum(2)       # every slot of a group subtracts its centre
         return dxyz, dq, dfeat, None
@@ -259,12 +246,10 @@ def _pinned(idx, shape, bound, what):
     return idx.long()
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=False, fps_start=None, fps_idx=None, idx=None, chosen=None):
-    """pointnet_util.py:99-136: FPS centres, ball-query neighbourhoods, centred coordinates + features.
-    Returns new_xyz [B,npoint,3], new_points [B,npoint,nsample,3+D] (+ grouped_xyz, fps_idx with returnfps).
-    `fps_idx` [B,npoint] / `idx` [B,npoint,nsample] pin the centres / the neighbourhoods instead of searching them; `chosen` (a list)
-    receives (fps_idx, idx) as used."""
-    B, N, C = xyz.shape
+def _centres_and_groups(xyz, npoint, radius, nsample, knn, fps_start, fps_idx, idx, chosen):
+    """FPS centres and their neighbourhoods (pointnet_util.py:105-120), each searched or pinned by the caller: fps_idx [B,npoint] / idx
+    [B,npoint,nsample]; `chosen` (a list) receives (fps_idx, idx) as used.  -> new_xyz [B,npoint,3], fps_idx, idx"""
+    B, N, _ = xyz.shape
     fps_idx = farthest_point_sample(xyz, npoint, start=fps_start) if fps_idx is None else _pinned(fps_idx, (B, npoint), N, "fps_idx")
     new_xyz = index_points(xyz, fps_idx)
     if idx is not None:
@@ -273,6 +258,16 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=
         idx = knn_point(nsample, xyz, new_xyz) if knn else query_ball_point(radius, nsample, xyz, new_xyz)      # :116-120
     if chosen is not None:
         chosen.append((fps_idx, idx))
+    return new_xyz, fps_idx, idx
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=False, fps_start=None, fps_idx=None, idx=None, chosen=None):
+    """pointnet_util.py:99-136: FPS centres, ball-query neighbourhoods, centred coordinates + features.
+    Returns new_xyz [B,npoint,3], new_points [B,npoint,nsample,3+D] (+ grouped_xyz, fps_idx with returnfps).
+    `fps_idx` [B,npoint] / `idx` [B,npoint,nsample] pin the centres / the neighbourhoods instead of searching them; `chosen` (a list)
+    receives (fps_idx, idx) as used."""
+    B = xyz.shape[0]
+    new_xyz, fps_idx, idx = _centres_and_groups(xyz, npoint, radius, nsample, knn, fps_start, fps_idx, idx, chosen)
     G = _Group.apply(xyz, new_xyz, points, idx)
     new_points = G.view(B, npoint, nsample, -1)
     if returnfps:
@@ -322,15 +317,7 @@ class PointNetSetAbstraction(nn.Module):
             # sample_and_group (pointnet_util.py:99-136) without its output tensor: the first conv is folded onto the points (the
             # coordinates' gradient flows through the two K = 3 products u and w of _fold_first_layer, like the features')
             S, ns = self.npoint, self.nsample
-            N = xyz.shape[1]
-            fps_idx = farthest_point_sample(xyz, S, start=self.fps_start) if fps_idx is None else _pinned(fps_idx, (B, S), N, "fps_idx")
-            new_xyz = index_points(xyz, fps_idx)
-            if idx is not None:
-                idx = _pinned(idx, (B, S, ns), N, "idx")
-            else:
-                idx = knn_point(ns, xyz, new_xyz) if self.knn else query_ball_point(self.radius, ns, xyz, new_xyz)
-            if chosen is not None:
-                chosen.append((fps_idx, idx))
+            new_xyz, fps_idx, idx = _centres_and_groups(xyz, S, self.radius, ns, self.knn, self.fps_start, fps_idx, idx, chosen)
             c0 = self.mlp_convs[0]
             X = _fold_first_layer(xyz, new_xyz, points, idx, c0.weight.view(c0.out_channels, c0.in_channels), c0, self.mlp_bns[0],
                                   self.training)

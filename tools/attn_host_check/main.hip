@@ -30,7 +30,7 @@ static double worst(const float* got, const std::vector<double>& want) {
     for (size_t i = 0; i < want.size(); ++i) { e = fmax(e, fabs((double)got[i] - want[i])); m = fmax(m, fabs(want[i])); }
     return e / m;
 }
-#define ALL_THREADS(call) for (int tid = 0; tid < AB_THREADS; ++tid) { call; }
+#define ALL_THREADS(call) for (int tid = 0; tid < RT_THREADS; ++tid) { call; }
 
 static void mhsa_case(int B, int L, int d, int H) {
     const int dh = d / H, ld = 3 * d;
@@ -154,9 +154,9 @@ static void ln_case(long long rows, int d, int rps, bool with_add, bool with_sca
             ALL_THREADS(ln_bwd_1(gb, b, row0, tid, red.p));
             ALL_THREADS(ln_bwd_2(gb, b, row0, tid, red.p));
         }
-    const int ct = d4 < AB_THREADS ? d4 : AB_THREADS, rl = AB_THREADS / ct, nparts = 5;
+    const int ct = d4 < RT_THREADS ? d4 : RT_THREADS, rl = RT_THREADS / ct, nparts = 5;
     const long long chunk = (rows + nparts - 1) / nparts;
-    Buf part((size_t)nparts * d * 2), sh(AB_THREADS * 8);
+    Buf part((size_t)nparts * d * 2), sh(RT_THREADS * 8);
     for (int bid = 0; bid < nparts; ++bid) {
         const long long e0 = bid * chunk, e1 = e0 + chunk < rows ? e0 + chunk : rows;
         for (int cq0 = 0; cq0 < d4; cq0 += ct) {
@@ -164,7 +164,7 @@ static void ln_case(long long rows, int d, int rps, bool with_add, bool with_sca
             ALL_THREADS(ln_par_2(gb, bid, cq0, ct, rl, tid, sh.p, part.p));
         }
     }
-    for (int c = 0; c < (d + AB_THREADS - 1) / AB_THREADS * AB_THREADS; ++c) ln_par_fin(part.p, nparts, d, c, dg.p, db.p);
+    for (int c = 0; c < (d + RT_THREADS - 1) / RT_THREADS * RT_THREADS; ++c) ln_par_fin(part.p, nparts, d, c, dg.p, db.p);
     std::vector<double> wdx(n), wdg(d, 0.0), wdb(d, 0.0);
     for (long long r = 0; r < rows; ++r) {
         double m = 0.0, v = 0.0, m1 = 0.0, m2 = 0.0;

@@ -34,17 +34,17 @@ static double worst(const float* got, const std::vector<double>& want) {
     for (size_t i = 0; i < want.size(); ++i) { e = fmax(e, fabs((double)got[i] - want[i])); m = fmax(m, fabs(want[i])); }
     return e / m;
 }
-#define ALL_THREADS(call) for (int tid = 0; tid < GE_THREADS; ++tid) { call; }
+#define ALL_THREADS(call) for (int tid = 0; tid < RT_THREADS; ++tid) { call; }
 
-// the walk of GE_FOR_ITEMS with a grid of `grid` workgroups
+// the walk of RT_FOR_ITEMS (rowtile.h) with a grid of `grid` workgroups
 template <typename F>
 static void for_items(long long rows, int c4, int grid, F f) {
-    const int rb = c4 >= 1024 ? 1 : 1024 / c4;
+    const int rb = row_tiles(rows, c4).rb;
     for (int bid = 0; bid < grid; ++bid)
         for (long long r0 = (long long)bid * rb; r0 < rows; r0 += (long long)grid * rb) {
             const int n = (int)((rows - r0 < rb ? rows - r0 : (long long)rb) * c4);
-            for (int tid = 0; tid < GE_THREADS; ++tid)
-                for (int it = tid; it < n; it += GE_THREADS) f(r0 + it / c4, it % c4);
+            for (int tid = 0; tid < RT_THREADS; ++tid)
+                for (int it = tid; it < n; it += RT_THREADS) f(r0 + it / c4, it % c4);
         }
 }
 
@@ -77,7 +77,7 @@ static void edge_case(int B, int Nk, int Nq, int k, int C, int groups, bool hubs
     }
     // forward: gn_edge_stats_kernel, gn_edge_stats_finalize_kernel, gn_edge_apply_kernel
     {
-        Buf<double> part(ge_fwd_ws_doubles(g)), sh(GE_THREADS * 2);
+        Buf<double> part(ge_fwd_ws_doubles(g)), sh(RT_THREADS * 2);
         for (int bid = 0; bid < B * g.np; ++bid) {
             const int b = bid / g.np, p = bid - b * g.np;
             for (int cq0 = 0; cq0 < g.c4; cq0 += g.ct) {
@@ -85,12 +85,12 @@ static void edge_case(int B, int Nk, int Nq, int k, int C, int groups, bool hubs
                 ALL_THREADS(ge_stats_2(g, b, p, cq0, tid, sh.p, part.p));
             }
         }
-        for (long long t = 0; t < (long long)(B * groups + GE_THREADS - 1) / GE_THREADS * GE_THREADS; ++t) ge_stats_fin(g, t, part.p, stats.p);
+        for (long long t = 0; t < (long long)(B * groups + RT_THREADS - 1) / RT_THREADS * RT_THREADS; ++t) ge_stats_fin(g, t, part.p, stats.p);
         for_items((long long)Pq, g.c4, 3, [&](long long i, int cq) { ge_apply_item(g, i, cq, stats.p, out.p, argk.p); });
     }
     // backward: gn_edge_bsum_kernel, gn_edge_bfin_cloud_kernel, gn_edge_bfin_param_kernel, gn_edge_bwd_dw_kernel, gn_edge_bwd_du_kernel
     {
-        Buf<float> chpart(ge_bwd_ws_floats(g)), sh(GE_THREADS * 8), ab((size_t)B * groups * 2);
+        Buf<float> chpart(ge_bwd_ws_floats(g)), sh(RT_THREADS * 8), ab((size_t)B * groups * 2);
         Buf<double> cloud(ge_bwd_ws_doubles(g));
         for (int bid = 0; bid < B * g.np; ++bid) {
             const int b = bid / g.np, p = bid - b * g.np;
@@ -103,7 +103,7 @@ static void edge_case(int B, int Nk, int Nq, int k, int C, int groups, bool hubs
             ALL_THREADS(ge_bfin_1(g, b, tid, chpart.p, cloud.p));
             ALL_THREADS(ge_bfin_2(g, b, tid, cloud.p, ab.p));
         }
-        for (int c = 0; c < (C + GE_THREADS - 1) / GE_THREADS * GE_THREADS; ++c) ge_bfin_param(g, c, cloud.p, dgamma.p, dbeta.p);
+        for (int c = 0; c < (C + RT_THREADS - 1) / RT_THREADS * RT_THREADS; ++c) ge_bfin_param(g, c, cloud.p, dgamma.p, dbeta.p);
         for_items((long long)Pq, g.c4, 2, [&](long long i, int cq) { ge_bwd_dw_item(g, i, cq, stats.p, ab.p, dOut.p, argk.p, dw.p); });
         for_items((long long)Pk, g.c4, 2, [&](long long j, int cq) { ge_bwd_du_item(g, j, cq, stats.p, ab.p, dOut.p, argk.p, rev_off.p, rev_ent.p, du.p); });
     }

@@ -34,24 +34,24 @@ static double worst(const float* got, const std::vector<double>& want) {
     for (size_t i = 0; i < want.size(); ++i) { e = fmax(e, fabs((double)got[i] - want[i])); m = fmax(m, fabs(want[i])); }
     return e / m;
 }
-// the item loop of pyramid.hip's PY_ITEM_LOOP on a grid of `grid` workgroups
+// the item loop of pyramid.hip (RT_FOR_ITEMS of rowtile.h) on a grid of `grid` workgroups
 template <typename F>
 static void item_loop(const PyGeo& g, long long rows, int grid, F f) {
-    const int rb = g.c4 >= 1024 ? 1 : 1024 / g.c4;
+    const int rb = row_tiles(rows, g.c4).rb;
     for (int bid = 0; bid < grid; ++bid)
         for (long long r0 = (long long)bid * rb; r0 < rows; r0 += (long long)grid * rb) {
             const int n = (int)((rows - r0 < rb ? rows - r0 : (long long)rb) * g.c4);
-            for (int tid = 0; tid < PY_THREADS; ++tid)
-                for (int it = tid; it < n; it += PY_THREADS) f(r0 + it / g.c4, it % g.c4);
+            for (int tid = 0; tid < RT_THREADS; ++tid)
+                for (int it = tid; it < n; it += RT_THREADS) f(r0 + it / g.c4, it % g.c4);
         }
 }
 static void cloud_sum(const PyGeo& g, double div, const float* X, float* out) {
-    Buf<double> sh((size_t)PY_THREADS * 4);
+    Buf<double> sh((size_t)RT_THREADS * 4);
     for (int bid = 0; bid < g.B * g.nqb; ++bid) {
         const int b = bid / g.nqb, cq0 = (bid - b * g.nqb) * g.ct;
         for (size_t i = 0; i < sh.n; ++i) sh.p[i] = 1e300;                  // (what another workgroup left behind)
-        for (int tid = 0; tid < PY_THREADS; ++tid) py_cloud_sum_1(g, b, cq0, tid, X, sh.p);
-        for (int tid = 0; tid < PY_THREADS; ++tid) py_cloud_sum_2(g, b, cq0, tid, sh.p, div, out);
+        for (int tid = 0; tid < RT_THREADS; ++tid) py_cloud_sum_1(g, b, cq0, tid, X, sh.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) py_cloud_sum_2(g, b, cq0, tid, sh.p, div, out);
     }
 }
 

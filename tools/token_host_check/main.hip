@@ -50,25 +50,25 @@ static void thin_run(const TkGeo& g, Buf<float>& H, Buf<float>& bn_save, Buf<dou
             for (int tid = 0; tid < TK_MOM_THREADS; ++tid) tk_mom_1<KC>(g, wg, tid, sh.p);
             for (int tid = 0; tid < TK_MOM_THREADS; ++tid) tk_mom_2(g, wg, tid, sh.p, part.p);
         }
-        for (int tid = 0; tid < TK_THREADS; ++tid) tk_fin_1(g, tid, part.p, shf.p);
-        for (int tid = 0; tid < TK_THREADS; ++tid) tk_fin_2(g, tid, shf.p, xmom.p);
-        for (int tid = 0; tid < TK_THREADS; ++tid) tk_fin_3(g, tid, xmom.p, bn_save.p, rm.p, rv.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) tk_fin_1(g, tid, part.p, shf.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) tk_fin_2(g, tid, shf.p, xmom.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) tk_fin_3(g, tid, xmom.p, bn_save.p, rm.p, rv.p);
     } else if (g.mode == TK_MODE_RUNNING) {
-        for (int c = 0; c < (g.C + TK_THREADS - 1) / TK_THREADS * TK_THREADS; ++c) tk_running_item(g, c, rm.p, rv.p, bn_save.p);
+        for (int c = 0; c < (g.C + RT_THREADS - 1) / RT_THREADS * RT_THREADS; ++c) tk_running_item(g, c, rm.p, rv.p, bn_save.p);
     }
     const float* bs = g.mode == TK_MODE_PLAIN ? nullptr : bn_save.p;
     const double* xm = g.mode == TK_MODE_BATCH ? xmom.p : nullptr;
     for (int wg = 0; wg < g.a_np; ++wg)
         for (int cq0 = 0; cq0 < g.c4; cq0 += g.ct)
-            for (int tid = 0; tid < TK_THREADS; ++tid) tk_apply<KC, MODE>(g, wg, cq0, tid, bs, xm, H.p);
+            for (int tid = 0; tid < RT_THREADS; ++tid) tk_apply<KC, MODE>(g, wg, cq0, tid, bs, xm, H.p);
     // backward: thin_in_bwd_sums_kernel, thin_in_bwd_finalize_kernel
-    Buf<float> part(tk_bwd_ws_floats(g)), sh((size_t)TK_THREADS * (2 + KC) * 4);
+    Buf<float> part(tk_bwd_ws_floats(g)), sh((size_t)RT_THREADS * (2 + KC) * 4);
     for (int wg = 0; wg < g.b_np; ++wg)
         for (int cq0 = 0; cq0 < g.c4; cq0 += g.ct) {
-            for (int tid = 0; tid < TK_THREADS; ++tid) tk_bwd_1<KC, MODE>(g, wg, cq0, tid, bs, xm, dH.p, sh.p);
-            for (int tid = 0; tid < TK_THREADS; ++tid) tk_bwd_2(g, wg, cq0, tid, sh.p, part.p);
+            for (int tid = 0; tid < RT_THREADS; ++tid) tk_bwd_1<KC, MODE>(g, wg, cq0, tid, bs, xm, dH.p, sh.p);
+            for (int tid = 0; tid < RT_THREADS; ++tid) tk_bwd_2(g, wg, cq0, tid, sh.p, part.p);
         }
-    for (int c = 0; c < (g.C + TK_THREADS - 1) / TK_THREADS * TK_THREADS; ++c)
+    for (int c = 0; c < (g.C + RT_THREADS - 1) / RT_THREADS * RT_THREADS; ++c)
         tk_bwd_fin(g, c, part.p, bs, xm, dW.p, db.p, g.mode == TK_MODE_PLAIN ? nullptr : dgamma.p, g.mode == TK_MODE_PLAIN ? nullptr : dbeta.p);
 }
 
@@ -149,8 +149,8 @@ static void thin_case(int M, int Cin, int C, int mode, int act, float off) {
 static void pool_case(int B, int L, int d, bool nans) {
     TpGeo g;
     EXPECT(tp_geo(B, L, d, g));
-    Buf<float> y((size_t)B * L * d), out((size_t)B * 2 * d), dOut((size_t)B * 2 * d), dy((size_t)B * L * d), sh_v(TK_THREADS * 4);
-    Buf<int> arg((size_t)B * d), sh_a(TK_THREADS * 4);
+    Buf<float> y((size_t)B * L * d), out((size_t)B * 2 * d), dOut((size_t)B * 2 * d), dy((size_t)B * L * d), sh_v(RT_THREADS * 4);
+    Buf<int> arg((size_t)B * d), sh_a(RT_THREADS * 4);
     fill(y, 1.f); fill(dOut, 1.f);
     if (L > 3) for (int c = 0; c < d; c += 3) y.p[(size_t)3 * d + c] = y.p[(size_t)2 * d + c] = 2.f;        // a tie at the top: row 2 wins
     if (nans) {
@@ -161,16 +161,16 @@ static void pool_case(int B, int L, int d, bool nans) {
     // token_pool_fwd_kernel, token_pool_bwd_kernel
     for (int bid = 0; bid < B * g.nqb; ++bid) {
         const int b = bid / g.nqb, cq0 = (bid - b * g.nqb) * g.ct;
-        for (int tid = 0; tid < TK_THREADS; ++tid) tp_fwd_1(g, b, cq0, tid, y.p, sh_v.p, sh_a.p);
-        for (int tid = 0; tid < TK_THREADS; ++tid) tp_fwd_2(g, b, cq0, tid, y.p, sh_v.p, sh_a.p, out.p, arg.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) tp_fwd_1(g, b, cq0, tid, y.p, sh_v.p, sh_a.p);
+        for (int tid = 0; tid < RT_THREADS; ++tid) tp_fwd_2(g, b, cq0, tid, y.p, sh_v.p, sh_a.p, out.p, arg.p);
     }
-    const int rb = g.c4 >= 1024 ? 1 : 1024 / g.c4, grid = 3;
     const long long rows = (long long)B * L;
+    const int rb = row_tiles(rows, g.c4).rb, grid = 3;
     for (int bid = 0; bid < grid; ++bid)
         for (long long r0 = (long long)bid * rb; r0 < rows; r0 += (long long)grid * rb) {
             const int n = (int)((rows - r0 < rb ? rows - r0 : (long long)rb) * g.c4);
-            for (int tid = 0; tid < TK_THREADS; ++tid)
-                for (int it = tid; it < n; it += TK_THREADS) tp_bwd_item(g, r0 + it / g.c4, it % g.c4, dOut.p, arg.p, dy.p);
+            for (int tid = 0; tid < RT_THREADS; ++tid)
+                for (int it = tid; it < n; it += RT_THREADS) tp_bwd_item(g, r0 + it / g.c4, it % g.c4, dOut.p, arg.p, dy.p);
         }
     for (int b = 0; b < B; ++b)
         for (int c = 0; c < d; ++c) {
