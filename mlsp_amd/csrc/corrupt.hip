@@ -5,7 +5,7 @@
 #include "common.h"
 
 // Y[b][j] = id of the voxel (x*n*n + y*n + z) whose OPEN box contains the clamped point, 0 when none does (points on a
-// voxel face): the reference labels by overwriting inside three nested loops, which is the same thing because the boxes
+// voxel face, points with a NaN coordinate): the reference labels by overwriting inside three nested loops, which is the same thing because the boxes
 // are disjoint.  thr[0..n] are the fp32 box edges -1 + i*d exactly as torch rounds the Python scalars; clip = fp32(0.99999999).
 __global__ __launch_bounds__(256) void region_assign_kernel(const float* __restrict__ X, int C, int N, int total, const float* __restrict__ thr,
                                                             int n, float clip, int* __restrict__ Y) {
@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void region_assign_kernel(const float* __restr
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         float v = xb[(size_t)a * N + j];
-        v = fminf(fmaxf(v, -clip), clip);
+        v = fminf(fmaxf(v, -clip), clip);      // a NaN becomes -clip; fp32(0.99999999) is 1, the outer face thr[0]: no box, like the reference's NaN
         int r = -1;
         for (int i = 0; i < n; ++i)
             if (thr[i] < v && v < thr[i + 1]) r = i;

@@ -109,6 +109,7 @@ int launch_radius_count(hipStream_t st, const float* x, int ld, int B, int N, fl
     return mlsp_launch_status();
 }
 int launch_knn_normals(hipStream_t st, const float* x, int ld, const int* idx, int B, int N, int k, float* normals) {
+    if (!x || !idx || !normals || B <= 0 || N <= 0 || k < 1 || ld < 3) return MLSP_ERR_ARG;
     int P = B * N;
     hipLaunchKernelGGL(knn_normals_kernel, dim3((P + 255) / 256), dim3(256), 0, st, x, ld, idx, P, N, k, normals);
     return mlsp_launch_status();

@@ -17,12 +17,13 @@ from .labels import cal_density, cal_density_gpu, estimate_normals   # noqa: F40
 DefRec_SCALER = 20.0   # MLSP/mlsp.py:7
 
 
-def deform_input(X, lookup, DefRec_dist='volume_based_voxels', device='cuda:0', groups=1, region_ids=None, noise=None, choice=None):
+def deform_input(X, lookup, DefRec_dist='volume_based_voxels', device='cuda:0', groups=1, region_ids=None, noise=None, choice=None, u=None):
     """MLSP/mlsp.py:10-51.  X [B,C,N] is deformed IN PLACE (as in the reference) and returned with the 0/1 mask [B,C,N].
     Per cloud the first `groups` voxels of a random visiting order that hold >= 40 points collapse to a Gaussian blob
     (std sqrt(0.001), pc_utils.draw_from_gaussian) around the voxel centre `lookup[i]`.
     The random inputs may be injected for reproducible runs: `region_ids` (a permutation of the 27 voxel ids; default
-    np.random.permutation like :27) and `noise` [B,3,N] standard normal (default torch.randn on the device)."""
+    np.random.permutation like :27) and `noise` [B,3,N] standard normal (default torch.randn on the device); for
+    'volume_based_radius' the pick: `choice` [B] point indices below N, or `u` [B] in [0,1) (default torch.rand)."""
     if DefRec_dist not in ('volume_based_voxels', 'volume_based_radius'):
         raise ValueError("DefRec_dist must be 'volume_based_voxels' or 'volume_based_radius'")
     lib = _lib.load()
@@ -36,14 +37,25 @@ def deform_input(X, lookup, DefRec_dist='volume_based_voxels', device='cuda:0', 
     B, C, N = X.shape
     if DefRec_dist == 'volume_based_radius':
         # pc_utils.collapse_to_point per cloud (utils/pc_utils.py:76-111): a random point with >= MIN_POINTS points inside RADIUS
-        # attracts everything within RADIUS of it; `choice` [B] pins the picked points (default: uniform among the candidates)
+        # attracts everything within RADIUS of it; `choice` [B] pins the picked points (negative: not pinned); otherwise `u` [B] in [0,1)
+        # (default torch.rand) picks candidate number int(u * ncand), counted in ascending index: uniform among the candidates
         if C != 3:
             raise ValueError("'volume_based_radius' needs [B,3,N] clouds (the reference assigns a 3-row block)")
         if noise is None:
             noise = torch.randn(B, 3, N, device=X.device)
         scaled = (noise.to(X.device, torch.float32) * float(np.sqrt(0.001))).contiguous()
-        ch = None if choice is None else torch.as_tensor(np.asarray(choice), dtype=torch.int32).to(X.device)
-        u = torch.rand(B, device=X.device)
+        ch = None
+        if choice is not None:
+            choice = np.asarray(choice.cpu() if torch.is_tensor(choice) else choice).reshape(-1)
+            if choice.shape[0] != B or (choice >= N).any():       # the kernel reads the picked point from its copy of the cloud
+                raise ValueError("choice must hold one index below N=%d (or a negative value: draw) per cloud, got %r" % (N, choice.tolist()))
+            ch = torch.as_tensor(choice, dtype=torch.int32).to(X.device)
+        if u is None:
+            u = torch.rand(B, device=X.device)
+        else:
+            u = torch.as_tensor(u, dtype=torch.float32).reshape(-1).to(X.device).contiguous()
+            if u.shape[0] != B:
+                raise ValueError("u must hold one value per cloud")
         mask = torch.empty_like(X)
         chosen = torch.empty(B, dtype=torch.int32, device=X.device)
         _lib.check(lib.mlsp_collapse_to_point_f32(X.data_ptr(), B, N, _lib.ptr(ch), u.data_ptr(), scaled.data_ptr(),

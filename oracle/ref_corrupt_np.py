@@ -1,11 +1,13 @@
 """CPU oracle (TEST INFRASTRUCTURE ONLY) for the input-corruption row: numpy restatement of
 utils/pc_utils.py:33-73 (assign_region_to_point), MLSP/mlsp.py:10-51 (deform_input, 'volume_based_voxels') and
-MLSP/PCM.py:6-38 (mix_shapes) / utils/pc_utils.py:137-161 (farthest_point_sample) with every random draw passed in.
+MLSP/PCM.py:6-73 (mix_shapes, mix_shapes_segmentation) / utils/pc_utils.py:137-161 (farthest_point_sample) with every random draw passed in.
 Pinned to the reference: tests/golden/deform_*.npz and pcm_*.npz were captured by running the reference functions with
 seeded / recorded random draws (tools/make_golden.py corrupt); tests/test_corrupt_oracle_cpu.py checks this file against them.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import this module.
 """
 import numpy as np
+
+ROW_CHUNK = 512       # rows of an N x N pair matrix held at a time
 
 
 def assign_region(X, n=3):
@@ -73,6 +75,18 @@ def mix_shapes(X, index, lam, start_a, start_b, points_perm):
     return np.concatenate([va, vb], 2)[:, :, points_perm]
 
 
+def mix_shapes_segmentation(X, Y, index, lam, start_a, start_b, points_perm):
+    """MLSP/PCM.py:40-73 with the draws passed in.  X [B,C,N], Y [B,N] -> (mixed_X, mixed_Y): the labels are gathered through the
+    same FPS indices and the same point permutation as their points."""
+    B, C, N = X.shape
+    na = round(lam * N)
+    nb = N - round(lam * N)
+    ia, va = fps(X, na, start_a) if na else (np.zeros((B, 0), np.int64), np.zeros((B, C, 0), np.float32))
+    ib, vb = fps(X[index], nb, start_b) if nb else (np.zeros((B, 0), np.int64), np.zeros((B, C, 0), np.float32))
+    mixed_Y = np.concatenate([np.take_along_axis(Y, ia, 1), np.take_along_axis(Y[index], ib, 1)], 1)
+    return np.concatenate([va, vb], 2)[:, :, points_perm], mixed_Y[:, points_perm]
+
+
 def rotation_matrix(angles):
     """MLSP/mlsp.py:91-112 rotate_point_cloud_3d: R = R1(y) R2(x) R3(z), float64."""
     c, s_ = np.cos(angles), np.sin(angles)
@@ -104,11 +118,12 @@ def scan(X, pixel_size, angles):
     return out, mask
 
 
-def collapse_to_point(X, choice, noise, radius=0.5, min_pts=20):
+def collapse_to_point(X, choice, noise, radius=0.5, min_pts=20, flags=True):
     """deform_input(..., 'volume_based_radius') = utils/pc_utils.py:76-111 collapse_to_point per cloud, with the random draws passed in:
     `choice` [B] the picked candidate of every cloud, `noise` [B,3,N] standard normal (scaled by sqrt(0.001) like draw_from_gaussian).
     X [B,3,N] -> (deformed copy, mask [B,3,N], candidate flags [B,N]).  fp32 arithmetic in the reference's association:
-    pd = (xx_j + (-2 x_i.x_j)) + xx_i, in-radius iff pd <= radius^2, candidate iff >= min_pts points in radius."""
+    pd = (xx_j + (-2 x_i.x_j)) + xx_i, in-radius iff pd <= radius^2, candidate iff >= min_pts points in radius.  flags=False evaluates
+    only the picked points' rows (the flags of the other rows stay False)."""
     X = X.astype(np.float32).copy()
     B, _, N = X.shape
     mask = np.zeros_like(X)
@@ -118,15 +133,47 @@ def collapse_to_point(X, choice, noise, radius=0.5, min_pts=20):
     for b in range(B):
         x = X[b]
         xx = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]
-        dot = (x[0][:, None] * x[0][None, :] + x[1][:, None] * x[1][None, :]) + x[2][:, None] * x[2][None, :]
-        pd = (xx[None, :] + np.float32(-2.0) * dot) + xx[:, None]
-        inr = pd <= r2
-        cand[b] = inr.sum(1) >= min_pts
+        inr_p = None
         p = int(choice[b])
+        for lo in range(0, N, ROW_CHUNK):                      # rows of the N x N matrix, a slab at a time
+            r = slice(lo, min(lo + ROW_CHUNK, N))
+            if not flags and not r.start <= p < r.stop:
+                continue
+            dot = (x[0][r, None] * x[0][None, :] + x[1][r, None] * x[1][None, :]) + x[2][r, None] * x[2][None, :]
+            pd = (xx[None, :] + np.float32(-2.0) * dot) + xx[r, None]
+            inr = pd <= r2
+            cand[b, r] = inr.sum(1) >= min_pts
+            if r.start <= p < r.stop:
+                inr_p = inr[p - r.start].copy()
         if p < 0:
             continue
-        hit = inr[p]
+        hit = inr_p
         centre = x[:, p].copy()
         X[b][:, hit] = centre[:, None] + noise[b][:, hit].astype(np.float32) * std
         mask[b][:, hit] = 1.0
     return X, mask, cand
+
+
+def collapse_pick(cand, u):
+    """The point the rank-selection branch of collapse_to_point picks: per cloud candidate number
+    min(int(fp32(u) * fp32(ncand)), ncand - 1) in ascending index among the candidate flags `cand` [B,N]; -1 without a candidate."""
+    pick = -np.ones(cand.shape[0], np.int64)
+    for b in range(cand.shape[0]):
+        ids = np.nonzero(cand[b])[0]
+        if len(ids):
+            pick[b] = ids[min(int(np.float32(u[b]) * np.float32(len(ids))), len(ids) - 1)]
+    return pick
+
+
+def collapse_ambiguous_pairs(X, radius=0.5, ulps=16.0):
+    """Number of ordered pairs (i, j) of X [B,3,N] whose float64 squared distance lies within ulps * 2^-24 * (xx_i + xx_j + r^2) of
+    r^2: there an fp32 evaluation of pd (with or without a fused dot product) may fall on either side of the radius test."""
+    r2 = float(np.float32(radius ** 2))
+    n = 0
+    for x in X.astype(np.float64):
+        xx = (x * x).sum(0)
+        for lo in range(0, x.shape[1], ROW_CHUNK):
+            r = slice(lo, lo + ROW_CHUNK)
+            pd = xx[None, :] - 2.0 * (x[:, r].T @ x) + xx[r, None]
+            n += int((np.abs(pd - r2) <= ulps * 2.0 ** -24 * (xx[None, :] + xx[r, None] + r2)).sum())
+    return n
