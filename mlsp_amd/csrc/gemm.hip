@@ -19,12 +19,9 @@
 // Block -> tile mapping keeps all column tiles of one 128-row panel on one XCD (blockIdx % 8 is the
 // XCD label under round-robin dispatch), so the activation panel is fetched into one L2 only.
 #include "common.h"
-#include "../../include/mlsp_hip.h"
+#include "gemm_plan.h"     // BM / BN / BK, SX_XF_KMAX, and what a launch of a given shape will do
 #include <cstdlib>
 
-#define BM 128
-#define BN 128
-#define BK 32
 #define SROW 36    // LDS row pitch (floats) for operands whose global source is row-major: image [rows][BK+4]
 #define SKMJ 128   // LDS stride for operands whose global source is k-major    [K][rows]
 
@@ -663,7 +660,6 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define SX_RPITCH 80
 #define SX_KPITCH 320
 #define SX_LDS __attribute__((address_space(3)))
-#define SX_XF_KMAX 1024          // channels (K range of one workgroup) of an A-side operand transform in gemm_split_kernel
 
 // this lane's byte offset of a fragment inside an image (rows rb .. rb+31 of the tile start at + rb * (KMAJ ? 2 : SX_RPITCH))
 template <bool KMAJ>
@@ -1416,57 +1412,39 @@ int launch_slab_reduce(hipStream_t st, const float* slab, float* C, int M, int N
     return mlsp_launch_status();
 }
 
-// How many K splits a launch will use (shared by the launcher and mlsp_workspace_bytes).
-static int gemm_pick_split(int M, int N, int K) {
-    int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-    long tiles = (long)ntm * ntn;
-    int ktiles = (K + BK - 1) / BK;
-    if (tiles >= 256 || ktiles < 4) return 1;
-    long want = (512 + tiles - 1) / tiles;          // aim at ~2 blocks per CU (measured: 320 is 35 % slower on the wgrad shapes; 768 / 1024 and 64-row tiles for the split launches: no gain)
-    int ns = (int)(want < ktiles / 2 ? want : ktiles / 2);
-    if (ns < 1) ns = 1;
-    if (ns > 256) ns = 256;
-    return ns;
+// ---- the shape queries: gemm_plan.h states each over the plan of a launch of that shape; here they meet the CallCtx and the operands ----
+static GemmAsk gemm_ask(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int ldc) {
+    GemmAsk q;
+    q.mode = cx.mode(); q.split_half = cx.split_half();
+    q.ta = ta; q.tb = tb; q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
+    q.a16 = ((uintptr_t)A & 15) == 0; q.b16 = ((uintptr_t)B & 15) == 0;
+    q.slab_floats = (size_t)-1;
+    return q;
 }
-
 // number of BN-statistic partial rows a stats-fused launch writes (0: the launch would split K, use colstats)
-// 64-row tiles when the 128-row grid is too small to keep ~3 workgroups per CU busy (and K is not split)
-// mode 2: does a contraction of `ktiles` K-tiles per workgroup go to the split kernel?  Short K loops stay on the fp32 kernel (measured per
-// launch on the headline step, tools/cmp_dump.py, and per shape, tools/x6/lib_bench: the split kernel's longer prologue loses at K = 64 and,
-// at K = 128, on grids too small to hide it: few rows AND a single column tile)
-static bool gemm_split_pays(int M, int N, int ktiles) {
-    return ktiles >= 8 || (ktiles >= 4 && (N >= 256 || M >= 16384));
-}
-static int gemm_pick_bm(const CallCtx& cx, int M, int N, int K) {
-    long tiles128 = (long)((M + 127) / 128) * ((N + BN - 1) / BN);
-    // the split kernel amortises its operand split over the tile: 128 rows unless the grid would not fill the 512 workgroup slots
-    const long few = (cx.mode() == 2 && gemm_split_pays(M, N, (K + BK - 1) / BK)) ? 512 : 1536;
-    return (gemm_pick_split(M, N, K) == 1 && tiles128 < few && M >= 256) ? 64 : 128;
-}
-int gemm_stat_parts(const CallCtx& cx, int M, int N, int K) {
-    if (gemm_pick_split(M, N, K) != 1) return 0;
-    int bm = gemm_pick_bm(cx, M, N, K);
-    return (M + bm - 1) / bm;
-}
-int gemm_panel_rows(const CallCtx& cx, int M, int N, int K) { return gemm_pick_bm(cx, M, N, K); }
-
-// A 64 x 64 weight gradient over many rows (dW = dY^T X of a 64 -> 64 layer over the edges of a set-abstraction level): neither the 128-row
-// tile kernels (a quarter of the tile used, predicated path) nor the N = 64 kernel (M % 128) fit it.  With contiguous operands two
-// consecutive rows are ONE row of a [K/2][128] matrix, and  A2^T B2  (128 x 128, an interior-tile launch) holds the even-row sum in its
-// upper-left 64 x 64 block and the odd-row sum in its lower-right one: dW = their sum.  Twice the products on the fast kernel instead of four
-// times on the slow one (configs[3]: 216 -> 70 us per step).
-static bool gemm_fold64(bool ta, bool tb, int M, int N, int K, int lda, int ldb) {
-    return ta && !tb && M == 64 && N == 64 && lda == 64 && ldb == 64 && K % 64 == 0 && K >= 8192;
-}
+int gemm_stat_parts(const CallCtx& cx, int M, int N, int K) { return gemm_q_stat_parts(cx.mode(), M, N, K); }
+int gemm_panel_rows(const CallCtx& cx, int M, int N, int K) { return gemm_q_panel_rows(cx.mode(), M, N, K); }
 size_t gemm_slab_floats(int M, int N, int K) {
-    int ns = gemm_pick_split(M, N, K);
-    size_t a = ns > 1 ? (size_t)ns * M * N : 0;
-    const size_t b = thin_tn_slab_floats(M, N, K);      // thin.hip: A^T B with one side <= 16
-    if (gemm_fold64(true, false, M, N, K, 64, 64)) {    // the folded launch's slab + its 128 x 128 result
-        const size_t f = gemm_slab_floats(128, 128, K / 2) + 128 * 128;
-        a = a > f ? a : f;
-    }
+    const size_t a = gemm_q_slab_floats(M, N, K), b = thin_tn_slab_floats(M, N, K);      // thin.hip: A^T B with one side <= 16
     return a > b ? a : b;
+}
+// Can this contraction stage `which` (1: A [M][K] row-major, 2: B [K][N] k-major) through the operand transform?  The streaming kernels
+// of thin.hip where they take the shape; else the MFMA tile kernels on interior tiles: gemm_split_kernel<.., XF, XD> where the split
+// kernel pays, the fp32 transform kernels on the short-K launches (exact fp32 products either way).
+bool gemm_xf_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which) {
+    return gemm_q_xf_supported(gemm_ask(cx, ta, tb, M, N, K, A, lda, B, ldb, N), which, thin_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, which));
+}
+// will a transform launch of this shape run on gemm_split_kernel (the only kernel that transforms inside a block-diagonal launch)?
+bool gemm_xf_on_split(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, int which) { return gemm_q_xf_on_split(cx.mode(), M, N, K, which); }
+// Row panels (of 128 rows) a dgrad dX [M][N] = dY [M][K] W with the fused statistics pass (GemmBs) writes partial sums for; 0: this
+// shape does not take the fused pass (the caller runs the streaming reduction instead).
+int gemm_bs_parts(const CallCtx& cx, int M, int N, int K, int lda, int ldb, int ldc) {
+    return gemm_q_bs_parts(gemm_ask(cx, false, false, M, N, K, nullptr, lda, nullptr, ldb, ldc));
+}
+// Can the layer's dgrad (ta = tb = false: dX [M][N] = dY [M][K] W) / weight gradient (ta, !tb: dW [M][N] = dY^T [K][M] X [K][N]) form dY from
+// (d', y) in its A operand loads (GemmDy)?  gemm_split_kernel only: interior tiles, 16-byte loads, the dgrad's K range within SX_XF_KMAX.
+bool gemm_dy_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
+    return gemm_q_dy_supported(gemm_ask(cx, ta, tb, M, N, K, A, lda, B, ldb, N));
 }
 __global__ __launch_bounds__(256) void gemm_fold64_sum_kernel(const float* __restrict__ C2, float* __restrict__ C, int ldc) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), j = threadIdx.x & 63;          // 16 workgroups x 4 rows x 64 columns
@@ -1596,177 +1574,151 @@ extern "C" int mlsp_profile_split_kinds(double* out) {
     return MLSP_OK;
 }
 
-// Can this contraction stage `which` (1: A [M][K] row-major, 2: B [K][N] k-major) through the operand transform?  Interior tiles,
-// 16-byte loads, fp32 operands, the MFMA tile kernels (not the thin / skinny / N = 64 ones).
-// (mode 2: gemm_split_kernel<.., XF, XD> where the split kernel pays, the fp32 transform kernels on the short-K launches: exact fp32
-// products either way.  On the split kernel the A-side transform keeps the scale / shift of a workgroup's K range in LDS: <= SX_XF_KMAX.)
-bool gemm_xf_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, int which) {
-    if (cx.mode() == 1) return false;
-    if (thin_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, which)) return true;       // the streaming kernels of thin.hip transform too
-    if (which == 1 ? ta : !(ta && !tb)) return false;
-    if (M <= 32 || N < 32 || K < 32 || (ta && !tb && K <= 32)) return false;
-    const bool vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0) && (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
-    int ns = gemm_pick_split(M, N, K);
-    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
-    const int ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
-    if (which == 1 && cx.mode() == 2 && gemm_split_pays(M, N, kts) && kts * BK > SX_XF_KMAX) return false;
-    return vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && (long)(ta ? M : K) * lda * 4 < (1L << 30) && (long)K * ldb * 4 < (1L << 30);
+// ---- the picker: every instantiation of the tile kernels is named here, once (taking its address is what instantiates it) ----------
+// All of them are void(GemmArgs) on 256 threads without dynamic LDS.  null: no such instantiation (the plan refuses those combinations).
+typedef void (*GemmKernel)(GemmArgs);
+struct GemmPick {
+    bool ta, tb; int bm; GemmFamily family;
+    int xf; bool xd, dy, pieces;        // transform side and its dropout, (d', y) pair A operand, two f16 pieces (split family)
+    int gm;                             // groups mode (a template argument of the fp32 kernel only)
+    int code; bool nedge;               // bf16 family: storage of A | B | C (4 | 2 | 1 = bf16), ragged N
+};
+template <bool TA, bool TB, int WM, int XF, bool XD, bool DY>
+static GemmKernel pick_split(bool pieces) { return pieces ? gemm_split_kernel<TA, TB, WM, XF, XD, DY, 2> : gemm_split_kernel<TA, TB, WM, XF, XD, DY, 3>; }
+template <bool TA, bool TB, int WM, int XF, bool DY>
+static GemmKernel pick_split_xd(bool xd, bool pieces) { return xd ? pick_split<TA, TB, WM, XF, true, DY>(pieces) : pick_split<TA, TB, WM, XF, false, DY>(pieces); }
+// activation x fp32 weight (or a ragged-N launch): A and C in {f32, bf16}
+template <bool TA, bool TB, int WM, bool NE>
+static GemmKernel pick_bf16_act_w(int code) {
+    return code == 0 ? gemm_bf16_kernel<TA, TB, WM, false, false, false, NE> : code == 1 ? gemm_bf16_kernel<TA, TB, WM, false, false, true, NE>
+         : code == 4 ? gemm_bf16_kernel<TA, TB, WM, true, false, false, NE> : code == 5 ? gemm_bf16_kernel<TA, TB, WM, true, false, true, NE> : nullptr;
+}
+// weight gradient: A = dY and B = X in {f32, bf16}, C fp32
+template <int WM>
+static GemmKernel pick_bf16_act_act(int code) {
+    return code == 0 ? gemm_bf16_kernel<true, false, WM, false, false, false> : code == 4 ? gemm_bf16_kernel<true, false, WM, true, false, false>
+         : code == 2 ? gemm_bf16_kernel<true, false, WM, false, true, false> : code == 6 ? gemm_bf16_kernel<true, false, WM, true, true, false> : nullptr;
+}
+#define PICK_TATB(F, ...) (!ta ? (tb ? F<false, true, __VA_ARGS__> : F<false, false, __VA_ARGS__>) : (tb ? F<true, true, __VA_ARGS__> : F<true, false, __VA_ARGS__>))
+template <int WM>
+static GemmKernel gemm_pick_wm(const GemmPick& k) {
+    const bool ta = k.ta, tb = k.tb;
+    switch (k.family) {
+    case GEMM_FAM_SPLIT:
+        if (k.dy) {                     // dgrad, or the weight gradient with or without the transform of X
+            if (tb || (!ta && k.xf) || (k.xf && k.xf != 2)) return nullptr;
+            if (!ta) return pick_split<false, false, WM, 0, false, true>(k.pieces);
+            return k.xf ? pick_split_xd<true, false, WM, 2, true>(k.xd, k.pieces) : pick_split<true, false, WM, 0, false, true>(k.pieces);
+        }
+        if (k.xf == 1) return (!ta && tb) ? pick_split_xd<false, true, WM, 1, false>(k.xd, k.pieces) : nullptr;
+        if (k.xf == 2) return (ta && !tb) ? pick_split_xd<true, false, WM, 2, false>(k.xd, k.pieces) : nullptr;
+        return PICK_TATB(pick_split, WM, 0, false, false)(k.pieces);
+    case GEMM_FAM_F32:
+        if (k.gm == 1) return ta ? nullptr : tb ? gemm_f32_kernel<false, true, WM, true, 0, 1> : gemm_f32_kernel<false, false, WM, true, 0, 1>;
+        if (k.gm == 2) return (ta && !tb) ? gemm_f32_kernel<true, false, WM, true, 0, 2> : nullptr;
+        if (k.xf == 1) return tb ? gemm_f32_kernel<false, true, WM, true, 1> : gemm_f32_kernel<false, false, WM, true, 1>;
+        if (k.xf == 2) return gemm_f32_kernel<true, false, WM, true, 2>;
+        return PICK_TATB(gemm_f32_kernel, WM, true);
+    case GEMM_FAM_F32_EDGE:
+        return PICK_TATB(gemm_f32_kernel, WM, false);
+    case GEMM_FAM_BF16:
+        if (k.nedge) return tb ? nullptr : ta ? pick_bf16_act_w<true, false, WM, true>(k.code) : pick_bf16_act_w<false, false, WM, true>(k.code);
+        if (!ta) return tb ? pick_bf16_act_w<false, true, WM, false>(k.code) : pick_bf16_act_w<false, false, WM, false>(k.code);
+        if (!tb) return pick_bf16_act_act<WM>(k.code);
+        return k.code == 0 ? gemm_bf16_kernel<true, true, WM, false, false, false> : nullptr;
+    default:
+        return nullptr;
+    }
+}
+#undef PICK_TATB
+static GemmKernel gemm_pick_kernel(const GemmPick& k) {
+    if (k.family == GEMM_FAM_N64)
+        return (k.ta && k.tb) ? nullptr : k.ta ? gemm_f32_n64_kernel<true, false> : k.tb ? gemm_f32_n64_kernel<false, true> : gemm_f32_n64_kernel<false, false>;
+    return k.bm == 128 ? gemm_pick_wm<2>(k) : gemm_pick_wm<1>(k);
 }
 
-// Row panels (of 128 rows) a dgrad dX [M][N] = dY [M][K] W with the fused statistics pass (GemmBs) writes partial sums for; 0: this
-// shape does not take the fused pass (the caller runs the streaming reduction instead).  Split kernel, 128-row interior tiles, one K pass.
-int gemm_bs_parts(const CallCtx& cx, int M, int N, int K, int lda, int ldb, int ldc) {
-    if (cx.mode() != 2 || M % 128 || N % BN || K % BK || lda % 4 || ldb % 4 || ldc % 4) return 0;
-    if (gemm_pick_split(M, N, K) != 1 || gemm_pick_bm(cx, M, N, K) != 128 || !gemm_split_pays(M, N, K / BK)) return 0;
-    return M / 128;
-}
-
-// Can the layer's dgrad (ta = tb = false: dX [M][N] = dY [M][K] W) / weight gradient (ta, !tb: dW [M][N] = dY^T [K][M] X [K][N]) form dY from
-// (d', y) in its A operand loads (GemmDy)?  gemm_split_kernel only: interior tiles, 16-byte loads, the dgrad's K range within SX_XF_KMAX.
-bool gemm_dy_supported(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
-    if (cx.mode() != 2 || tb) return false;
-    if (M <= 32 || N < 32 || K <= 32) return false;
-    const bool vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0) && (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
-    const int ns = gemm_pick_split(M, N, K);
-    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
-    const int ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
-    if (!gemm_split_pays(M, N, kts) || (!ta && kts * BK > SX_XF_KMAX)) return false;
-    return vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && (long)(ta ? K : M) * lda * 4 < (1L << 30) && (long)K * ldb * 4 < (1L << 30);
-}
-
-// will a transform launch of this shape run on gemm_split_kernel (the only kernel that transforms inside a block-diagonal launch)?
-bool gemm_xf_on_split(const CallCtx& cx, bool ta, bool tb, int M, int N, int K, int which) {
-    if (cx.mode() != 2) return false;
-    const int ns = gemm_pick_split(M, N, K), ktiles = (K + BK - 1) / BK, kts = (ktiles + ns - 1) / ns;
-    return gemm_split_pays(M, N, kts) && (which != 1 || kts * BK <= SX_XF_KMAX);
-}
-
+// validate the pointers, build the plan, fill GemmArgs from the options and the plan, gather the f16x3 bounds where the plan says the
+// launch is eligible, pick the kernel, launch, reduce the slabs.
+// o.grp (nullable): block-diagonal product in one launch (GemmArgs groups; M / N are the LAUNCH's dimensions, K one group's):
+// MLSP_ERR_UNSUPPORTED where no kernel takes it (nothing launched; the caller launches group by group).
+// o.stat_ld (0: N): C is a column slice of a [M][stat_ld] matrix whose BatchNorm statistics are taken as ONE vector (multi.hip):
+// stat_part points at this slice's first column of the [panels][2][stat_ld] partial rows
 int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const float* A, int lda, const float* B,
                 int ldb, float* C, int ldc, const GemmOpts& o) {
-    const float* const bias = o.bias; const float* const gbias = o.gbias; const int rows_per_group = o.rows_per_group;
-    float* const slab = o.slab; const size_t slab_floats = o.slab_floats; double* const stat_part = o.stat_part; const int stat_ld = o.stat_ld;
-    const float* const sel_gamma = o.sel_gamma; float* const sel_val = o.sel_val; int* const sel_row = o.sel_row; const bool accumulate = o.accumulate;
     const GemmXf* const xf = o.xf; const GemmGroups* const grp = o.grp; const GemmBs* const bs = o.bs; const GemmDy* const dy = o.dy;
     if (o.unfolded) *o.unfolded = false;
-    // grp (nullable): block-diagonal product in one launch (GemmArgs groups; M / N are the LAUNCH's dimensions, K one group's).
-    // Only on the interior-tile fp32 kernel: MLSP_ERR_UNSUPPORTED otherwise (nothing launched; the caller launches group by group).
-    // stat_ld (0: N): C is a column slice of a [M][stat_ld] matrix whose BatchNorm statistics are taken as ONE vector (multi.hip):
-    // stat_part points at this slice's first column of the [panels][2][stat_ld] partial rows
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || (!C && !sel_gamma)) return MLSP_ERR_ARG;
-    // one tiny dimension (3 coordinates, 3 / 16 outputs): streaming VALU kernels priced against HBM, not MFMA tiles (thin.hip)
-    if (grp && (grp->G < 2 || grp->G > 4 || sel_gamma || gbias || cx.mode() == 1 || (ta && tb))) return MLSP_ERR_UNSUPPORTED;
-    // a transform in a block-diagonal launch: split kernel only; the dropout stream is indexed in 32 bits per aligned quad
-    if (xf && ((xf->ld & 3) || (xf->col & 3) || (((uintptr_t)xf->scale | (uintptr_t)xf->shift) & 15) || (double)(xf->which == 1 ? M : K) * xf->ld >= 17179869184.0))
-        return MLSP_ERR_UNSUPPORTED;
-    if (dy && (!dy->y || !dy->coef || (dy->cld & 3) || (((uintptr_t)dy->y | (uintptr_t)dy->coef) & 15) || gbias || sel_gamma || stat_part ||
-               (xf && xf->which != 2) || !gemm_dy_supported(cx, ta, tb, M, N, K, A, lda, B, ldb)))
-        return MLSP_ERR_UNSUPPORTED;                                         // nothing launched: the caller runs the streaming apply pass
-    if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && (!xf || cx.mode() != 1)) {
+    if (!A || !B || (!C && !o.sel_gamma)) return MLSP_ERR_ARG;
+    GemmAsk q = gemm_ask(cx, ta, tb, M, N, K, A, lda, B, ldb, ldc);
+    q.bias = o.bias; q.bias_a4 = ((uintptr_t)o.bias & 3) == 0; q.gbias = o.gbias; q.rows_per_group = o.rows_per_group;
+    q.stat = o.stat_part; q.sel = o.sel_gamma; q.sel_ok = o.sel_val && o.sel_row; q.accumulate = o.accumulate;
+    q.slab_floats = o.slab ? o.slab_floats : 0;
+    if (xf) {       // the dropout stream is indexed in 32 bits per aligned quad
+        q.xf = xf->which; q.xf_drop = xf->thresh != 0;
+        q.xf_ok = (xf->which == 1 || xf->which == 2) && !(xf->ld & 3) && !(xf->col & 3) && !(((uintptr_t)xf->scale | (uintptr_t)xf->shift) & 15) &&
+                  (double)(xf->which == 1 ? M : K) * xf->ld < 17179869184.0;
+        q.thin_xf = thin_xf_supported(ta, tb, M, N, K, A, lda, B, ldb, xf->which);
+    }
+    if (grp) {
+        q.grp = true; q.G = grp->G; q.gmode = grp->mode;
+        for (int g = 0; g < grp->G && g < 4 && grp->mode == 1; ++g) q.grp_ok = q.grp_ok && grp->Bg[g] && (((uintptr_t)grp->Bg[g] & 15) == 0);
+    }
+    if (bs) { q.bs = true; q.bs_ok = bs->y && bs->bn && bs->part && !(bs->ld & 3) && !(bs->col & 3) && (double)M * bs->ld < 17179869184.0; }
+    if (dy) { q.dy = true; q.dy_ok = dy->y && dy->coef && !(dy->cld & 3) && !(((uintptr_t)dy->y | (uintptr_t)dy->coef) & 15); }
+    const GemmPlan pl = gemm_plan(q);
+    if (pl.offer_thin) {
         const int rc = launch_thin_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, o);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
-    if (xf && !gemm_xf_supported(cx, ta, tb, M, N, K, A, lda, B, ldb, xf->which)) return MLSP_ERR_UNSUPPORTED;   // nothing launched: caller materialises
-    if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && !xf && !bs && !bias && C && gemm_fold64(ta, tb, M, N, K, lda, ldb) &&
-        (((uintptr_t)A | (uintptr_t)B) & 15) == 0) {
+    if (pl.family == GEMM_FAM_FOLD64) {
         const size_t inner = gemm_slab_floats(128, 128, K / 2);
-        if (slab && slab_floats >= inner + 128 * 128) {
-            float* C2 = slab + inner;
-            const size_t used0 = g_prof.used;
-            GemmOpts oi; oi.slab = slab; oi.slab_floats = inner;      // (C2 is not the caller's C: no unfold_dw)
-            const int rc = launch_gemm(st, cx, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, oi);
-            if (rc != MLSP_OK) return rc;
-            if (g_prof.used == used0 + 1) {              // the profiler prices the ALGORITHMIC contraction (64 x 64 x K), not the folded one
-                auto& r = g_prof.rec[used0];
-                g_prof.flop -= 2.0 * 128 * 128.0 * (K / 2) - 2.0 * 64 * 64.0 * K;
-                r.M = 64; r.N = 64; r.K = K;
-            }
-            hipLaunchKernelGGL(gemm_fold64_sum_kernel, dim3(16), dim3(256), 0, st, C2, C, ldc);
-            return mlsp_launch_status();
+        float* C2 = o.slab + inner;
+        const size_t used0 = g_prof.used;
+        GemmOpts oi; oi.slab = o.slab; oi.slab_floats = inner;      // (C2 is not the caller's C: no unfold_dw)
+        const int rc = launch_gemm(st, cx, true, false, 128, 128, K / 2, A, 128, B, 128, C2, 128, oi);
+        if (rc != MLSP_OK) return rc;
+        if (g_prof.used == used0 + 1) {              // the profiler prices the ALGORITHMIC contraction (64 x 64 x K), not the folded one
+            auto& r = g_prof.rec[used0];
+            g_prof.flop -= 2.0 * 128 * 128.0 * (K / 2) - 2.0 * 64 * 64.0 * K;
+            r.M = 64; r.N = 64; r.K = K;
         }
+        hipLaunchKernelGGL(gemm_fold64_sum_kernel, dim3(16), dim3(256), 0, st, C2, C, ldc);
+        return mlsp_launch_status();
     }
-    // per-cloud layers (<= 32 rows, or a 32-deep wgrad): one-pass skinny kernels, no split-K slab (skinny.hip)
-    if (!dy && !grp && !gbias && !stat_part && !sel_gamma && !accumulate && !xf && !bs && ((!ta && M <= 32) || (ta && !tb && K <= 32))) {
-        const int rc = launch_skinny_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias);
+    if (pl.offer_skinny) {
+        const int rc = launch_skinny_gemm(st, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, o.bias);
         if (rc != MLSP_ERR_UNSUPPORTED) return rc;
     }
-    if (sel_gamma && (!sel_val || !sel_row || gemm_pick_split(M, N, K) != 1)) return MLSP_ERR_ARG;
-    if (gbias && rows_per_group <= 0) return MLSP_ERR_ARG;
-    GemmArgs p;
-    p.A = A; p.B = B; p.C = C; p.bias = bias; p.gbias = gbias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.rows_per_group = rows_per_group;
-    int ns = gemm_pick_split(M, N, K);
-    if (ns > 1 && (!slab || slab_floats < (size_t)ns * M * N)) ns = 1;   // no slab: fall back to one pass
-    if (accumulate) ns = 1;                                              // beta = 1 lives in the one-pass epilogue
-    p.accumulate = accumulate ? 1 : 0;
-    p.fast_out = 0;
-    if (stat_part && gemm_pick_split(M, N, K) != 1) return MLSP_ERR_ARG;  // caller must check gemm_stat_parts()
-    p.stat_part = stat_part; p.stat_ld = stat_ld > 0 ? stat_ld : N;
-    p.sel_gamma = sel_gamma; p.sel_val = sel_val; p.sel_row = sel_row;
-    p.bs_amax = nullptr; p.dy_amax = 0;
-    p.bs_y = nullptr; p.bs_ldy = 0; p.bs_bn = nullptr; p.bs_bnld = 0; p.bs_slope = 1.f; p.bs_thresh = 0; p.bs_ik = 1.f; p.bs_xH = 0; p.bs_ld4 = 0; p.bs_col = 0;
+    if (pl.status != MLSP_OK) return pl.status;          // nothing launched: the caller takes its other path (materialise, streaming pass, group by group)
+    GemmArgs p = {};
+    p.A = A; p.B = B; p.C = pl.ns > 1 ? o.slab : C; p.bias = o.bias; p.gbias = o.gbias;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = pl.ldc; p.rows_per_group = o.rows_per_group;
+    p.ntm = pl.ntm; p.ntn = pl.ntn; p.nsplit = pl.ns; p.ksplit = pl.kts * BK;
+    p.a_vec = pl.a_vec; p.b_vec = pl.b_vec; p.xcd_map = pl.xcd_map; p.accumulate = o.accumulate ? 1 : 0; p.fast_out = pl.fast_out ? 1 : 0;
+    p.stat_part = o.stat_part; p.stat_ld = o.stat_ld > 0 ? o.stat_ld : N;
+    p.sel_gamma = o.sel_gamma; p.sel_val = o.sel_val; p.sel_row = o.sel_row;
+    p.bs_slope = 1.f; p.bs_ik = 1.f; p.x_inv_keep = 1.f;
     if (bs) {
-        if (ta || tb || xf || bias || gbias || accumulate || stat_part || sel_gamma || !bs->y || !bs->bn || !bs->part || (bs->ld & 3) || (bs->col & 3) ||
-            gemm_bs_parts(cx, M, N, K, lda, ldb, ldc) == 0 || (double)M * bs->ld >= 17179869184.0)
-            return MLSP_ERR_UNSUPPORTED;
         p.bs_y = bs->y; p.bs_ldy = bs->ldy; p.bs_bn = bs->bn; p.bs_bnld = bs->bnld;
         p.bs_slope = bs->act == 0 ? 1.f : bs->act == 1 ? 0.f : bs->slope; p.bs_thresh = bs->thresh; p.bs_ik = bs->inv_keep;
         p.bs_xH = mix32_host((uint32_t)bs->seed) ^ (uint32_t)(bs->seed >> 32) * 0x9e3779b9U; p.bs_ld4 = bs->ld / 4; p.bs_col = bs->col;
         p.stat_part = bs->part; p.stat_ld = bs->stat_ld; p.bs_amax = bs->amax;
     }
-    p.dy_y = dy ? dy->y : nullptr; p.dy_coef = dy ? dy->coef : nullptr; p.dy_cld = dy ? dy->cld : 0; p.dy_amax = (dy && dy->amax) ? 1 : 0;
-    p.a_amax = nullptr; p.a_amax_n = 0; p.b_amax[0] = p.b_amax[1] = p.b_amax[2] = p.b_amax[3] = nullptr; p.b_amax_n[0] = p.b_amax_n[1] = p.b_amax_n[2] = p.b_amax_n[3] = 0; p.x_mean = p.x_invstd = nullptr; p.stat_sqrt_rows = 0.f;
-    p.x_scale = p.x_shift = nullptr; p.x_act = 0; p.x_slope = 0.f; p.x_thresh = 0; p.x_inv_keep = 1.f; p.x_seed = 0; p.x_ld = 0; p.x_col = 0;
+    if (dy) { p.dy_y = dy->y; p.dy_coef = dy->coef; p.dy_cld = dy->cld; p.dy_amax = dy->amax ? 1 : 0; }
     if (xf) {
         p.x_scale = xf->scale; p.x_shift = xf->shift; p.x_act = xf->act; p.x_thresh = xf->thresh;
         p.x_slope = xf->act == 0 ? 1.f : xf->act == 1 ? 0.f : xf->slope;          // effective negative-side factor (xf_quad)
         p.x_inv_keep = xf->inv_keep; p.x_seed = xf->seed; p.x_ld = xf->ld; p.x_col = xf->col;
     }
-    int ktiles = (K + BK - 1) / BK;
-    int kts = (ktiles + ns - 1) / ns;
-    ns = (ktiles + kts - 1) / kts;
-    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
-    p.ntm = (M + bm - 1) / bm; p.ntn = (N + BN - 1) / BN;
-    p.nsplit = ns; p.ksplit = kts * BK;
-    p.a_vec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0);
-    p.b_vec = (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
-    if (ns > 1) { p.C = slab; p.ldc = N; }
-    p.xcd_map = p.ntm >= 16 && p.ntn > 1;
-    dim3 grid(p.xcd_map ? ((p.ntm + 7) / 8) * 8 * p.ntn : p.ntm * p.ntn, ns);
-    const bool prof = g_prof.on && g_prof.used < PROF_MAX_PAIRS;
-    // FAST: every tile interior (M, N, K-range multiples of the tile), 16-byte loads legal on both operands
-    // (byte offsets inside an operand tile's K range are 32-bit buffer offsets)
-    const long a_span = ta ? (long)p.ksplit * lda * 4 : 128L * lda * 4 + (long)p.ksplit * 4;
-    const long b_span = !tb ? (long)p.ksplit * ldb * 4 : 128L * ldb * 4 + (long)p.ksplit * 4;
-    const bool fast = p.a_vec && p.b_vec && (M % bm == 0) && (N % BN == 0) && (K % BK == 0) && a_span < (1L << 31) - 4096 && b_span < (1L << 31) - 4096;
-    // lean output pass: every row of a tile takes the same per-cloud bias row, byte offsets inside a wave's region fit 31 bits
-    p.fast_out = (fast && (!gbias || rows_per_group % bm == 0) && (long)p.ldc * 4 * 64 < (1L << 30)) ? 1 : 0;
-    p.gmode = 0; p.gtiles = 1; p.a_gs = p.b_gs = 0; p.Bg[0] = p.Bg[1] = p.Bg[2] = p.Bg[3] = B;
+    p.gtiles = pl.gtiles; p.Bg[0] = p.Bg[1] = p.Bg[2] = p.Bg[3] = B;
     if (grp) {
-        const int per = (grp->mode == 1 ? N : M) / grp->G;                  // columns (mode 1) / rows (mode 2) of one group
-        const int tile = grp->mode == 1 ? BN : bm;
-        bool ok = fast && cx.mode() != 1 && (grp->mode == 1 || grp->mode == 2) && per * grp->G == (grp->mode == 1 ? N : M) && per % tile == 0;
-        for (int g = 0; g < grp->G && ok && grp->mode == 1; ++g) ok = grp->Bg[g] && (((uintptr_t)grp->Bg[g] & 15) == 0);
-        if (!ok) return MLSP_ERR_UNSUPPORTED;
-        p.gmode = grp->mode; p.gtiles = per / tile; p.a_gs = grp->a_gs; p.b_gs = grp->b_gs;
+        p.gmode = grp->mode; p.a_gs = grp->a_gs; p.b_gs = grp->b_gs;
         for (int g = 0; g < 4; ++g) p.Bg[g] = grp->mode == 1 ? grp->Bg[g < grp->G ? g : 0] : B;
     }
-    const bool xf_split = xf && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && (xf->which != 1 || kts * BK <= SX_XF_KMAX);
-    if (grp && xf && !xf_split) return MLSP_ERR_UNSUPPORTED;             // (the fp32 transform kernels take no groups: nothing launched)
-    // split-K launches of gemm_split_kernel with few row panels (weight gradients): XCD-grouped (split, panel) order, see the kernel
-    const bool xcd2 = !p.xcd_map && ns > 1 && p.ntn > 1 && (p.ntm * ns) % 8 == 0 && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) &&
-           (!xf || xf_split);
-    const bool xcd3 = !p.xcd_map && ns > 1 && ns % 8 == 0 && p.ntm > 1 && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && (!xf || xf_split);
-    if (xcd3) { p.xcd_map = 3; grid = dim3(p.ntm * p.ntn * ns, 1); }       // (all tiles of a split on one XCD: see the kernel)
-    else if (xcd2) { p.xcd_map = 2; grid = dim3(p.ntm * p.ntn * ns, 1); }
-    // (mode 1, N = 64: the bf16 kernel's tiles are 128 columns wide, so these launches used to fall to the bounds-checked f32 kernel at half-empty
-    // tiles -- 33 us where the 64-column f32 kernel takes 12; exact products are within what mode 1 promises.)
-    const bool n64 = !dy && !grp && !xf && N == 64 && p.a_vec && p.b_vec && M % 128 == 0 && K % BK == 0 && !(ta && tb) && !gbias && (!stat_part || (bm == 128 && ns == 1)) && !sel_gamma &&
-                     (!bias || (ns == 1 && (((uintptr_t)bias) & 3) == 0)) && (ns == 1 || p.ldc == N);
     // two-piece f16 products (mode 3) on this launch?  The split kernel, and a bound for both operands: partial maxima of the operands as
     // they lie in memory (measured by ONE streaming launch here, or earlier in this API call), the analytic bound for a transformed one
     // (batch statistics at hand).  Anything missing: the three-piece bf16 products (same kernel family, same accuracy class).
     bool half = false;
-    if (cx.split_half() && cx.has_tail() && fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split)) {
+    if (pl.pieces && cx.has_tail()) {
         AmaxBatch batch;
         bool ok = true;
         // Does MEASURING what is not at hand pay?  The three-product kernel saves about a third of the six-product launch (~150 TF on
@@ -1806,90 +1758,22 @@ int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int
         p.stat_sqrt_rows = sqrtf((float)(ta ? K : M));
         half = ok;
     }
+    const GemmKernel kern = gemm_pick_kernel({ta, tb, pl.bm, pl.family, q.xf, q.xf_drop, q.dy, half, grp ? grp->mode : 0, 0, false});
+    if (!kern) return MLSP_ERR_UNSUPPORTED;
+    const bool prof = g_prof.on && g_prof.used < PROF_MAX_PAIRS;
     if (prof) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], st);
-    if (n64) {
-        dim3 g64(M / 128, ns);
-        if (!ta && tb) hipLaunchKernelGGL((gemm_f32_n64_kernel<false, true>), g64, dim3(256), 0, st, p);
-        else if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_n64_kernel<false, false>), g64, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_f32_n64_kernel<true, false>), g64, dim3(256), 0, st, p);
-    } else
-#define GEMM_GO(TA_, TB_, WM_) do { if (fast && cx.mode() == 1) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, TB_, WM_, false, false, false>), grid, dim3(256), 0, st, p); \
-                                     else if (half) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, WM_, 0, false, false, 2>), grid, dim3(256), 0, st, p); \
-                                     else if (fast && cx.mode() == 2 && gemm_split_pays(M, N, kts)) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, WM_>), grid, dim3(256), 0, st, p); \
-                                     else if (fast) hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_, WM_, true>), grid, dim3(256), 0, st, p); \
-                                     else hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_, WM_, false>), grid, dim3(256), 0, st, p); } while (0)
-    if (dy) {                                                            // dual A operand (validated above: split kernel, interior tiles)
-        if (!fast || (xf && !xf_split) || (grp && grp->mode != (ta ? 2 : 1))) return MLSP_ERR_UNSUPPORTED;
-#define SPLIT_DY_GO(TA_, XF_, XD_) do { if (half) { if (bm == 128) hipLaunchKernelGGL((gemm_split_kernel<TA_, false, 2, XF_, XD_, true, 2>), grid, dim3(256), 0, st, p); \
-                                                    else hipLaunchKernelGGL((gemm_split_kernel<TA_, false, 1, XF_, XD_, true, 2>), grid, dim3(256), 0, st, p); } \
-                                        else if (bm == 128) hipLaunchKernelGGL((gemm_split_kernel<TA_, false, 2, XF_, XD_, true>), grid, dim3(256), 0, st, p); \
-                                        else hipLaunchKernelGGL((gemm_split_kernel<TA_, false, 1, XF_, XD_, true>), grid, dim3(256), 0, st, p); } while (0)
-        if (!ta) { if (xf) return MLSP_ERR_UNSUPPORTED; SPLIT_DY_GO(false, 0, false); }
-        else if (!xf) SPLIT_DY_GO(true, 0, false);
-        else if (xf->thresh) SPLIT_DY_GO(true, 2, true);
-        else SPLIT_DY_GO(true, 2, false);
-#undef SPLIT_DY_GO
-    } else if (xf_split) {                                               // operand transform on the split kernel, plain or block-diagonal
-#define SPLIT_XF_GO(TA_, TB_, XF_) do { if (half) { if (bm == 128) { if (xf->thresh) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 2, XF_, true, false, 2>), grid, dim3(256), 0, st, p); \
-                                                                      else hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 2, XF_, false, false, 2>), grid, dim3(256), 0, st, p); } \
-                                                     else { if (xf->thresh) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 1, XF_, true, false, 2>), grid, dim3(256), 0, st, p); \
-                                                            else hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 1, XF_, false, false, 2>), grid, dim3(256), 0, st, p); } } \
-                                         else if (bm == 128) { if (xf->thresh) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 2, XF_, true>), grid, dim3(256), 0, st, p); \
-                                                          else hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 2, XF_, false>), grid, dim3(256), 0, st, p); } \
-                                         else { if (xf->thresh) hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 1, XF_, true>), grid, dim3(256), 0, st, p); \
-                                                else hipLaunchKernelGGL((gemm_split_kernel<TA_, TB_, 1, XF_, false>), grid, dim3(256), 0, st, p); } } while (0)
-        if (xf->which == 1 && !ta && tb && (!grp || grp->mode == 1)) SPLIT_XF_GO(false, true, 1);
-        else if (xf->which == 2 && ta && !tb && (!grp || grp->mode == 2)) SPLIT_XF_GO(true, false, 2);
-        else return MLSP_ERR_UNSUPPORTED;
-#undef SPLIT_XF_GO
-    } else if (grp && cx.mode() == 2 && gemm_split_pays(M, N, kts)) {   // block-diagonal launch on the split kernel (groups are a run-time argument there)
-        if (grp->mode == 1 && !ta && tb) { if (bm == 128) GEMM_GO(false, true, 2); else GEMM_GO(false, true, 1); }
-        else if (grp->mode == 1 && !ta && !tb) { if (bm == 128) GEMM_GO(false, false, 2); else GEMM_GO(false, false, 1); }
-        else if (grp->mode == 2 && ta && !tb) { if (bm == 128) GEMM_GO(true, false, 2); else GEMM_GO(true, false, 1); }
-        else return MLSP_ERR_UNSUPPORTED;
-    } else if (grp) {                                     // block-diagonal launch (validated above: fast, fp32)
-        if (grp->mode == 1 && !ta && tb) { if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<false, true, 2, true, 0, 1>), grid, dim3(256), 0, st, p);
-                                           else hipLaunchKernelGGL((gemm_f32_kernel<false, true, 1, true, 0, 1>), grid, dim3(256), 0, st, p); }
-        else if (grp->mode == 1 && !ta && !tb) { if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 2, true, 0, 1>), grid, dim3(256), 0, st, p);
-                                                 else hipLaunchKernelGGL((gemm_f32_kernel<false, false, 1, true, 0, 1>), grid, dim3(256), 0, st, p); }
-        else if (grp->mode == 2 && ta && !tb) { if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<true, false, 2, true, 0, 2>), grid, dim3(256), 0, st, p);
-                                                else hipLaunchKernelGGL((gemm_f32_kernel<true, false, 1, true, 0, 2>), grid, dim3(256), 0, st, p); }
-        else return MLSP_ERR_UNSUPPORTED;
-    } else if (xf) {                                      // operand transform: FAST fp32 instantiations only (gemm_xf_supported)
-        if (xf->which == 1 && tb) {
-            if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<false, true, 2, true, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_f32_kernel<false, true, 1, true, 1>), grid, dim3(256), 0, st, p);
-        } else if (xf->which == 1) {
-            if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 2, true, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_f32_kernel<false, false, 1, true, 1>), grid, dim3(256), 0, st, p);
-        } else {
-            if (bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<true, false, 2, true, 2>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_f32_kernel<true, false, 1, true, 2>), grid, dim3(256), 0, st, p);
-        }
-    } else if (bm == 128) {
-        if (!ta && tb) GEMM_GO(false, true, 2);
-        else if (!ta && !tb) GEMM_GO(false, false, 2);
-        else if (ta && !tb) GEMM_GO(true, false, 2);
-        else GEMM_GO(true, true, 2);
-    } else {
-        if (!ta && tb) GEMM_GO(false, true, 1);
-        else if (!ta && !tb) GEMM_GO(false, false, 1);
-        else if (ta && !tb) GEMM_GO(true, false, 1);
-        else GEMM_GO(true, true, 1);
-    }
-#undef GEMM_GO
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x, pl.grid_y), dim3(256), 0, st, p);
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
-        const bool on_split = fast && cx.mode() == 2 && gemm_split_pays(M, N, kts) && !n64 && (!xf || xf_split);
-        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (stat_part ? 1 : 0) + (sel_gamma ? 2 : 0), on_split ? (half ? 2 : 1) : 0, (dy ? 1 : 0) + (accumulate ? 2 : 0)};
+        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, pl.ns, pl.bm, (o.stat_part ? 1 : 0) + (o.sel_gamma ? 2 : 0),
+                                   pl.family == GEMM_FAM_SPLIT ? (half ? 2 : 1) : 0, (dy ? 1 : 0) + (o.accumulate ? 2 : 0)};
         g_prof.used++;
         g_prof.flop += 2.0 * M * (double)N * K;
         g_prof.bytes += 4.0 * ((double)M * K + (double)K * N + (C ? (double)M * N : 0.0));
     }
-    if (ns > 1 && launch_splitk_reduce_any(st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group, o.unfold_dw) && o.unfolded) *o.unfolded = true;
+    if (pl.ns > 1 && launch_splitk_reduce_any(st, o.slab, C, M, N, ldc, pl.ns, o.bias, o.gbias, o.rows_per_group, o.unfold_dw) && o.unfolded) *o.unfolded = true;
     return mlsp_launch_status();
 }
-
 
 // ---- bf16 activation storage (BASELINE.json configs[4]) ---------------------------------------------------------------------
 // The same contraction with operands and/or the output held as bf16 in HBM: activations X / Y / Z and their gradients are bf16,
@@ -1905,61 +1789,29 @@ int launch_gemm_mx(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, 
     if (o.unfolded) *o.unfolded = false;
     if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return MLSP_ERR_ARG;
     if (o.gbias && o.rows_per_group <= 0) return MLSP_ERR_ARG;
-    GemmArgs p;
-    p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.bias = o.bias; p.gbias = o.gbias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.rows_per_group = o.rows_per_group;
-    int ns = gemm_pick_split(M, N, K);
-    if (ns > 1 && (!o.slab || o.slab_floats < (size_t)ns * M * N)) ns = 1;
-    if (o.accumulate) ns = 1;
+    GemmPlan pl;                                                         // (the tiling of the plan; the kernel is the bf16 one whatever the mode)
+    gemm_plan_tiles(pl, cx.mode(), M, N, K, o.slab ? o.slab_floats : 0, o.accumulate);
+    const int ns = pl.ns, bm = pl.bm;
     if (ns > 1 && c_bf16) return MLSP_ERR_UNSUPPORTED;                   // a split result is reduced in fp32
     if (o.stat_part && ns != 1) return MLSP_ERR_ARG;
-    p.accumulate = o.accumulate ? 1 : 0; p.c_bf16 = c_bf16; p.fast_out = 0;
-    p.stat_part = o.stat_part; p.stat_ld = N; p.sel_gamma = nullptr; p.sel_val = nullptr; p.sel_row = nullptr;
-    const int ktiles = (K + BK - 1) / BK;
-    const int kts = (ktiles + ns - 1) / ns;
-    ns = (ktiles + kts - 1) / kts;
-    const int bm = (ns == 1) ? gemm_pick_bm(cx, M, N, K) : 128;
-    p.ntm = (M + bm - 1) / bm; p.ntn = (N + BN - 1) / BN;
-    p.nsplit = ns; p.ksplit = kts * BK;
+    GemmArgs p = {};
+    p.A = (const float*)A; p.B = (const float*)B; p.C = ns > 1 ? o.slab : (float*)C; p.bias = o.bias; p.gbias = o.gbias;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ns > 1 ? N : ldc; p.rows_per_group = o.rows_per_group;
+    p.accumulate = o.accumulate ? 1 : 0; p.c_bf16 = c_bf16;
+    p.stat_part = o.stat_part; p.stat_ld = N;
+    p.ntm = pl.ntm; p.ntn = pl.ntn; p.nsplit = ns; p.ksplit = pl.kts * BK; p.xcd_map = pl.xcd_map;
     const bool a_ok = a_bf16 ? (lda % 8 == 0) : (lda % 4 == 0), b_ok = b_bf16 ? (ldb % 8 == 0) : (ldb % 4 == 0);
     p.a_vec = a_ok && (((uintptr_t)A & 15) == 0);
     p.b_vec = b_ok && (((uintptr_t)B & 15) == 0);
-    const bool nedge = (N % BN != 0);
-    if (nedge && !(!tb && !b_bf16 && N % 4 == 0 && !o.stat_part && !(c_bf16 && ns > 1))) return MLSP_ERR_UNSUPPORTED;   // k-major fp32 B only
+    const bool nedge = (N % BN != 0);     // ragged channel count on the N side (192-channel head input): dgrad dX = dY * W and wgrad dW = dY^T * X, k-major fp32 B only
+    if (nedge && !(!tb && !b_bf16 && N % 4 == 0 && !o.stat_part && !(c_bf16 && ns > 1))) return MLSP_ERR_UNSUPPORTED;
     if (!(p.a_vec && p.b_vec && M % bm == 0 && K % BK == 0)) return MLSP_ERR_UNSUPPORTED;
-    if (ns > 1) { p.C = o.slab; p.ldc = N; }
-    p.xcd_map = p.ntm >= 16 && p.ntn > 1;
-    dim3 grid(p.xcd_map ? ((p.ntm + 7) / 8) * 8 * p.ntn : p.ntm * p.ntn, ns);
+    const int code = (a_bf16 ? 4 : 0) | (b_bf16 ? 2 : 0) | ((c_bf16 && ns == 1) ? 1 : 0);
+    const GemmKernel kern = (ta && tb) ? nullptr : gemm_pick_kernel({ta, tb, bm, GEMM_FAM_BF16, 0, false, false, false, 0, code, nedge});
+    if (!kern) return MLSP_ERR_UNSUPPORTED;
     const bool prof = g_prof.on && g_prof.used < PROF_MAX_PAIRS;
     if (prof) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], st);
-    const int code = (a_bf16 ? 4 : 0) | (b_bf16 ? 2 : 0) | ((c_bf16 && ns == 1) ? 1 : 0);
-#define MX_GO(TA_, TB_, WM_, A_, B_, C_) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, TB_, WM_, A_, B_, C_>), grid, dim3(256), 0, st, p)
-#define MX_ACT_W(TA_, TB_, WM_) do { /* activation x weight: A in {f32, bf16}, B = fp32 weights, C in {f32, bf16} */ \
-        if (code == 0) MX_GO(TA_, TB_, WM_, false, false, false); else if (code == 1) MX_GO(TA_, TB_, WM_, false, false, true); \
-        else if (code == 4) MX_GO(TA_, TB_, WM_, true, false, false); else if (code == 5) MX_GO(TA_, TB_, WM_, true, false, true); \
-        else return MLSP_ERR_UNSUPPORTED; } while (0)
-#define MX_ACT_ACT(WM_) do { /* wgrad: A = dY, B = X in {f32, bf16}, C = fp32 */ \
-        if (code == 0) MX_GO(true, false, WM_, false, false, false); else if (code == 4) MX_GO(true, false, WM_, true, false, false); \
-        else if (code == 2) MX_GO(true, false, WM_, false, true, false); else if (code == 6) MX_GO(true, false, WM_, true, true, false); \
-        else return MLSP_ERR_UNSUPPORTED; } while (0)
-    if (ta && tb) return MLSP_ERR_UNSUPPORTED;
-    if (nedge) {            // ragged channel count on the N side (192-channel head input): dgrad dX = dY * W and wgrad dW = dY^T * X, B in fp32
-#define MX_NE(TA_, WM_) do { if (code == 0) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, false, WM_, false, false, false, true>), grid, dim3(256), 0, st, p); \
-        else if (code == 1) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, false, WM_, false, false, true, true>), grid, dim3(256), 0, st, p); \
-        else if (code == 4) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, false, WM_, true, false, false, true>), grid, dim3(256), 0, st, p); \
-        else if (code == 5) hipLaunchKernelGGL((gemm_bf16_kernel<TA_, false, WM_, true, false, true, true>), grid, dim3(256), 0, st, p); \
-        else return MLSP_ERR_UNSUPPORTED; } while (0)
-        if (ta) { if (bm == 128) MX_NE(true, 2); else MX_NE(true, 1); }
-        else { if (bm == 128) MX_NE(false, 2); else MX_NE(false, 1); }
-#undef MX_NE
-    } else if (bm == 128) {
-        if (!ta && tb) MX_ACT_W(false, true, 2); else if (!ta && !tb) MX_ACT_W(false, false, 2); else MX_ACT_ACT(2);
-    } else {
-        if (!ta && tb) MX_ACT_W(false, true, 1); else if (!ta && !tb) MX_ACT_W(false, false, 1); else MX_ACT_ACT(1);
-    }
-#undef MX_ACT_ACT
-#undef MX_ACT_W
-#undef MX_GO
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x, pl.grid_y), dim3(256), 0, st, p);
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
         g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (o.stat_part ? 1 : 0) + 4, 0, 0};
