@@ -3,6 +3,7 @@
 // no synchronisation, no global state (hipGraph-capturable).
 #include "common.h"
 #include "../../include/mlsp_hip.h"
+#include "knn_plan.h"      // mlsp_knn_f32 sizes the planes from the plan of its call
 
 #define CHECK(x) do { int _r = (x); if (_r != MLSP_OK) return _r; } while (0)
 #define SLAB_BOUND_FLOATS ((size_t)16 << 20)   /* 64 MiB of fp32: bound on any split-K slab (gemm_pick_split) */
@@ -63,8 +64,10 @@ int mlsp_knn_f32(const float* x, int ldx, int B, int N, int C, int k, int32_t* i
     Workspace w(ws, ws_bytes);
     float* xx = w.take<float>((size_t)B * N);
     if (!w.ok()) return MLSP_ERR_WORKSPACE;
-    const size_t pbytes = (knn6_supported(B, N, C, k) || knn6w_supported(B, N, C, k)) ? knn6_plane_bytes(B * N, C) : 0;      // bf16 hi / lo images of the points (knn6.hip)
-    char* planes = pbytes ? w.take<char>(pbytes) : nullptr;          // (a workspace too small for them keeps the call on the v5 kernels)
+    KnnAsk q;                                                        // this call with every byte of planes on offer: what its family takes
+    q.B = B; q.N = N; q.C = C; q.k = k; q.ld = ldx; q.x16 = ((uintptr_t)x & 15) == 0; q.planes_avail = (size_t)-1;
+    const size_t pbytes = knn_plan(q).plane_bytes;                   // the images of the v6 families (knn6.hip); 0: a family without planes
+    char* planes = pbytes ? w.take<char>(pbytes) : nullptr;          // (a workspace too small for them: launch_knn plans again without)
     {   // bench.py roofline_kernels: C <= 4 priced against HBM (compulsory bytes), C = 64 / 128 against the fp32 matrix peak
         const int cls = C <= 4 ? MLSP_PROF_KNN_C3 : C == 64 ? MLSP_PROF_KNN_C64 : C == 128 ? MLSP_PROF_KNN_C128 : 0;
         const int tok = prof_cls_begin(st, cls);

@@ -171,3 +171,14 @@ static inline XfDev xf_dev(const GemmXf& x) {
 
 // every host function that one translation unit defines and another calls (after the Gemm* structs its prototypes name)
 #include "launchers.h"
+
+// raise the kernel's dynamic-LDS limit where the launch asks for more than the 64 KiB a kernel gets by default, launch, status
+template <class... P, class... A>
+static inline int mlsp_launch_lds(hipStream_t st, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A... a) {
+    if (lds > 64 * 1024) {
+        hipError_t e = mlsp_lds_limit((const void*)kern, lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, a...);
+    return mlsp_launch_status();
+}

@@ -1,4 +1,4 @@
-// Brute-force self-kNN in canonical arithmetic + the reverse (transposed) neighbour index.
+// Brute-force self-kNN in canonical arithmetic: the search kernels (v6's are in knn6.hip) and their one launcher, which follows knn_plan.h.
 // Replaces PointDA/model_utils.py:9-16 `knn` (and its PointSegDA/Models.py:8-15 twin).  The
 // [B,N,N] distance matrix of the reference never exists: distances live in registers only.
 //
@@ -11,12 +11,10 @@
 // top-K list in registers; the 4 partial lists are merged through LDS under the same total order,
 // so the result does not depend on the partition.
 #include "common.h"
+#include "knn_plan.h"      // KNN_QB / KNN_TJ, KM_STRIDE, the CAP constants, and which kernel a search of a given shape runs on
 #include <type_traits>
 #include <math.h>
 #include <cstdlib>
-
-#define KNN_QB 64      // queries per workgroup
-#define KNN_TJ 32      // candidates per LDS tile per wave
 
 // squared norms with the canonical chain
 // `idx` (nullable): the kNN output [P][k], zero-filled here -- a row with fewer than k comparable candidates (NaN coordinates) keeps index 0
@@ -175,8 +173,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ x, c
 // bit-for-bit a k-ordered fmaf chain (c = 2s on lanes 0-31, c = 2s+1 on lanes 32-63), i.e. exactly the canonical dot product.
 // Candidate tiles are staged k-major through LDS [c][33]; channels are zero-padded to CT (fmaf(0,0,acc) == acc, so padding does not
 // perturb the chain).  (The round-1 list-merge kernel that kept k sorted entries per lane -- and spilled for k = 40 -- is gone: its
-// shapes run on the two-pass kernel, the few it does not take on the VALU kernel above.)
-#define KM_STRIDE 33
+// shapes run on the two-pass kernel, the few it does not take on the VALU kernel above.)  KM_STRIDE = 33: knn_plan.h.
 
 template <int CT>
 __global__ __launch_bounds__(256) void knn_mfma3_kernel(const float* __restrict__ x, const float* __restrict__ xx_all,
@@ -330,29 +327,6 @@ __global__ __launch_bounds__(256) void knn_mfma3_kernel(const float* __restrict_
     }
 }
 
-template <int CT>
-static int launch_knn_mfma3_ct(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx) {
-    size_t lds = ((size_t)2 * CT * KM_STRIDE + 96) * sizeof(float);
-    if (lds > 160 * 1024) return MLSP_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = mlsp_lds_limit((const void*)knn_mfma3_kernel<CT>, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    int vec_ok = (ld % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    dim3 grid((N + 127) / 128, B);
-    hipLaunchKernelGGL((knn_mfma3_kernel<CT>), grid, dim3(256), lds, st, x, xx, ld, N, C, k, vec_ok, idx);
-    return mlsp_launch_status();
-}
-
-static int launch_knn_mfma3(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx) {
-    if (C <= 4) return launch_knn_mfma3_ct<4>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 16) return launch_knn_mfma3_ct<16>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 64) return launch_knn_mfma3_ct<64>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 128) return launch_knn_mfma3_ct<128>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 256) return launch_knn_mfma3_ct<256>(st, x, ld, xx, B, N, C, k, idx);
-    return MLSP_ERR_UNSUPPORTED;
-}
-
 // ------------------------------------------------------------------------------------------------
 // v4: two-pass threshold select on top of the v3 tile pipeline (same canonical distances, same total order).
 //   pass A  every lane keeps the running max of ITS column of the distance tiles (one v_max per value): 32 disjoint
@@ -362,8 +336,7 @@ static int launch_knn_mfma3(hipStream_t st, const float* x, int ld, const float*
 //           per-query LDS buffer by ballot + prefix count -- no per-candidate loop.
 //   final   exact rank of every survivor by counting (value desc, index asc): rank < k -> idx[q][rank].
 // If any query of the workgroup overflows its 64-entry buffer (massive ties) the workgroup re-runs the v3
-// sequential insertion (pass C), which is exact for any input.
-#define KNN4_CAP 64
+// sequential insertion (pass C), which is exact for any input.  (KNN4_CAP = 64: knn_plan.h)
 
 template <int CT>
 __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict__ x, const float* __restrict__ xx_all,
@@ -597,28 +570,6 @@ __global__ __launch_bounds__(256) void knn_mfma4_kernel(const float* __restrict_
     }
 }
 
-template <int CT>
-static int launch_knn_mfma4_ct(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx) {
-    size_t lds = ((size_t)2 * CT * KM_STRIDE + 96 + 2 * 4 * 32 * KNN4_CAP) * sizeof(float);
-    if (lds > 160 * 1024) return MLSP_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = mlsp_lds_limit((const void*)knn_mfma4_kernel<CT>, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    int vec_ok = (ld % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    dim3 grid(((N + 127) / 128) * B);
-    hipLaunchKernelGGL((knn_mfma4_kernel<CT>), grid, dim3(256), lds, st, x, xx, ld, N, C, k, vec_ok, idx, B);
-    return mlsp_launch_status();
-}
-
-static int launch_knn_mfma4(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx) {
-    if (C <= 4) return launch_knn_mfma4_ct<4>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 16) return launch_knn_mfma4_ct<16>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 64) return launch_knn_mfma4_ct<64>(st, x, ld, xx, B, N, C, k, idx);
-    if (C <= 128) return launch_knn_mfma4_ct<128>(st, x, ld, xx, B, N, C, k, idx);
-    return MLSP_ERR_UNSUPPORTED;
-}
-
 // ------------------------------------------------------------------------------------------------
 // v5: the v4 two-pass threshold select with the candidates of a query split over TWO waves.
 // A workgroup is 8 waves = 4 query groups (32 queries each) x 2 candidate halves, so every SIMD holds two waves and one
@@ -643,9 +594,8 @@ static int launch_knn_mfma4(hipStream_t st, const float* x, int ld, const float*
 //   pass C  (overflow: massive ties) lane-distributed sorted lists with two entries per lane (positions l and 32 + l);
 //           the halves publish one after the other through the same buffer and rank their own keys against the other's.
 // The query fragments are re-read from global memory after the tau phase instead of staying live across it (registers).
-#define KNN5_CAP 32
-#define KNN5_CAPT 88               // KB = 1: keys per query, both halves together (16-byte aligned rows)
-#define KNN5_XS 68                 // row stride (floats) of the pass-A exchange image: 16 B aligned rows, 2-way banked
+// (KNN5_CAP = 32, KNN5_CAPT = 88: knn_plan.h)
+#define KNN5_XS 68                // row stride (floats) of the pass-A exchange image: 16 B aligned rows, 2-way banked
 typedef unsigned long long u64;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -1262,370 +1212,62 @@ __global__ __launch_bounds__(512) void knn_mfma5_kernel(const float* __restrict_
     }
 }
 
-template <int CT, bool VEC, bool RES, int KB>
-static int launch_knn_mfma5_ct(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx,
-                               size_t lds, const int* only, bool dry) {
-    if (dry) return 0;
-    if (lds > 64 * 1024) {
-        hipError_t e = mlsp_lds_limit((const void*)knn_mfma5_kernel<CT, VEC, RES, KB>, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((knn_mfma5_kernel<CT, VEC, RES, KB>), dim3((N / 128) * B), dim3(512), lds, st, x, xx, ld, N, C, k, idx, B, only);
-    return mlsp_launch_status();
-}
-
-static size_t knn5_lds_bytes(int CT, int N, bool res, bool kb, bool vec = false) {
-    size_t tile = (size_t)CT * KM_STRIDE;
-    if ((CT == 64 || (CT == 128 && !kb)) && !res && vec && (size_t)32 * (CT + 8) > tile) tile = (size_t)32 * (CT + 8);     // pass-A images (kernel: TILE_ALLOC)
-    const size_t keys = kb ? (size_t)2 * 128 * KNN5_CAPT : (size_t)2 * 4 * 2 * 32 * KNN5_CAP;     // floats
-    const size_t fl = (res ? (size_t)(N / 32) * tile + N : 4 * tile + 192) + keys + 128 + 256;
-    return fl * sizeof(float);
-}
-
-// returns MLSP_ERR_UNSUPPORTED when the shape is outside v5's fast path (caller falls back to v4 / the list-merge kernel).
-// only: per-cloud flags (device), nullptr = every cloud; dry: launch nothing, just say whether the shape is taken
-static int launch_knn_mfma5(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx,
-                            const int* only = nullptr, bool dry = false) {
-    if (N % 128 != 0 || k > 64 || C > 128) return MLSP_ERR_UNSUPPORTED;
-    const bool kb = k > 24;        // k = 25..32 on the 64-maxima bound overflow its 32-key buffers too often (734 us vs 290 at N = 2048)
-    const int CT = C <= 4 ? 4 : C <= 16 ? 16 : C <= 64 ? 64 : 128;
-    const bool vec = (C == CT) && (ld % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    const bool res = CT <= 16 && knn5_lds_bytes(CT, N, true, kb) <= 160 * 1024;
-    const size_t lds = knn5_lds_bytes(CT, N, res, kb, vec);
-    if (lds > 160 * 1024) return MLSP_ERR_UNSUPPORTED;
-#define KNN5_GO(CTV, VECV, RESV) do { if (kb) return launch_knn_mfma5_ct<CTV, VECV, RESV, 1>(st, x, ld, xx, B, N, C, k, idx, lds, only, dry); \
-                                      return launch_knn_mfma5_ct<CTV, VECV, RESV, 0>(st, x, ld, xx, B, N, C, k, idx, lds, only, dry); } while (0)
-    if (CT == 4) { if (res) { if (vec) KNN5_GO(4, true, true); KNN5_GO(4, false, true); } if (vec) KNN5_GO(4, true, false); KNN5_GO(4, false, false); }
-    if (CT == 16) { if (res) { if (vec) KNN5_GO(16, true, true); KNN5_GO(16, false, true); } if (vec) KNN5_GO(16, true, false); KNN5_GO(16, false, false); }
-    if (CT == 64) { if (vec) KNN5_GO(64, true, false); KNN5_GO(64, false, false); }
-    if (vec) KNN5_GO(128, true, false);
-    if (kb) return MLSP_ERR_UNSUPPORTED;       // k > 24 with 64 < C < 128 or unaligned rows: out of registers, stays on the list-merge kernel
-    return launch_knn_mfma5_ct<128, false, false, 0>(st, x, ld, xx, B, N, C, k, idx, lds, only, dry);
-#undef KNN5_GO
-}
-
-static size_t knn_lds_bytes(int KMAX, int C, bool runtime_c) {
-    size_t tiles = (size_t)4 * KNN_TJ * C + 4 * KNN_TJ + (runtime_c ? (size_t)KNN_QB * (C + 1) : 0);
-    size_t merge = (size_t)3 * KMAX * 64 * 2;
-    return (tiles > merge ? tiles : merge) * sizeof(float);
-}
-
-template <int KMAX>
-static int launch_knn_k(hipStream_t st, const float* x, int ld, const float* xx, int B, int N, int C, int k, int* idx) {
-    dim3 grid((N + KNN_QB - 1) / KNN_QB, B), block(256);
-    if (C == 3) {
-        hipLaunchKernelGGL((knn_kernel<KMAX, 3>), grid, block, knn_lds_bytes(KMAX, 3, false), st, x, xx, ld, N, C, k, idx);
-    } else {
-        size_t lds = knn_lds_bytes(KMAX, C, true);
-        if (lds > 160 * 1024) return MLSP_ERR_UNSUPPORTED;
-        if (lds > 64 * 1024) {
-            hipError_t e = mlsp_lds_limit((const void*)knn_kernel<KMAX, 0>, lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((knn_kernel<KMAX, 0>), grid, block, lds, st, x, xx, ld, N, C, k, idx);
-    }
-    return mlsp_launch_status();
-}
-
-// xx_ws: [B*N] floats of workspace; planes (nullable): knn6_plane_bytes(B*N, C) bytes of workspace for the v6 kernel's bf16 images
-int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx_ws, void* planes, size_t plane_bytes) {
-    if (!x || !idx || !xx_ws || B <= 0 || N <= 0 || C <= 0 || k <= 0 || k > N || ld < C) return MLSP_ERR_ARG;
-    int P = B * N;
-    // C <= 3 (raw and transformed cloud): the v6 skeleton with vector-exact sweeps (knn6.hip VEX)
-    if (planes && knn6_vex_supported(B, N, C, k) && plane_bytes >= knn6_vex_bytes(P)) {
-        const int rc = launch_knn6_vex(st, x, ld, B, N, C, k, idx, xx_ws, planes);
-        if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-    }
-    // v6 (knn6.hip): k <= 24 on whole 128-query chunks -- the five graph stages of DGCNN
-    if (planes && knn6_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) && C > 16) {   // (C <= 16 stays on v5 until v6's selection phases beat it there)
-        const int rc = launch_knn6(st, x, ld, B, N, C, k, idx, xx_ws, planes);
-        if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-    }
-    // 24 < k <= 40 (PointSegDA's k = 40): the wide v6 kernel, with the v5 kernel behind it for the clouds it flags (list overflow: massive
-    // ties; non-finite bounds) -- v5's workgroups of unflagged clouds return at once.  Only where v5 itself takes the shape.
-    // Every C <= 128: at C = 3 (B = 16, N = 2048, k = 40) 82 us against v5's 117, C = 64 152 / 235, C = 128 210 / 435.
-    if (planes && knn6w_supported(B, N, C, k) && plane_bytes >= knn6_plane_bytes(P, C) &&
-        launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx, nullptr, true) == 0) {
-        int* flags = nullptr;
-        const int rc = launch_knn6w(st, x, ld, B, N, C, k, idx, xx_ws, planes, &flags);
-        if (rc == 0) return launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx, flags, false);
-        if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-    }
-    hipLaunchKernelGGL(sqnorm_kernel, dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, C, xx_ws, idx, k);
-    // matrix-core kernels for every C <= 256 (the widest graph stage of the reference is 128 channels); beyond that only what the
-    // VALU kernel's LDS tiles hold (C <= ~200 at k <= 40): MLSP_ERR_UNSUPPORTED otherwise
-    if (C <= 256) {
-        // two-pass threshold select pays once there are enough candidates per query; small clouds keep v3
-        if (k <= 32 && C <= 128 && N >= 256) {
-            const int rc = launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx);
-            if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-            return launch_knn_mfma4(st, x, ld, xx_ws, B, N, C, k, idx);
-        }
-        if (k > 24 && k <= 64 && C <= 128 && N >= 128) {       // 128 chunk maxima per query need N >= 128
-            const int rc = launch_knn_mfma5(st, x, ld, xx_ws, B, N, C, k, idx);
-            if (rc != MLSP_ERR_UNSUPPORTED) return rc;
-        }
-        if (k <= 32) return launch_knn_mfma3(st, x, ld, xx_ws, B, N, C, k, idx);      // lane-distributed lists
-        // 32 < k <= 40 on a shape the two-pass kernel does not take (ragged N, N < 128, 64 < C < 128 or C > 128): the VALU kernel
-    }
-    if (k <= 20) return launch_knn_k<20>(st, x, ld, xx_ws, B, N, C, k, idx);
-    if (k <= 40) return launch_knn_k<40>(st, x, ld, xx_ws, B, N, C, k, idx);
-    return MLSP_ERR_UNSUPPORTED;
-}
 
 // ------------------------------------------------------------------------------------------------
-// Reverse neighbour index (CSR of the transposed kNN graph), one workgroup per cloud.
-// For every point j: the list of (i, slot) with idx[i][slot] == j, sorted by i*256+slot so that the
-// backward gather-reduce that walks it sums in a fixed order (bitwise reproducible gradients).
-//   rev_off [B*N+1]  global edge offsets;  rev_ent [B*N*k]  packed (i_local << 8 | slot)
-#define RV_SPLIT_MAX 16                   // workgroups per cloud: 8, or 16 when 8 would leave CUs idle (chosen by the launcher)
-#define RV_CAP (16 * 1024)                // LDS entries of a slice's lists, twice: filled / ordered (a slice past that sorts in place in global memory)
-// `nsplit` workgroups per cloud, each owns a contiguous slice of the destinations: it counts only the edges that point into its
-// slice (LDS atomics are the expensive instruction here: ~3 clocks per lane), gets the slice's base offset by counting the edges
-// that point BELOW it (plain adds + one block reduction), fills its lists and orders every list.
-// skip_pad: the padding slots of a ball-query group (copies of its first hit: slot s > 0 with idx[i][s] == idx[i][0]) are left out of the
-// lists -- their rows are identical, the consumer adds them as a multiple of one row (sa.hip, sa_fold_bwd_point_kernel).  The lists of a
-// cloud then no longer fill its E entries, so the list LENGTHS are returned as well (rev_cnt, nullable otherwise).
-typedef int knn_i32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict__ idx, int N, int k,
-                                                           int* __restrict__ rev_off, int* __restrict__ rev_ent,
-                                                           int B, int S, int nsplit, int skip_pad, int* __restrict__ rev_cnt) {
-    extern __shared__ __attribute__((aligned(16))) int ism[];
-    __shared__ int wsum[16];
-    __shared__ int nbig;                  // lists of more than 64 entries: queued (cnt is free by then) for the whole-workgroup loop
-    int b, part;
-    xcd_cloud_map(blockIdx.x, nsplit, B, b, part);        // the workgroups of a cloud share an XCD (they read the same idx)
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int dper = (N + nsplit - 1) / nsplit, d0 = min(N, part * dper), d1 = min(N, d0 + dper), nd = d1 - d0;
-    int* cnt = ism;            // [dper]
-    int* off = ism + dper;     // [dper + 1]  offsets inside the slice
-    int* offp = off + dper + 1;   // [dper + 1]  the same with every list padded to a multiple of 4 entries: where the lists lie in `lent`
-    int* lent = ism + ((3 * dper + 2 + 3) & ~3);   // [RV_CAP] as filled; 16-byte aligned lists (pads hold INT_MAX): the ordering reads four entries per LDS instruction
-    int* lord = lent + RV_CAP;    // [RV_CAP] ordered (unpadded: the slice's part of rev_ent)
-    // S source rows of k slots per cloud point at N destinations (S == N for the kNN graph; the set-abstraction grouping has
-    // S sampled centres gathering from N points)
-    const int* ib = idx + (size_t)b * S * k;
-    const int E = S * k;
-    for (int j = tid; j < nd; j += nt) cnt[j] = 0;
-    if (tid == 0) nbig = 0;
-    __syncthreads();
-    int below = 0;
-    // RV_B index loads in flight per thread (the atomics would serialise them): a pass is a chain of ceil(E / (RV_B nt)) load latencies, ONE
-    // at the DGCNN shape (E = 20 Ki entries, 1024 threads) -- and then the fill pass below reuses the registers instead of reading idx again
-    constexpr int RV_B = 20;
-    const bool one_trip = E <= nt * RV_B;
-    // Several trips (PointSegDA: N = 2048, k = 40 -> 80 entries per thread): the entries that fall into this workgroup's slice (E / nsplit of
-    // them on average) are COMPACTED into `lord` as (destination, source entry) pairs while they are counted -- `lord` is free until the
-    // lists are ordered -- and the fill pass walks those pairs instead of scanning the cloud's E indices again.  More than RV_CAP / 2 pairs:
-    // the fill pass scans again as before.
-    __shared__ int ncomp;
-    if (tid == 0) ncomp = 0;
-    const int comp_cap = RV_CAP / 2;
-    int jk[RV_B];
-    __syncthreads();
-    for (int eb = tid; eb < E; eb += nt * RV_B) {
-#pragma unroll
-        for (int u = 0; u < RV_B; ++u) jk[u] = eb + u * nt < E ? ib[eb + u * nt] : -1;
-#pragma unroll
-        for (int u = 0; u < RV_B; ++u) {
-            int j = jk[u];
-            if (skip_pad && j >= 0) { const int e = eb + u * nt, sl = e % k; if (sl != 0 && j == ib[e - sl]) j = -1; }
-            jk[u] = j;
-            below += j >= 0 && j < d0;
-            const bool mine = j >= d0 && j < d1;
-            if (mine) atomicAdd(&cnt[j - d0], 1);
-            if (!one_trip) {                             // (uniform) one LDS atomic per wave and entry slot: the wave's matches take consecutive places
-                const unsigned long long mm = __ballot(mine);
-                if (mm) {
-                    const int lane_ = tid & 63;
-                    int base_ = 0;
-                    if (lane_ == 0) base_ = atomicAdd(&ncomp, __builtin_popcountll(mm));
-                    base_ = __shfl(base_, 0, 64);
-                    const int at = base_ + __builtin_popcountll(mm & ((1ull << lane_) - 1ull));
-                    if (mine && at < comp_cap) { lord[2 * at] = j - d0; lord[2 * at + 1] = eb + u * nt; }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o, 64);
-    if ((tid & 63) == 0) wsum[tid >> 6] = below;
-    __syncthreads();
-    int s0 = 0;
-    for (int w = 0; w < (nt >> 6); ++w) s0 += wsum[w];   // edges into the slices before this one
-    // exclusive scan of the slice's counts by one wave
-    if (tid < 64) {
-        const int chunk = (nd + 63) / 64;
-        const int beg = min(nd, tid * chunk), end = min(nd, beg + chunk);
-        int sm = 0, smp = 0;
-        for (int j = beg; j < end; ++j) { sm += cnt[j]; smp += (cnt[j] + 3) & ~3; }
-        int incl = sm, inclp = smp;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64), tp = __shfl_up(inclp, o, 64);
-            if (tid >= o) { incl += t; inclp += tp; }
-        }
-        int run = incl - sm, runp = inclp - smp;
-        for (int j = beg; j < end; ++j) { off[j] = run; run += cnt[j]; offp[j] = runp; runp += (cnt[j] + 3) & ~3; }
-        if (tid == 63) { off[nd] = incl; offp[nd] = inclp; }
-    }
-    __syncthreads();
-    const int gbase = b * E;
-    const int sn = off[nd];
-    const bool in_lds = offp[nd] <= RV_CAP;
-    for (int j = tid; j < nd; j += nt) {
-        rev_off[(size_t)b * N + d0 + j] = gbase + s0 + off[j];
-        if (rev_cnt) rev_cnt[(size_t)b * N + d0 + j] = off[j + 1] - off[j];
-        if (in_lds) {
-            const int c = off[j + 1] - off[j];
-            for (int q = c; q < ((c + 3) & ~3); ++q) lent[offp[j] + q] = 0x7fffffff;       // pads: never below a real entry
-        }
-        cnt[j] = 0;
-    }
-    if (b == B - 1 && part == nsplit - 1 && tid == 0) rev_off[(size_t)B * N] = gbase + E;
-    __syncthreads();
-    // fill + order this slice's lists in LDS, then one coalesced copy out: the ordering never touches global memory
-    // (a slice with more than RV_CAP entries orders in place in global memory instead)
-    int* ent = in_lds ? lent : rev_ent + gbase + s0;
-    const int* eoff = in_lds ? offp : off;                                 // where list j starts in `ent`
-    const bool compacted = !one_trip && in_lds && ncomp <= comp_cap;       // (ncomp == sn: every pair is there)
-    if (compacted) {
-        for (int i = tid; i < sn; i += nt) {
-            const int jl = lord[2 * i], e = lord[2 * i + 1];
-            const int pos = atomicAdd(&cnt[jl], 1);
-            ent[eoff[jl] + pos] = ((e / k) << 8) | (e % k);
-        }
-    } else
-    for (int eb = tid; eb < E; eb += nt * RV_B) {
-        if (!one_trip) {
-#pragma unroll
-            for (int u = 0; u < RV_B; ++u) jk[u] = eb + u * nt < E ? ib[eb + u * nt] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < RV_B; ++u) {
-            int j = jk[u];
-            const int e = eb + u * nt;
-            if (!one_trip && skip_pad && j >= 0) { const int sl = e % k; if (sl != 0 && j == ib[e - sl]) j = -1; }
-            if (j >= d0 && j < d1) {
-                const int pos = atomicAdd(&cnt[j - d0], 1);
-                ent[eoff[j - d0] + pos] = ((e / k) << 8) | (e % k);
-            }
-        }
-    }
-    __syncthreads();
-    if (in_lds) {
-        // order every list by (i, slot) by RANK: 16 lanes per list, every lane ranks its entries against the whole list (the 16 lanes
-        // read the same LDS words: broadcasts) and writes them straight to their final place.  Lists of more than 64 entries
-        // (ball-query groups are padded with copies of their first hit: a few points collect hundreds of edges) are left to the
-        // second loop, where the whole workgroup shares one list.
-        int* out = lord;
-        const int lg = tid >> 4, ll = tid & 15;
-        for (int j = lg; j < nd; j += nt >> 4) {
-            const int e0 = off[j], n = off[j + 1] - e0;
-            if (n > 64) {
-                if (ll == 0) cnt[atomicAdd(&nbig, 1)] = j;
-                continue;
-            }
-            const int* a = ent + offp[j];                  // 16-byte aligned, padded with INT_MAX to a multiple of 4
-            for (int q = ll; q < n; q += 16) {
-                const int v = a[q];
-                int rank = 0;
-                for (int e = 0; e < n; e += 4) {
-                    const knn_i32x4 t = *(const knn_i32x4*)(a + e);
-                    rank += (t[0] < v) + (t[1] < v) + (t[2] < v) + (t[3] < v);
-                }
-                out[e0 + rank] = v;
-            }
-        }
-        __syncthreads();
-        // lists of 65 .. 512 entries (the tail of a kNN graph's in-degree distribution: a dozen per workgroup at k = 40, a few at k = 20):
-        // ONE WAVE per list, sixteen lists at a time -- the whole workgroup walking them one after the other was the longest phase of the
-        // kernel (8 of 21 us at k = 20, 29 of 61 us at k = 40, N = 2048).  Longer ones (ball-query hubs): the whole workgroup per list.
-        {
-            const int wv = tid >> 6, ln = tid & 63;
-            for (int bi = wv; bi < nbig; bi += nt >> 6) {
-                const int j = cnt[bi];
-                const int e0 = off[j], n = off[j + 1] - e0;
-                if (n > 512) continue;
-                const int* a = ent + offp[j];
-                for (int q = ln; q < n; q += 64) {
-                    const int v = a[q];
-                    int rank = 0;
-                    for (int e = 0; e < n; e += 4) {
-                        const knn_i32x4 t = *(const knn_i32x4*)(a + e);
-                        rank += (t[0] < v) + (t[1] < v) + (t[2] < v) + (t[3] < v);
-                    }
-                    out[e0 + rank] = v;
-                }
-            }
-        }
-        for (int bi = 0; bi < nbig; ++bi) {
-            const int j = cnt[bi];
-            const int e0 = off[j], n = off[j + 1] - e0;
-            if (n <= 512) continue;
-            const int* a = ent + offp[j];
-            for (int q = tid; q < n; q += nt) {
-                const int v = a[q];
-                int rank = 0;
-                for (int e = 0; e < n; ++e) rank += a[e] < v;
-                out[e0 + rank] = v;
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < sn; i += nt) rev_ent[gbase + s0 + i] = lord[i];      // one coalesced copy out
-        return;
-    }
-    __threadfence_block();
-    // a slice too large for LDS: per-destination insertion sort in place in global memory
-    for (int j = tid; j < nd; j += nt) {
-        int* a = ent + off[j];
-        const int n = off[j + 1] - off[j];
-        for (int u = 1; u < n; ++u) {
-            const int key = a[u];
-            int w = u - 1;
-            while (w >= 0 && a[w] > key) { a[w + 1] = a[w]; --w; }
-            a[w + 1] = key;
-        }
-    }
+// The launcher.  knn_plan.h decides; a picker per family names every instantiation of its kernel once.
+typedef void (*Knn1Fn)(const float*, const float*, int, int, int, int, int*);
+typedef void (*Knn3Fn)(const float*, const float*, int, int, int, int, int, int*);
+typedef void (*Knn4Fn)(const float*, const float*, int, int, int, int, int, int*, int);
+typedef void (*Knn5Fn)(const float*, const float*, int, int, int, int, int*, int, const int*);
+
+static Knn1Fn knn1_pick(int KMAX, int CT) {
+    if (KMAX == 20) return CT == 3 ? knn_kernel<20, 3> : knn_kernel<20, 0>;
+    return CT == 3 ? knn_kernel<40, 3> : knn_kernel<40, 0>;
+}
+static Knn3Fn knn3_pick(int CT) {
+    return CT == 4 ? knn_mfma3_kernel<4> : CT == 16 ? knn_mfma3_kernel<16> : CT == 64 ? knn_mfma3_kernel<64> : CT == 128 ? knn_mfma3_kernel<128> : knn_mfma3_kernel<256>;
+}
+static Knn4Fn knn4_pick(int CT) {
+    return CT == 4 ? knn_mfma4_kernel<4> : CT == 16 ? knn_mfma4_kernel<16> : CT == 64 ? knn_mfma4_kernel<64> : knn_mfma4_kernel<128>;
+}
+template <int CT, bool VEC, bool RES>
+static Knn5Fn knn5_kb(bool kb) { return kb ? knn_mfma5_kernel<CT, VEC, RES, 1> : knn_mfma5_kernel<CT, VEC, RES, 0>; }
+template <int CT, bool RES>
+static Knn5Fn knn5_vec(const Knn5Plan& v) { return v.vec ? knn5_kb<CT, true, RES>(v.kb) : knn5_kb<CT, false, RES>(v.kb); }
+static Knn5Fn knn5_pick(const Knn5Plan& v) {
+    if (v.CT == 4) return v.res ? knn5_vec<4, true>(v) : knn5_vec<4, false>(v);
+    if (v.CT == 16) return v.res ? knn5_vec<16, true>(v) : knn5_vec<16, false>(v);
+    if (v.CT == 64) return knn5_vec<64, false>(v);
+    if (v.vec) return knn5_kb<128, true, false>(v.kb);
+    return knn_mfma5_kernel<128, false, false, 0>;          // (KB = 1 here is out of registers: the plan never asks for it)
 }
 
-static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent, int skip_pad = 0,
-                          int* rev_cnt = nullptr) {
-    if (!idx || !rev_off || !rev_ent || B <= 0 || N <= 0 || S <= 0 || k <= 0 || k > 256 || N > (1 << 22) || S > (1 << 22)) return MLSP_ERR_ARG;
-    const int nsplit = B * 8 >= 256 || N < 1024 ? 8 : RV_SPLIT_MAX;
-    const int dper = (N + nsplit - 1) / nsplit;
-    const size_t lds = (size_t)(((3 * dper + 2 + 3) & ~3) + 2 * RV_CAP) * sizeof(int);
-    if (lds > 160 * 1024) return MLSP_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = mlsp_lds_limit((const void*)knn_reverse_kernel, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(knn_reverse_kernel, dim3(B * nsplit), dim3(1024), lds, st, idx, N, k, rev_off, rev_ent, B, S, nsplit, skip_pad, rev_cnt);
-    return mlsp_launch_status();
-}
+bool knn6_vex_supported(int B, int N, int C, int k) { return knn_q_vex_supported(B, N, C, k); }
+bool knn6_supported(int B, int N, int C, int k) { return knn_q_v6_supported(B, N, C, k); }
+bool knn6w_supported(int B, int N, int C, int k) { return knn_q_v6w_supported(B, N, C, k); }
 
-// ball-query groups (padded with copies of the first hit)
-int launch_group_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent) {
-    return launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent);
-}
-// the same without the padding slots; pad_cnt [B*S] = number of padding slots of every group (s > 0 with idx[i][s] == idx[i][0])
-__global__ __launch_bounds__(256) void group_pad_count_kernel(const int* __restrict__ idx, int G, int k, int* __restrict__ pad_cnt) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= G) return;
-    const int* r = idx + (size_t)g * k;
-    const int first = r[0];
-    int c = 0;
-    for (int s = 1; s < k; ++s) c += r[s] == first;
-    pad_cnt[g] = c;
-}
-int launch_group_reverse_compact(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_cnt, int* rev_ent,
-                                 int* pad_cnt) {
-    if (!rev_cnt || !pad_cnt) return MLSP_ERR_ARG;
-    const int rc = launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, 1, rev_cnt);
-    if (rc != MLSP_OK) return rc;
-    hipLaunchKernelGGL(group_pad_count_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, idx, B * S, k, pad_cnt);
-    return mlsp_launch_status();
-}
-int launch_knn_reverse(hipStream_t st, const int* idx, int B, int N, int k, int* rev_off, int* rev_ent) {
-    return launch_reverse(st, idx, B, N, N, k, rev_off, rev_ent);
+// xx_ws: [B*N] floats of workspace; planes (nullable): plane_bytes bytes of workspace for the v6 families (the plan's plane_bytes: the
+// bf16 images of knn6_kernel / knn6w_kernel, the {x, xx} image of the vector-exact mode); a call the plan refuses launches nothing
+int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx_ws, void* planes, size_t plane_bytes) {
+    if (!x || !idx || !xx_ws) return MLSP_ERR_ARG;
+    KnnAsk q;
+    q.B = B; q.N = N; q.C = C; q.k = k; q.ld = ld; q.x16 = ((uintptr_t)x & 15) == 0;
+    q.planes_avail = planes ? plane_bytes : 0; q.planes16 = ((uintptr_t)planes & 15) == 0;
+    const KnnPlan p = knn_plan(q);
+    if (p.status != MLSP_OK) return p.status;
+    const int P = B * N;
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    if (p.norm_pass) hipLaunchKernelGGL(sqnorm_kernel, dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, C, xx_ws, idx, k);
+    switch (p.family) {
+    case KNN_FAM_V5: return mlsp_launch_lds(st, knn5_pick(p.v5), grid, block, p.lds, x, xx_ws, ld, N, C, k, idx, B, nullptr);
+    case KNN_FAM_V4: return mlsp_launch_lds(st, knn4_pick(p.CT), grid, block, p.lds, x, xx_ws, ld, N, C, k, (int)p.vec, idx, B);
+    case KNN_FAM_V3: return mlsp_launch_lds(st, knn3_pick(p.CT), grid, block, p.lds, x, xx_ws, ld, N, C, k, (int)p.vec, idx);
+    case KNN_FAM_VALU: return mlsp_launch_lds(st, knn1_pick(p.KMAX, p.CT), grid, block, p.lds, x, xx_ws, ld, N, C, k, idx);
+    default: break;                                         // the v6 families: knn6.hip
+    }
+    int* flags = nullptr;
+    const int rc = launch_knn6(st, p, x, ld, B, N, C, k, idx, xx_ws, planes, &flags);
+    if (rc != MLSP_OK || p.family != KNN_FAM_V6W_V5) return rc;
+    // the v5 kernel behind the wide one: its workgroups of unflagged clouds return at once
+    return mlsp_launch_lds(st, knn5_pick(p.v5), dim3(p.v5.grid_x), dim3(512), p.v5.lds, x, xx_ws, ld, N, C, k, idx, B, flags);
 }

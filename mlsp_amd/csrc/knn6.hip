@@ -41,6 +41,7 @@
 // tau 5.5 k, list conversion 5 k, sort / flag / settle 26 k, exact distances 16 k (bound by cache-line transactions: every 16-byte piece
 // of a gathered row is its own transaction; a cooperative fetch through LDS lost to its chain of dependent steps as written here).
 #include "common.h"
+#include "knn_plan.h"      // K6_KMAX / K6W_KMAX / K6_LSTR, knn6_lds_bytes, the layout of the planes
 #include <math.h>
 #include <type_traits>
 
@@ -49,11 +50,8 @@ typedef unsigned int k6u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int k6u32x4 __attribute__((ext_vector_type(4)));
 typedef int k6i32x4 __attribute__((ext_vector_type(4)));
 
-#define K6_KMAX 24          // largest k of knn6_kernel
-#define K6W_KMAX 40         // ... of knn6w_kernel
 #define K6_CAP 24           // survivors one list (a query's candidates of one part and half-wave) keeps
 #define K6_LENT 28          // entries of a list: the cursor is clamped every 4 appends
-#define K6_LSTR 232         // bytes between lists (58 dwords: 16 consecutive lists start in 16 different even banks)
 #define K6_EPS 1.220703125e-04f      // 2^-13 (error budget in the header)
 
 // byte offset of the 16-byte piece (point row of its tile, half h) of block kb, plane p (0 hi, 1 lo) of tile T
@@ -1023,76 +1021,33 @@ __global__ __launch_bounds__(512) void knn6w_kernel(const float* __restrict__ x,
     k6_counting_final<Cut>(fin, false);
 }
 
-static size_t knn6_lds_bytes(int N) { return (size_t)512 * K6_LSTR + (size_t)N * 4 + 128 * 4 + 512 * 4 + 64 + (size_t)8 * 512 * 4 + 512 * 4; }
-
-// shapes v6 takes (the rest stays on knn.hip's kernels)
-// the vector-exact mode of the kernel: C <= 3 on whole 128-query chunks, the cloud's {x, xx} image in the 16 KB work-list area
-bool knn6_vex_supported(int B, int N, int C, int k) {
-    return B > 0 && N >= 128 && N % 128 == 0 && N <= 1024 && C >= 1 && C <= 3 && k >= 1 && k <= K6_KMAX && k <= N;
-}
-size_t knn6_vex_bytes(int P) { return (size_t)P * 16; }
-int launch_knn6_vex(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* cand) {
-    if (!knn6_vex_supported(B, N, C, k) || !cand || (((uintptr_t)cand) & 15)) return MLSP_ERR_UNSUPPORTED;
-    const int P = B * N;
-    hipLaunchKernelGGL(knn6_prep_vex_kernel, dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, C, xx, (f32x4*)cand, idx, k);
-    const size_t lds = knn6_lds_bytes(N);
-    hipError_t e = mlsp_lds_limit((const void*)knn6_kernel<16, true>, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((knn6_kernel<16, true>), dim3((N / 128) * B), dim3(512), lds, st, x, ld, xx, xx, (const char*)cand, N, C, k, idx, B);
-    return mlsp_launch_status();
-}
-
-bool knn6_supported(int B, int N, int C, int k) {
-    return B > 0 && N >= 128 && N % 128 == 0 && N <= 4096 && C >= 1 && C <= 128 && k >= 1 && k <= K6_KMAX && k <= N &&
-           knn6_lds_bytes(N) <= 160 * 1024;
-}
-static int knn6_padded_channels(int C) { return C <= 16 ? 16 : C <= 64 ? 64 : 128; }
-// image + centred norms + the wide kernel's cloud flags (B <= P / 128 ints)
-size_t knn6_plane_bytes(int P, int C) { return (size_t)P * 2 * knn6_padded_channels(C) * sizeof(__bf16) + (size_t)P * sizeof(float) + ((size_t)P / 128 + 4) * sizeof(int); }
-bool knn6w_supported(int B, int N, int C, int k) {
-    return B > 0 && N >= 128 && N % 128 == 0 && N <= 4096 && C >= 1 && C <= 128 && k > K6_KMAX && k <= K6W_KMAX && k <= N &&
-           knn6_lds_bytes(N) <= 160 * 1024;
-}
-
 template <int CT>
-static int knn6_go(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, float* xc, char* planes) {
+static int knn6_go(hipStream_t st, const KnnPlan& p, bool wide, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, float* xc, char* planes,
+                   int* flags) {
     const int P = B * N;
-    hipLaunchKernelGGL((knn6_prep_kernel<CT>), dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, N, C, xx, xc, planes, idx, k, (int*)nullptr);
-    const size_t lds = knn6_lds_bytes(N);
-    hipError_t e = mlsp_lds_limit((const void*)knn6_kernel<CT>, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((knn6_kernel<CT>), dim3((N / 128) * B), dim3(512), lds, st, x, ld, xx, xc, planes, N, C, k, idx, B);
-    return mlsp_launch_status();
-}
-
-template <int CT>
-static int knn6w_go(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, float* xc, char* planes, int* flags) {
-    const int P = B * N;
+    const dim3 grid(p.grid_x), block(p.block);
     hipLaunchKernelGGL((knn6_prep_kernel<CT>), dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, N, C, xx, xc, planes, idx, k, flags);
-    const size_t lds = knn6_lds_bytes(N);
-    hipError_t e = mlsp_lds_limit((const void*)knn6w_kernel<CT>, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((knn6w_kernel<CT>), dim3((N / 64) * B), dim3(512), lds, st, x, ld, xx, xc, planes, N, C, k, idx, B, flags);
-    return mlsp_launch_status();
-}
-// 24 < k <= 40: prep + knn6w_kernel; *flags_out = the per-cloud flags ([B] ints inside `planes`) the caller hands to the v5 launch behind it
-int launch_knn6w(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes, int** flags_out) {
-    if (!knn6w_supported(B, N, C, k) || !planes || (((uintptr_t)planes) & 15)) return MLSP_ERR_UNSUPPORTED;
-    const int CT = knn6_padded_channels(C);
-    float* xc = (float*)((char*)planes + (size_t)B * N * CT * 4);
-    int* flags = (int*)(xc + (size_t)B * N);
-    *flags_out = flags;
-    if (CT == 16) return knn6w_go<16>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
-    if (CT == 64) return knn6w_go<64>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
-    return knn6w_go<128>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
+    if (wide) return mlsp_launch_lds(st, knn6w_kernel<CT>, grid, block, p.lds, x, ld, xx, xc, planes, N, C, k, idx, B, flags);
+    return mlsp_launch_lds(st, knn6_kernel<CT>, grid, block, p.lds, x, ld, xx, xc, planes, N, C, k, idx, B);
 }
 
-// xx [B*N] floats and planes (knn6_plane_bytes) are workspace; both are written here (xx = canonical squared norms, as sqnorm_kernel)
-int launch_knn6(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes) {
-    if (!knn6_supported(B, N, C, k) || !planes || (((uintptr_t)planes) & 15)) return MLSP_ERR_UNSUPPORTED;
-    const int CT = knn6_padded_channels(C);
-    float* xc = (float*)((char*)planes + (size_t)B * N * CT * 4);            // centred norms behind the fragment image (knn6_plane_bytes covers them)
-    if (CT == 16) return knn6_go<16>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes);
-    if (CT == 64) return knn6_go<64>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes);
-    return knn6_go<128>(st, x, ld, B, N, C, k, idx, xx, xc, (char*)planes);
+// The v6 families of a plan (knn_plan.h: VEX, V6, V6W_V5): the prep kernel, then the search kernel.  xx [B*N] floats and `planes` (the
+// plan's plane_bytes) are workspace that the launch writes (xx = canonical squared norms, as sqnorm_kernel).  V6W_V5: *flags_out = the
+// per-cloud flags ([B] ints inside `planes`) the caller hands to the v5 launch behind it.  The kernels' own preconditions are checked here.
+int launch_knn6(hipStream_t st, const KnnPlan& p, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes,
+                int** flags_out) {
+    const bool vex = p.family == KNN_FAM_VEX, wide = p.family == KNN_FAM_V6W_V5;
+    const bool takes = vex ? knn6_vex_supported(B, N, C, k) : wide ? knn6w_supported(B, N, C, k) : p.family == KNN_FAM_V6 && knn6_supported(B, N, C, k);
+    if (p.status != MLSP_OK || !takes || !planes || (((uintptr_t)planes) & 15)) return MLSP_ERR_UNSUPPORTED;
+    const int P = B * N;
+    if (vex) {
+        hipLaunchKernelGGL(knn6_prep_vex_kernel, dim3((P + 255) / 256), dim3(256), 0, st, x, ld, P, C, xx, (f32x4*)planes, idx, k);
+        return mlsp_launch_lds(st, knn6_kernel<16, true>, dim3(p.grid_x), dim3(p.block), p.lds, x, ld, xx, xx, (const char*)planes, N, C, k, idx, B);
+    }
+    float* xc = (float*)((char*)planes + (size_t)P * p.CT * 4);              // centred norms behind the fragment image (knn6_plane_bytes covers them)
+    int* flags = wide ? (int*)(xc + (size_t)P) : nullptr;
+    *flags_out = flags;
+    if (p.CT == 16) return knn6_go<16>(st, p, wide, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
+    if (p.CT == 64) return knn6_go<64>(st, p, wide, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
+    return knn6_go<128>(st, p, wide, x, ld, B, N, C, k, idx, xx, xc, (char*)planes, flags);
 }

@@ -30,24 +30,25 @@ int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int
 int launch_gemm_mx(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int K, const void* A, int a_bf16, int lda, const void* B, int b_bf16,
                    int ldb, void* C, int c_bf16, int ldc, const GemmOpts& o = GemmOpts());
 
-// knn.hip
-// xx_ws: [B*N] floats of workspace; planes (nullable): knn6_plane_bytes(B*N, C) bytes of workspace for the v6 kernel's bf16 images
+// knn.hip (the search kernels v1 - v5 and the launcher that follows knn_plan.h)
+// xx_ws: [B*N] floats of workspace; planes (nullable): plane_bytes bytes of workspace for the v6 families (what the plan's plane_bytes asks)
 int launch_knn(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx_ws, void* planes, size_t plane_bytes);
+// the shapes knn6.hip's kernels take, as statements over knn_plan.h: vector-exact mode / knn6_kernel / knn6w_kernel
+bool knn6_vex_supported(int B, int N, int C, int k);
+bool knn6_supported(int B, int N, int C, int k);
+bool knn6w_supported(int B, int N, int C, int k);
+
+// knn6.hip (the v6 search kernels)
+// p: the plan of the call (family VEX, V6 or V6W_V5); xx [B*N] floats and planes (the plan's plane_bytes) are workspace that the launch
+// writes; *flags_out (V6W_V5): the per-cloud flags ([B] ints inside `planes`) the caller hands to the v5 launch behind it
+struct KnnPlan;
+int launch_knn6(hipStream_t st, const KnnPlan& p, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes,
+                int** flags_out);
+
+// reverse.hip (the reverse neighbour index: not a search kernel)
 int launch_group_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent);
 int launch_group_reverse_compact(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_cnt, int* rev_ent, int* pad_cnt);
 int launch_knn_reverse(hipStream_t st, const int* idx, int B, int N, int k, int* rev_off, int* rev_ent);
-
-// knn6.hip
-// xx [B*N] floats, planes (knn6_plane_bytes) and cand (knn6_vex_bytes) are workspace that the launch writes; *flags_out of launch_knn6w:
-// the per-cloud flags ([B] ints inside `planes`) the caller hands to the v5 launch behind it
-bool knn6_vex_supported(int B, int N, int C, int k);
-size_t knn6_vex_bytes(int P);
-int launch_knn6_vex(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* cand);
-bool knn6_supported(int B, int N, int C, int k);
-size_t knn6_plane_bytes(int P, int C);
-bool knn6w_supported(int B, int N, int C, int k);
-int launch_knn6w(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes, int** flags_out);
-int launch_knn6(hipStream_t st, const float* x, int ld, int B, int N, int C, int k, int* idx, float* xx, void* planes);
 
 // bn.hip
 int bn_vec_parts(int M);

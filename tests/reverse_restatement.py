@@ -1,4 +1,4 @@
-"""The reverse neighbour index (mlsp_amd/csrc/knn.hip: knn_reverse_kernel, launch_reverse, group_pad_count_kernel) restated in plain numpy:
+"""The reverse neighbour index (mlsp_amd/csrc/reverse.hip: knn_reverse_kernel, launch_reverse, group_pad_count_kernel) restated in plain numpy:
 the exact index a host sort gives, the launcher's and the kernel's dispatch arithmetic (which slice of which cloud takes which path), a
 builder of groups shaped like ball-query output, and the case table of tests/test_gpu_reverse_index.py.
 Shared by tests/test_gpu_reverse_index.py and tests/test_reverse_restatement_cpu.py (which proves which case reaches which path)."""
@@ -6,7 +6,7 @@ import collections
 
 import numpy as np
 
-# restated from knn.hip; tests/test_reverse_restatement_cpu.py reads the three lines there and fails when they drift
+# restated from reverse.hip; tests/test_reverse_restatement_cpu.py reads the three lines there and fails when they drift
 RV_CAP = 16 * 1024          # LDS entries of a slice's lists (a slice past that orders in place in global memory)
 RV_B = 20                   # index loads in flight per thread: E <= RV_THREADS * RV_B entries is ONE trip
 RV_SPLIT_MAX = 16           # workgroups per cloud: 8, or 16

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import golden_common as gc
+import knn_shapes
 from oracle import knn_canon, ref_cpu, ref_torch_modules
 from tnet_restatement import tnet_edge_f64 as _tnet_edge_f64
 
@@ -34,23 +35,7 @@ def _rand(shape, seed, scale=1.0):
 
 
 # ----------------------------------------------------------------------------- kNN: bit-exact
-@pytest.mark.parametrize("B,N,C,k", [(2, 256, 3, 20), (2, 1024, 3, 20), (2, 256, 64, 20), (1, 1024, 128, 20),
-                                     (3, 20, 3, 20), (2, 33, 64, 20), (2, 100, 5, 7), (1, 300, 3, 40), (2, 70, 16, 1),
-                                     # v5 (two waves per query group) paths: LDS-resident / streamed, vector / scalar loads
-                                     (2, 384, 16, 20), (2, 256, 5, 32), (1, 512, 100, 20), (1, 2048, 3, 20),
-                                     (1, 4096, 16, 8), (2, 640, 64, 32), (8, 128, 64, 20), (9, 256, 128, 20),
-                                     # the benchmarked shapes themselves (BASELINE.json configs[1]: B = 32, N = 1024; XCD-mapped 8-wave path)
-                                     (32, 1024, 3, 20), (32, 1024, 64, 20), (32, 1024, 128, 20), (32, 2048, 64, 20),
-                                     # k > 32 (configs[4]: k = 40): the two-pass select with 128 chunk maxima per query
-                                     (2, 2048, 3, 40), (8, 2048, 64, 40), (3, 1024, 128, 40), (2, 512, 64, 33), (1, 256, 16, 48),
-                                     (1, 128, 64, 64), (2, 2048, 64, 64), (2, 1024, 64, 25), (1, 384, 100, 40),
-                                     # v6 (knn6.hip: k <= 24, N % 128 == 0): fewest tiles, ragged tile-ring tails, k = 1 / 24, unaligned rows
-                                     (1, 128, 3, 1), (2, 128, 64, 24), (2, 256, 3, 24), (3, 384, 5, 20), (2, 1152, 64, 20), (1, 1152, 3, 20),
-                                     (2, 640, 33, 7), (1, 2048, 128, 24), (16, 128, 16, 20),
-                                     # v6 wide (knn6w_kernel: 24 < k <= 40, N % 128 == 0, C > 16): one tile per quarter, ragged rings, the configs[4] shape
-                                     (2, 128, 64, 40), (3, 256, 64, 25), (2, 640, 128, 40), (1, 1152, 33, 37), (16, 2048, 64, 40), (1, 4096, 64, 40),
-                                     # the VALU kernel: 32 < k <= 40 on shapes outside the two-pass kernel (ragged N, N < 128, 64 < C < 128, C > 128)
-                                     (2, 150, 200, 40), (1, 96, 200, 36), (2, 100, 24, 33)])
+@pytest.mark.parametrize("B,N,C,k", [s[:4] for s in knn_shapes.BIT_EXACT])      # (each with the kernel it reaches: knn_shapes.py)
 def test_knn_bit_exact_vs_oracle(dev, B, N, C, k):
     Fh = _fh()
     xp = _rand((B * N, C), 100 + N + C)
@@ -1536,8 +1521,17 @@ def test_pointmlp_colmax_fwd_bwd(dev, B, N, Cin, Cout, training):
 
 def test_knn_two_pass_overflow_fallback(dev):
     """v4 threshold select: massive ties overflow the survivor buffers and must fall back to the exact
-    sequential path (all-identical points; few distinct points; a cloud that mixes both with random points)."""
+    sequential path (all-identical points; few distinct points; a cloud that mixes both with random points).  The N = 300 clouds reach
+    knn_mfma4_kernel (knn_shapes.OTHER); the two older cases reach the v6 kernels' own overflow paths since those kernels exist."""
     Fh = _fh()
+    for B, N, C in ((2, 300, 3), (1, 300, 64)):
+        x = _rand((B, N, C), 11 + C)
+        x[0] = x[0, :1]                                                      # N identical points: every buffer overflows
+        if B > 1:
+            x[1, 20:280] = x[1, torch.arange(260) % 4]                       # 4 distinct points, 65 copies each, inside a random cloud
+        want = knn_canon.knn_point_major(x, 20)
+        got = Fh.knn_graph(x.view(B * N, C).to(dev), B, N, 20).idx.view(B, N, 20).cpu().numpy()
+        assert np.array_equal(got, want), (N, C, int((got != want).any(-1).sum()))
     B, N, k = 3, 512, 20
     x = torch.zeros(B, N, 3)
     x[1] = (torch.arange(N) % 4).float().view(N, 1).expand(N, 3) * 0.25      # 4 distinct points, 128 copies each

@@ -1,5 +1,5 @@
 """The host restatement that tests/test_gpu_reverse_index.py measures the reverse-index builder against (tests/reverse_restatement.py),
-pinned on the CPU: its constants against the text of knn.hip, its index on an example worked by hand, and -- the point of the case table
+pinned on the CPU: its constants against the text of reverse.hip, its index on an example worked by hand, and -- the point of the case table
 -- which case reaches which path of knn_reverse_kernel, so that the GPU file cannot silently test something else."""
 import os
 import re
@@ -9,7 +9,7 @@ import pytest
 
 import reverse_restatement as rr
 
-KNN_HIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mlsp_amd", "csrc", "knn.hip")
+REVERSE_HIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mlsp_amd", "csrc", "reverse.hip")
 _cache = {}
 
 
@@ -23,7 +23,7 @@ def _case(name, skip_pad):
 
 
 def test_constants_match_the_kernel_source():
-    src = open(KNN_HIP).read()
+    src = open(REVERSE_HIP).read()
     m = re.search(r"^#define RV_SPLIT_MAX (\d+)\b", src, re.M)
     assert m and int(m.group(1)) == rr.RV_SPLIT_MAX
     m = re.search(r"^#define RV_CAP \((\d+) \* (\d+)\)", src, re.M)
