@@ -672,6 +672,23 @@ int mlsp_interp3_add_bwd_f32(const float* dout, const float* dist, const int32_t
 int mlsp_cloud_mean_fwd_f32(const float* X, int B, int N, int C, float* out, mlsp_stream_t stream);
 int mlsp_cloud_mean_bwd_f32(const float* dOut, int B, int N, int C, float* dX, mlsp_stream_t stream);
 
+/* Training-batch preparation in one launch, one workgroup per cloud (PointDA/data/dataloader.py __getitem__: scale_to_unit_cube,
+ * rotate_shape, farthest_point_sample_np, random_rotate_one_axis, jitter_pointcloud).  raw [B][Nmax] rows of >= 3 floats (pitch ld);
+ * cloud b has counts[b] <= Nmax points (counts NULL: Nmax each).  Stages of cloud b, in this order:
+ *   unit cube     c = mean, r = max |x - c| in double, u = f32((x - c) / r)          unless flags[b] & 8 (the coordinates pass through)
+ *   pre-rotation  v = f32((u0 R[0][k] + u1 R[1][k]) + u2 R[2][k]) in double, R = Rpre + 9 b (row-major)           if flags[b] & 1
+ *   sampling      farthest point sampling of S points on v in fp32 from start[b] (clamped into the cloud), first index wins ties;
+ *                 S == counts[b]: nothing is sampled, idx = 0 .. S-1
+ *   post-rotation the same product with Rpost + 9 b                                                                 if flags[b] & 2
+ *   jitter        f32(f64(w) + min(max(sigma noise[b][i][k], -clip), clip))                                         if flags[b] & 4
+ * -> out [B][S][3], idx [B][S] (int32, local to the cloud).  counts and flags are HOST arrays, read during the call (flags NULL: 0);
+ * start [B], Rpre / Rpost [B][9], noise [B][S][3] are device arrays and may be NULL when no cloud's count / flags ask for them.
+ * counts[b] <= 8192 (MLSP_ERR_UNSUPPORTED beyond); S <= counts[b], non-null required operands (MLSP_ERR_ARG otherwise) -- checked for
+ * every cloud before anything is launched.  A cloud of identical points has r = 0: its output is NaN, its idx [start, 0, 0, ...]. */
+int mlsp_batch_prepare_f32(const float* raw, int ld, int B, int Nmax, const int* counts, int S, const int* flags, const int* start,
+                           const double* Rpre, const double* Rpost, const double* noise, double sigma, double clip, float* out, int* idx,
+                           mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,7 @@ SIGNATURES = {
     "mlsp_interp3_add_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mlsp_cloud_mean_fwd_f32": [_P, _I, _I, _I, _P, _P],
     "mlsp_cloud_mean_bwd_f32": [_P, _I, _I, _I, _P, _P],
+    "mlsp_batch_prepare_f32": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],

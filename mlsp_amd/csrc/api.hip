@@ -1172,4 +1172,10 @@ int mlsp_cloud_mean_bwd_f32(const float* dOut, int B, int N, int C, float* dX, m
     return launch_cloud_mean_bwd(st, dOut, B, N, C, dX);
 }
 
+int mlsp_batch_prepare_f32(const float* raw, int ld, int B, int Nmax, const int* counts, int S, const int* flags, const int* start,
+                           const double* Rpre, const double* Rpost, const double* noise, double sigma, double clip, float* out, int* idx,
+                           mlsp_stream_t st) {
+    return launch_batch_prepare(st, raw, ld, B, Nmax, counts, S, flags, start, Rpre, Rpost, noise, sigma, clip, out, idx);
+}
+
 }  // extern "C"

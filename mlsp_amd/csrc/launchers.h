@@ -319,3 +319,8 @@ int launch_interp3_add_bwd(hipStream_t st, const float* dout, const float* dist,
                            int C, float* dfeat);
 int launch_cloud_mean_fwd(hipStream_t st, const float* X, int B, int N, int C, float* out);
 int launch_cloud_mean_bwd(hipStream_t st, const float* dOut, int B, int N, int C, float* dX);
+
+// batchprep.hip
+// counts / flags: HOST arrays [B] (nullable); start / Rpre / Rpost / noise: device, nullable where no cloud's flags or count ask for them
+int launch_batch_prepare(hipStream_t st, const float* raw, int ld, int B, int Nmax, const int* counts, int S, const int* flags, const int* start,
+                         const double* Rpre, const double* Rpost, const double* noise, double sigma, double clip, float* out, int* idx);
