@@ -495,6 +495,14 @@ int mlsp_profile_classes(double* out, int ncls);
 /* out [4][4]: {ms, launches, algorithmic FLOP, algorithmic bytes} of the bracket's gemm_split_kernel launches by kind (forward, dgrad, wgrad);
  * row 3 (ABI v13): those of all kinds that ran on the two-piece f16 products (MLSP_PREC_F16X3). */
 int mlsp_profile_split_kinds(double* out);
+/* The bracket's GEMM-family launches one by one, in launch order (call after mlsp_profile_end): out [max_rows][MLSP_PROF_LAUNCH_COLS] =
+ * {M, N, K, ta, tb, K splits, tile rows, epilogue bits, split (0 | 1 = bf16 pieces | 2 = f16 pieces), extra bits, kernel family
+ * (0 FOLD64 | 1 N64 | 2 F32_EDGE | 3 F32 | 4 BF16 | 5 SPLIT), grid x, grid y, slab reducer (0-2 VEC 8 / 4 / 1 | 3 WAVE | 4 SCALAR |
+ * 5-7 UNFOLD 8 / 4 / 1; -1: one pass)}.  Returns the number of launches recorded (at most max_rows rows are written) or a negative
+ * MLSP_ERR_*.  What the tests read to assert the kernel a shape reached; it changes no kernel choice.  (Symbol added under ABI v14:
+ * a v14 library built before it lacks it, and the Python binding says so when it loads one.) */
+#define MLSP_PROF_LAUNCH_COLS 14
+int mlsp_profile_launches(int32_t* out, int max_rows);
 
 /* Adam step (PointDA/trainer.py:258-259, stepped at :571) over flat parameter / exp_avg / exp_avg_sq buffers P / M / V in ONE launch:
  * segment s covers elements [off[s], off[s] + numel[s]) of the three buffers (buffers 16-byte aligned; off % 4 == 0 takes the 16-byte path) and reads its

@@ -135,6 +135,7 @@ SIGNATURES = {
     "mlsp_profile_end": [_P],
     "mlsp_profile_classes": [_P, _I],
     "mlsp_profile_split_kinds": [_P],
+    "mlsp_profile_launches": [_P, _I],
     "mlsp_gemm_f32": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _SZ, _P],
     "mlsp_operand_bounds_next": [_P, _I],
 }
@@ -208,7 +209,11 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'`.  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)         # AttributeError if a declared symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:          # a declared symbol is not exported: a library older than this binding (symbols are added within an ABI version)
+            raise MlspLibraryError("mlsp_amd: %s does not export %s -- it was built from older sources; rebuild it (`make -C mlsp_amd/csrc`)"
+                                   % (LIB_PATH, name)) from None
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, _I)
         if _SZ in args and _P in args:

@@ -1375,34 +1375,40 @@ __global__ __launch_bounds__(256) void splitk_reduce_unfold_kernel(const float* 
 // dW (nullable; common.h GemmOpts): where the shape allows, the sums go there through the kernel above and C stays unwritten.
 // -> whether they did
 static bool launch_splitk_reduce_any(hipStream_t st, const float* slab, float* C, int M, int N, int ldc, int ns, const float* bias,
-                                     const float* gbias, int rows_per_group, float* dW = nullptr) {
-    size_t total = (size_t)M * N;
-    const bool vec = (N % 4 == 0) && ldc == N && ((((uintptr_t)slab | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)gbias) & 15) == 0);
-    if (dW && vec && !bias && !gbias && M % 2 == 0 && (((uintptr_t)dW) & 15) == 0) {
-        const size_t h4 = total / 8;
-        if (ns >= 32 && 2 * h4 <= 64 * 1024)
-            hipLaunchKernelGGL((splitk_reduce_unfold_kernel<8>), dim3((unsigned)((h4 + 31) / 32)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
-        else if (ns >= 8)
-            hipLaunchKernelGGL((splitk_reduce_unfold_kernel<4>), dim3((unsigned)((h4 + 63) / 64)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
-        else
-            hipLaunchKernelGGL((splitk_reduce_unfold_kernel<1>), dim3((unsigned)((h4 + 255) / 256)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
+                                     const float* gbias, int rows_per_group, float* dW = nullptr, int* which = nullptr) {
+    const size_t total = (size_t)M * N, t4 = total / 4, h4 = total / 8;
+    const bool aligned16 = ((((uintptr_t)slab | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)gbias) & 15) == 0);
+    const bool unfold = dW && !bias && !gbias && M % 2 == 0 && (((uintptr_t)dW) & 15) == 0;
+    const GemmReduce red = gemm_pick_reduce(M, N, ldc, ns, aligned16, unfold);          // (gemm_plan.h)
+    if (which) *which = (int)red;
+    switch (red) {
+    case GEMM_RED_UNFOLD8:
+        hipLaunchKernelGGL((splitk_reduce_unfold_kernel<8>), dim3((unsigned)((h4 + 31) / 32)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
         return true;
-    }
-    if (vec) {
-        size_t t4 = total / 4;
-        // enough workgroups to fill the chip: more slab groups per workgroup when the output is small
-        if (ns >= 32 && t4 <= 64 * 1024)
-            hipLaunchKernelGGL((splitk_reduce_vec_kernel<8>), dim3((unsigned)((t4 + 31) / 32)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
-        else if (ns >= 8)
-            hipLaunchKernelGGL((splitk_reduce_vec_kernel<4>), dim3((unsigned)((t4 + 63) / 64)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
-        else
-            hipLaunchKernelGGL((splitk_reduce_vec_kernel<1>), dim3((unsigned)((t4 + 255) / 256)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
-    } else if (ns >= 32 && total <= 256 * 1024) {
+    case GEMM_RED_UNFOLD4:
+        hipLaunchKernelGGL((splitk_reduce_unfold_kernel<4>), dim3((unsigned)((h4 + 63) / 64)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
+        return true;
+    case GEMM_RED_UNFOLD1:
+        hipLaunchKernelGGL((splitk_reduce_unfold_kernel<1>), dim3((unsigned)((h4 + 255) / 256)), dim3(256), 0, st, slab, dW, h4, N / 4, ns);
+        return true;
+    case GEMM_RED_VEC8:
+        hipLaunchKernelGGL((splitk_reduce_vec_kernel<8>), dim3((unsigned)((t4 + 31) / 32)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
+        break;
+    case GEMM_RED_VEC4:
+        hipLaunchKernelGGL((splitk_reduce_vec_kernel<4>), dim3((unsigned)((t4 + 63) / 64)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
+        break;
+    case GEMM_RED_VEC1:
+        hipLaunchKernelGGL((splitk_reduce_vec_kernel<1>), dim3((unsigned)((t4 + 255) / 256)), dim3(256), 0, st, slab, C, t4, N / 4, ns, bias, gbias, rows_per_group);
+        break;
+    case GEMM_RED_WAVE: {
         int blocks = (int)((total + 3) / 4 < 4096 ? (total + 3) / 4 : 4096);
         hipLaunchKernelGGL(splitk_reduce_wave_kernel, dim3(blocks), dim3(256), 0, st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group);
-    } else {
+        break;
+    }
+    default: {
         int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, C, M, N, ldc, ns, bias, gbias, rows_per_group);
+    }
     }
     return false;
 }
@@ -1462,7 +1468,7 @@ static struct GemmProf {
     std::vector<hipEvent_t> ev;     // pairs
     size_t used = 0;
     double flop = 0.0, bytes = 0.0;   // algorithmic: 2*M*N*K and the A + B + C bytes in their storage types
-    struct Rec { int M, N, K, ta, tb, ns, bm, fused, split, extra; };       // extra: bit 0 = the A operand is a (d', y) PAIR (DY), bit 1 = C is read too (beta = 1)
+    struct Rec { int M, N, K, ta, tb, ns, bm, fused, split, extra, family, grid_x, grid_y, reduce; };       // extra: bit 0 = the A operand is a (d', y) PAIR (DY), bit 1 = C is read too (beta = 1); family: GemmFamily; reduce: GemmReduce of the slab sum (-1: one pass)
     std::vector<Rec> rec;           // one per pair, for the MLSP_PROF_DUMP listing
 } g_prof;
 #define PROF_MAX_PAIRS 4096
@@ -1549,6 +1555,20 @@ extern "C" int mlsp_profile_classes(double* out, int ncls) {
         out[3 * c] += t; out[3 * c + 1] += 1.0; out[3 * c + 2] += g_cls.work[i];
     }
     return MLSP_OK;
+}
+
+// One row of MLSP_PROF_LAUNCH_COLS ints per GEMM-family launch of the last bracket, in launch order (the listing of MLSP_PROF_DUMP as
+// data; tests/test_gpu_gemm_variants.py asserts the kernel each shape reached): M, N, K, ta, tb, ns, bm, epilogue, split (0 / 1 = bf16
+// pieces / 2 = f16 pieces), extra, family (GemmFamily), grid_x, grid_y, reduce (GemmReduce; -1: one pass).  Call after mlsp_profile_end.
+// -> the number of launches recorded (rows written: at most max_rows), or a negative MLSP_ERR_*.
+extern "C" int mlsp_profile_launches(int32_t* out, int max_rows) {
+    if (!out || max_rows < 0 || g_prof.on) return MLSP_ERR_ARG;
+    for (size_t i = 0; i < g_prof.used && i < (size_t)max_rows; ++i) {
+        const auto& r = g_prof.rec[i];
+        const int row[MLSP_PROF_LAUNCH_COLS] = {r.M, r.N, r.K, r.ta, r.tb, r.ns, r.bm, r.fused, r.split, r.extra, r.family, r.grid_x, r.grid_y, r.reduce};
+        for (int c = 0; c < MLSP_PROF_LAUNCH_COLS; ++c) out[i * MLSP_PROF_LAUNCH_COLS + c] = row[c];
+    }
+    return (int)g_prof.used;
 }
 
 // out [4][4] = {milliseconds, launches, algorithmic FLOP, algorithmic A + B + C bytes (split-K slabs: written and read once more)} of the
@@ -1679,7 +1699,7 @@ int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int
         if (g_prof.used == used0 + 1) {              // the profiler prices the ALGORITHMIC contraction (64 x 64 x K), not the folded one
             auto& r = g_prof.rec[used0];
             g_prof.flop -= 2.0 * 128 * 128.0 * (K / 2) - 2.0 * 64 * 64.0 * K;
-            r.M = 64; r.N = 64; r.K = K;
+            r.M = 64; r.N = 64; r.K = K; r.family = (int)GEMM_FAM_FOLD64;       // (ns / bm / grid / split / reduce stay the inner launch's)
         }
         hipLaunchKernelGGL(gemm_fold64_sum_kernel, dim3(16), dim3(256), 0, st, C2, C, ldc);
         return mlsp_launch_status();
@@ -1733,8 +1753,7 @@ int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int
             if (xf && xf->which == 2) { }
             else if (grp && grp->mode == 1) { for (int g = 0; g < grp->G; ++g) need(grp->Bg[g], tb ? N / grp->G : K, tb ? K : N / grp->G, ldb); }
             else need(B, tb ? N : K, (tb ? K : N) + ((grp && grp->mode == 2) ? (int)((grp->G - 1) * grp->b_gs) : 0), ldb);
-            const double gain_us = 0.33 * (2.0 * M * N * K) / 150e6, cost_us = 3.0 + mbytes / 3e6;
-            if (mbytes > 0.0 && gain_us < cost_us) ok = false;
+            if (!gemm_pieces_measure_pays(M, N, K, mbytes)) ok = false;          // (gemm_plan.h)
         }
         if (!ok) { }
         else if (xf && xf->which == 1) ok = xf->mean && xf->invstd;
@@ -1766,12 +1785,14 @@ int launch_gemm(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, int
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
         g_prof.rec[g_prof.used] = {M, N, K, ta, tb, pl.ns, pl.bm, (o.stat_part ? 1 : 0) + (o.sel_gamma ? 2 : 0),
-                                   pl.family == GEMM_FAM_SPLIT ? (half ? 2 : 1) : 0, (dy ? 1 : 0) + (o.accumulate ? 2 : 0)};
+                                   pl.family == GEMM_FAM_SPLIT ? (half ? 2 : 1) : 0, (dy ? 1 : 0) + (o.accumulate ? 2 : 0),
+                                   (int)pl.family, (int)pl.grid_x, (int)pl.grid_y, -1};
         g_prof.used++;
         g_prof.flop += 2.0 * M * (double)N * K;
         g_prof.bytes += 4.0 * ((double)M * K + (double)K * N + (C ? (double)M * N : 0.0));
     }
-    if (pl.ns > 1 && launch_splitk_reduce_any(st, o.slab, C, M, N, ldc, pl.ns, o.bias, o.gbias, o.rows_per_group, o.unfold_dw) && o.unfolded) *o.unfolded = true;
+    if (pl.ns > 1 && launch_splitk_reduce_any(st, o.slab, C, M, N, ldc, pl.ns, o.bias, o.gbias, o.rows_per_group, o.unfold_dw, prof ? &g_prof.rec[g_prof.used - 1].reduce : nullptr) &&
+        o.unfolded) *o.unfolded = true;
     return mlsp_launch_status();
 }
 
@@ -1814,11 +1835,11 @@ int launch_gemm_mx(hipStream_t st, CallCtx& cx, bool ta, bool tb, int M, int N, 
     hipLaunchKernelGGL(kern, dim3(pl.grid_x, pl.grid_y), dim3(256), 0, st, p);
     if (prof) {
         (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st);
-        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (o.stat_part ? 1 : 0) + 4, 0, 0};
+        g_prof.rec[g_prof.used] = {M, N, K, ta, tb, ns, bm, (o.stat_part ? 1 : 0) + 4, 0, 0, (int)GEMM_FAM_BF16, (int)pl.grid_x, (int)pl.grid_y, -1};
         g_prof.used++;
         g_prof.flop += 2.0 * M * (double)N * K;
         g_prof.bytes += (a_bf16 ? 2.0 : 4.0) * M * K + (b_bf16 ? 2.0 : 4.0) * K * N + (c_bf16 ? 2.0 : 4.0) * M * N;
     }
-    if (ns > 1) launch_splitk_reduce_any(st, o.slab, (float*)C, M, N, ldc, ns, o.bias, o.gbias, o.rows_per_group);
+    if (ns > 1) launch_splitk_reduce_any(st, o.slab, (float*)C, M, N, ldc, ns, o.bias, o.gbias, o.rows_per_group, nullptr, prof ? &g_prof.rec[g_prof.used - 1].reduce : nullptr);
     return mlsp_launch_status();
 }

@@ -189,6 +189,29 @@ static inline GemmPlan gemm_plan(const GemmAsk& q) {
     return p;
 }
 
+// Which kernel sums the slabs of a split-K launch (gemm.hip launch_splitk_reduce_any follows it).  aligned16: slab, C, bias and gbias all
+// start on 16-byte boundaries; unfold: the caller offered an aligned unfold_dw (GemmOpts), the launch has no bias / gbias and M is even.
+// VEC<ZG>: 16 bytes per lane over a contiguous C, ZG slab groups per workgroup; WAVE: one wave per output element (few outputs, many
+// slabs); SCALAR: everything else (N % 4, a pitched C, a pointer 4 bytes off); UNFOLD<ZG>: VEC<ZG>'s sums written in the EdgeConv layout.
+enum GemmReduce { GEMM_RED_VEC8, GEMM_RED_VEC4, GEMM_RED_VEC1, GEMM_RED_WAVE, GEMM_RED_SCALAR, GEMM_RED_UNFOLD8, GEMM_RED_UNFOLD4, GEMM_RED_UNFOLD1 };
+static inline GemmReduce gemm_pick_reduce(int M, int N, int ldc, int ns, bool aligned16, bool unfold) {
+    const size_t total = (size_t)M * N;
+    const bool vec = N % 4 == 0 && ldc == N && aligned16;
+    if (vec) {      // enough workgroups to fill the chip: more slab groups per workgroup when the output is small
+        const int zg = (ns >= 32 && total / 4 <= 64 * 1024) ? 8 : ns >= 8 ? 4 : 1;
+        if (unfold) return zg == 8 ? GEMM_RED_UNFOLD8 : zg == 4 ? GEMM_RED_UNFOLD4 : GEMM_RED_UNFOLD1;
+        return zg == 8 ? GEMM_RED_VEC8 : zg == 4 ? GEMM_RED_VEC4 : GEMM_RED_VEC1;
+    }
+    return (ns >= 32 && total <= 256 * 1024) ? GEMM_RED_WAVE : GEMM_RED_SCALAR;
+}
+// Mode 3, a launch eligible for the two-piece f16 products (GemmPlan::pieces) whose operand bounds are not all at hand: does MEASURING
+// `mbytes` bytes of operands pay?  The three-product kernel saves about a third of the six-product launch (~150 TF on these shapes); a
+// measuring pass streams the operand at ~3 TB/s plus a launch.  Nothing to measure: it pays.
+static inline bool gemm_pieces_measure_pays(int M, int N, int K, double mbytes) {
+    const double gain_us = 0.33 * (2.0 * M * N * K) / 150e6, cost_us = 3.0 + mbytes / 3e6;
+    return !(mbytes > 0.0 && gain_us < cost_us);
+}
+
 // ---- the shape queries of launchers.h as statements over the plan of a launch of that shape with its slab and no `accumulate`
 // (gemm.hip binds them to a CallCtx and to the operands' alignment; q: that shape's ask with no option set and slab_floats = (size_t)-1)
 static inline GemmPlan gemm_q_tiles(int mode, int M, int N, int K) { GemmPlan t; gemm_plan_tiles(t, mode, M, N, K, (size_t)-1, false); return t; }

@@ -2494,15 +2494,36 @@ def cloud_mean(X, B, N):
     return _CloudMean.apply(X, int(B), int(N))
 
 
-def gemm(A, B, ta=False, tb=False, bias=None):
-    """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests."""
+def _gemm_row_view(t):
+    """t itself where the kernels can read it in place -- a 2-D row view with unit column stride and a pitch of at least the row length --
+    else a contiguous copy"""
+    if t.dim() == 2 and t.shape[0] > 1 and t.shape[1] > 1 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t
+    return t.contiguous()
+
+
+def gemm(A, B, ta=False, tb=False, bias=None, out=None):
+    """Plain fp32 GEMM on the matrix cores: opA(A) @ opB(B) (+bias).  No autograd; used by tests.  A and B may be row views (unit column
+    stride, any pitch >= the row length, any 4-byte aligned start): they are read in place, so a test reaches the kernels' scalar-load and
+    pitched paths.  out (optional): a [M][N] fp32 row view on A's device to write into, with unit column stride, any pitch >= N (the launch's
+    ldc) and a start on a 16-byte boundary, sharing no storage with A, B or bias; returned."""
     lib = _lib.load()
-    A, B = A.contiguous(), B.contiguous()
-    _lib.require_gpu(A, B)
+    A, B = _gemm_row_view(A), _gemm_row_view(B)
+    _lib.require_gpu(A, B, bias, out)
     M, K = (A.shape[1], A.shape[0]) if ta else A.shape
     N = B.shape[0] if tb else B.shape[1]
-    C = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    if out is None:
+        C = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    else:
+        C = out
+        if C.dtype != torch.float32 or tuple(C.shape) != (M, N) or (N > 1 and C.stride(1) != 1) or (M > 1 and C.stride(0) < N):
+            raise ValueError("gemm: out must be a [%d][%d] fp32 row view with unit column stride" % (M, N))
+        if C.device != A.device or C.data_ptr() % 16:
+            raise ValueError("gemm: out must be on the operands' device and start on a 16-byte boundary")
+        if any(t is not None and t.untyped_storage().data_ptr() == C.untyped_storage().data_ptr() for t in (A, B, bias)):
+            raise ValueError("gemm: out shares its storage with an operand")
+    lda, ldb, ldc = (max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1] for t in (A, B, C))
     ws, wsn = _lib.workspace(A.device, max(M, 1), max(K, 1), max(N, 1))
-    _lib.check(lib.mlsp_gemm_f32(int(ta), int(tb), M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
-                                 C.data_ptr(), N, _lib.ptr(bias), gemm_precision.code(), ws, wsn, _lib.stream()), "mlsp_gemm_f32")
+    _lib.check(lib.mlsp_gemm_f32(int(ta), int(tb), M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb,
+                                 C.data_ptr(), ldc, _lib.ptr(bias), gemm_precision.code(), ws, wsn, _lib.stream()), "mlsp_gemm_f32")
     return C

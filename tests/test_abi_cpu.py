@@ -41,6 +41,10 @@ def test_library_exports_every_declared_symbol():
     assert lib.mlsp_abi_version() == _lib.ABI_VERSION == 14
     assert b"workspace" in lib.mlsp_strerror(-2)
     assert lib.mlsp_workspace_bytes(32768, 512, 1024) > 32768 * 1024 * 4
+    # the per-launch read-out of the measurement hook: a row is MLSP_PROF_LAUNCH_COLS ints, a null table is an argument error
+    header = open(os.path.join(ROOT, "include", "mlsp_hip.h")).read()
+    assert "#define MLSP_PROF_LAUNCH_COLS 14" in header and protos["mlsp_profile_launches"][1] == 2
+    assert lib.mlsp_profile_launches(None, 0) == -1
 
 
 def test_reference_api_surface_cpu():

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_shapes
 import golden_common as gc
 import knn_shapes
 from oracle import knn_canon, ref_cpu, ref_torch_modules
@@ -201,12 +202,7 @@ def test_knn_public_api_and_errors(dev):
 
 
 # ----------------------------------------------------------------------------- GEMM
-@pytest.mark.parametrize("ta,tb,M,N,K", [(0, 1, 300, 200, 64), (0, 1, 1024, 128, 3), (0, 0, 257, 130, 100),
-                                         (1, 0, 64, 6, 5000), (1, 0, 256, 512, 4096), (0, 1, 32, 512, 1024),
-                                         (0, 1, 4096, 2048, 512), (1, 1, 100, 70, 50), (0, 1, 5, 9, 256),
-                                         # skinny.hip: <= 32 rows (fwd / dgrad) and 32-deep wgrads, ragged edges
-                                         (0, 1, 32, 256, 1024), (0, 1, 17, 33, 100), (0, 0, 32, 1024, 256), (0, 0, 7, 50, 9),
-                                         (1, 0, 256, 1024, 32), (1, 0, 9, 256, 20), (1, 0, 70, 33, 3)])
+@pytest.mark.parametrize("ta,tb,M,N,K", gemm_shapes.shapes("test_gemm"))      # (each with the kernel it reaches: gemm_shapes.py)
 def test_gemm(dev, ta, tb, M, N, K):
     Fh = _fh()
     A = _rand((K, M) if ta else (M, K), 1)
@@ -217,8 +213,7 @@ def test_gemm(dev, ta, tb, M, N, K):
     assert err < 2e-6 * K ** 0.5 * 4 + 1e-6, err
 
 
-@pytest.mark.parametrize("ta,tb,M,N,K", [(0, 1, 1024, 256, 512), (0, 0, 512, 384, 256), (1, 0, 256, 128, 8192), (0, 1, 4096, 128, 64),
-                                         (1, 1, 256, 256, 128), (0, 1, 300, 200, 64)])
+@pytest.mark.parametrize("ta,tb,M,N,K", gemm_shapes.shapes("test_gemm_bf16_operand_mode"))
 def test_gemm_bf16_operand_mode(dev, ta, tb, M, N, K):
     """gemm_precision("bf16") (MLSP_PREC_BF16 per call): operands rounded to bf16 (RNE), fp32 accumulation -- compared with that exact model in
     float64; shapes off the fast path (last case) keep using the fp32 kernel.  The switch is restored afterwards."""
@@ -242,10 +237,7 @@ def test_gemm_bf16_operand_mode(dev, ta, tb, M, N, K):
     assert (again - opA.double() @ opB.double()).abs().max().item() < 2e-6 * K ** 0.5 * 4 + 1e-6
 
 
-@pytest.mark.parametrize("ta,tb,M,N,K,bias", [(0, 1, 4096, 128, 3, 0), (0, 0, 4096, 128, 3, 0), (0, 0, 2048, 256, 16, 0), (0, 1, 4096, 3, 128, 0),
-                                              (0, 1, 4096, 16, 256, 1), (0, 0, 4096, 3, 128, 0), (1, 0, 3, 128, 4096, 0),
-                                              (1, 0, 16, 256, 8192, 0), (1, 0, 128, 3, 4096, 0), (1, 0, 256, 16, 2048, 0), (1, 0, 64, 3, 8192, 0), (1, 0, 3, 64, 8192, 0),
-                                              (0, 1, 32768, 128, 3, 1), (1, 0, 3, 128, 32768, 0)])
+@pytest.mark.parametrize("ta,tb,M,N,K,bias", gemm_shapes.shapes("test_thin_gemms", bias=True))
 def test_thin_gemms(dev, ta, tb, M, N, K, bias):
     """One tiny dimension (3 coordinates, 3 / 16 outputs): the streaming VALU kernels of thin.hip behind mlsp_gemm_f32."""
     Fh = _fh()
@@ -266,6 +258,8 @@ def test_gemm_matches_fma_chain_bitwise(dev):
     """The f32 MFMA is a fmaf chain in issue order (what makes the MFMA kNN canonical).  The GEMM kernel feeds K in
     groups of four as (4m, 4m+2, 4m+1, 4m+3) -- see gemm.hip -- so emulate exactly that chain and compare bitwise."""
     Fh = _fh()
+    (_, _, M, N, K), = gemm_shapes.shapes("test_gemm_matches_fma_chain_bitwise")
+    assert (M, N, K) == (64, 40, 24)
     A, B = _rand((64, 24), 3), _rand((40, 24), 4)
     got = Fh.gemm(A.to(dev), B.to(dev), tb=True).cpu().numpy()
     want = np.zeros((64, 40), np.float32)
@@ -278,10 +272,7 @@ def test_gemm_matches_fma_chain_bitwise(dev):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("ta,tb,M,N,K", [(False, True, 32768, 256, 512), (False, False, 32768, 512, 256), (True, False, 512, 256, 32768),
-                                          (False, True, 4096, 1024, 128), (False, True, 32768, 1024, 512), (False, False, 65536, 1024, 128),
-                                          (True, True, 256, 256, 16384), (True, False, 1024, 512, 32768), (True, False, 2048, 2048, 512),
-                                          (True, True, 2048, 2560, 256), (False, False, 2048, 2048, 512)])
+@pytest.mark.parametrize("ta,tb,M,N,K", [(bool(ta), bool(tb), M, N, K) for ta, tb, M, N, K in gemm_shapes.shapes("test_gemm_split_bf16_accuracy")])
 @pytest.mark.parametrize("mode,scale", [("bf16x6", 1.0), ("f16x3", 1.0), ("f16x3", 1e-6), ("f16x3", 3e5)])
 def test_gemm_split_bf16_accuracy(dev, ta, tb, M, N, K, mode, scale):
     """gemm_precision("bf16x6"): products as six bf16 piece products on the bf16 matrix cores; gemm_precision("f16x3"): as THREE f16 piece
@@ -289,9 +280,11 @@ def test_gemm_split_bf16_accuracy(dev, ta, tb, M, N, K, mode, scale):
     with the operands at 1e-6 and 3e5 of their size: the scale, not the f16 range, decides).  The bar is the same for both.
     Against float64 its error must be at the
     level of the exact-fp32 MFMA kernel's (both are fp32 accumulations of products exact to <= 2^-25): <= 2x that error and
-    <= 2e-6 relative L2 on random operands with a wide dynamic range.  The shapes cover both tile heights (64 / 128 rows), split-K, and
-    all four operand layouts (row-major images read with ds_read_b128, k-major images read with ds_read_b64_tr_b16), the last three with a
-    k-major / row-major A operand on the 64-row tile (256-511 tiles of 128 rows, no split-K)."""
+    <= 2e-6 relative L2 on random operands with a wide dynamic range.  The shapes (gemm_shapes.py, each with the kernel it reaches) cover
+    both tile heights (64 / 128 rows), split-K, and all four operand layouts (row-major images read with ds_read_b128, k-major images
+    read with ds_read_b64_tr_b16), the last three with a k-major / row-major A operand on the 64-row tile (256-511 tiles of 128 rows, no
+    split-K).  In mode "f16x3" the launcher keeps (32768, 256, 512), (512, 256, 32768), (4096, 1024, 128) and (256, 256, 16384) on the six
+    bf16 products (measuring their operands does not pay): the rows labelled pieces:six; tests/test_gpu_gemm_variants.py asserts which ran."""
     Fh = _fh()
     g = torch.Generator().manual_seed(11)
     shpA, shpB = ((K, M) if ta else (M, K)), ((N, K) if tb else (K, N))
@@ -317,7 +310,8 @@ def test_gemm_split_short_k_stays_on_fp32_kernel(dev):
     """K loops of fewer than 4 tiles (8 when N < 256) lose on the split kernel's prologue: mode "bf16x6" keeps them on the f32 MFMA kernel,
     bit for bit."""
     Fh = _fh()
-    for M, N, K in ((16384, 128, 64), (4096, 128, 128), (1024, 512, 96)):
+    for ta, tb, M, N, K in gemm_shapes.shapes("test_gemm_split_short_k_stays_on_fp32_kernel"):
+        assert (ta, tb) == (0, 1)
         A, B = _rand((M, K), 3).to(dev), _rand((N, K), 4).to(dev)
         with Fh.gemm_precision("fp32"):
             want = Fh.gemm(A, B, False, True)
@@ -332,7 +326,8 @@ def test_precision_is_per_call_two_threads_and_late_backward(dev):
     `with gemm_precision(...)` block has exited uses the forward's products (the mode travels in the autograd context)."""
     import threading
     Fh = _fh()
-    M, Cin, Cout = 32768, 256, 256        # (enough tiles that K is not split: the K = 256 loop then runs on the split kernel in mode "bf16x6")
+    (_, _, M, Cout, Cin), = gemm_shapes.shapes("test_precision_is_per_call_two_threads_and_late_backward")      # 32768 x 256 x 256
+    # (enough tiles that K is not split: the K = 256 loop then runs on the split kernel in mode "bf16x6")
     X = _rand((M, Cin), 31).to(dev)
     W = _rand((Cout, Cin), 32).to(dev)
     gamma, beta = (_rand((Cout,), 33).abs() + 0.5).to(dev), _rand((Cout,), 34).to(dev)
@@ -1656,7 +1651,9 @@ def test_gemm_fold64_weight_gradient(dev):
     in both product modes, and the non-foldable neighbours (pitch != 64, short K) keep their old path."""
     Fh = _fh()
     g = torch.Generator().manual_seed(5)
-    for K in (8192, 65536, 524288):
+    folded = gemm_shapes.shapes("test_gemm_fold64_weight_gradient")
+    assert [s[:4] for s in folded] == [(1, 0, 64, 64)] * 3
+    for K in (s[4] for s in folded):                                       # 8192, 65536, 524288
         A, B = torch.randn(K, 64, generator=g).to(dev), torch.randn(K, 64, generator=g).to(dev)
         ref = A.double().t() @ B.double()
         for mode in ("fp32", "bf16x6"):
@@ -1664,8 +1661,10 @@ def test_gemm_fold64_weight_gradient(dev):
                 got = Fh.gemm(A, B, True, False).double()
             rel = ((got - ref).norm() / ref.norm()).item()
             assert rel < 2e-6, (K, mode, rel)
+    pitched = gemm_shapes.TESTS["test_gemm_fold64_weight_gradient"][-1]
+    assert (pitched.K, gemm_shapes.pitches(pitched)[0]) == (8192, 96)
     A, B = torch.randn(8192, 96, generator=g).to(dev), torch.randn(8192, 64, generator=g).to(dev)
-    got = Fh.gemm(A[:, :64], B, True, False).double()                      # pitch 96: not foldable
+    got = Fh.gemm(A[:, :64], B, True, False).double()                      # pitch 96 (read in place): not foldable
     assert ((got - A[:, :64].double().t() @ B.double()).norm() / got.norm()).item() < 2e-6
 
 
@@ -1674,7 +1673,9 @@ def test_gemm_split_layouts_agree_and_are_linear(dev):
     images read with ds_read_b64_tr_b16, in either operand) compute the same product to fp32 accuracy, and the kernel is linear in an
     operand (C(A1 + A2, B) = C(A1, B) + C(A2, B) to fp32 accuracy; exactly so for a power-of-two scale)."""
     Fh = _fh()
-    M, N, K = 32768, 512, 1024
+    layouts = gemm_shapes.shapes("test_gemm_split_layouts_agree_and_are_linear")
+    (M, N, K), = {s[2:] for s in layouts}                                   # 32768 x 512 x 1024
+    assert sorted(s[:2] for s in layouts) == [(0, 0), (0, 1), (1, 0), (1, 1)]
     A, B = _rand((M, K), 21).to(dev), _rand((N, K), 22).to(dev)
     At, Bt = A.t().contiguous(), B.t().contiguous()
     with Fh.gemm_precision("bf16x6"):

@@ -1,17 +1,28 @@
 // Host check of the GEMM dispatch plan (mlsp_amd/csrc/gemm_plan.h): the one function that decides what a launch of a given shape does,
-// and the shape queries that are statements over it.  Three parts:
+// and the shape queries that are statements over it.  Five parts:
 //   agreement  over a grid of shapes x layouts x pitches x product modes, a query that says yes implies a launchable plan with that option
 //              set; where the logic inherited from before the plan disagrees with itself, the shapes are listed below, by value;
 //   pins       the plan of every GEMM launch of one BASELINE configs[1] step and one configs[4] step, as the library listed them on an
 //              MI355X (MLSP_PROF_DUMP, tools/r6/gemm_dump.py and tools/time_config4.py) before the plan existed;
-//   corners    the folded 64 x 64 weight gradient and the N = 64 kernel, by hand.
+//   corners    the folded 64 x 64 weight gradient and the N = 64 kernel, by hand;
+//   reach      one "reach p<prec>:<label> <- ta tb M N K bias" line (the smallest such product) per distinct label that plain and bias launches of a grid of shapes meet, as mlsp_gemm_f32 makes
+//              them (contiguous operands, the slab at hand, no operand bound at hand), up to the largest product the tests launch;
+//   plans      one "plan" line per line of stdin
+//                  `prec ta tb M N K lda ldb ldc a16 b16 bias bias_a4 bias_a16 slab_floats`   (slab_floats -1: whatever the launch asks)
+//              (tests/test_gemm_plan_cpu.py pins the kernel each test shape reaches with them).
+// Labels: FAMILY/bm/ns=<n>/xcd=<m>[/fast][/pieces | /pieces:six][/thin?][/skinny?] -- pieces: mode 3 and eligible for the two-piece f16
+// products; ":six": measuring both operands does not pay (gemm_pieces_measure_pays), so the launch stays on the six bf16 products;
+// thin? / skinny?: thin.hip / skinny.hip are offered the launch first.  FOLD64:<label of the 128 x 128 x K/2 launch it runs>.  A plan line
+// of a split-K launch names the kernel that sums its slabs.
 // A stand-alone program that needs no GPU and no HIP header:
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/gemm_plan_host_check/main.cpp
-//       -o build/gemm_plan_host_check && build/gemm_plan_host_check
+//       -o build/gemm_plan_host_check && build/gemm_plan_host_check < /dev/null
 #include "../../mlsp_amd/csrc/gemm_plan.h"
 #include <initializer_list>
+#include <map>
 #include <stdio.h>
+#include <string>
 
 
 static int fails = 0;
@@ -292,10 +303,91 @@ static void pins() {
     EXPECT(n == 34 + 47);
 }
 
+// ---- labels, reach, plans ---------------------------------------------------------------------------------------------------------
+static const char* const FAMILY_NAMES[] = {"FOLD64", "N64", "F32_EDGE", "F32", "BF16", "SPLIT"};
+static const char* const REDUCE_NAMES[] = {"VEC8", "VEC4", "VEC1", "WAVE", "SCALAR", "UNFOLD8", "UNFOLD4", "UNFOLD1"};
+
+// the 128 x 128 x K/2 launch a folded 64 x 64 weight gradient runs (gemm.hip launch_gemm): A^T B at pitch 128, its own slab, no bias
+static GemmAsk fold_inner(const GemmAsk& q) {
+    GemmAsk in = q;
+    in.M = in.N = 128; in.K = q.K / 2; in.lda = in.ldb = in.ldc = 128; in.bias = false;
+    in.slab_floats = gemm_q_slab_floats(128, 128, q.K / 2);
+    return in;
+}
+static std::string label(const GemmAsk& q, const GemmPlan& p) {
+    if (p.family == GEMM_FAM_FOLD64 && p.status == MLSP_OK) { const GemmAsk in = fold_inner(q); return "FOLD64:" + label(in, gemm_plan(in)); }
+    std::string s;
+    if (p.status != MLSP_OK) s = p.status == MLSP_ERR_ARG ? "ERR_ARG" : "ERR_UNSUPPORTED";
+    else {
+        s = std::string(FAMILY_NAMES[p.family]) + "/" + std::to_string(p.bm) + "/ns=" + std::to_string(p.ns) + "/xcd=" + std::to_string(p.xcd_map);
+        if (p.fast) s += "/fast";
+        // (mlsp_gemm_f32 finds no bound at hand: both operands as they lie in memory would be measured)
+        if (p.pieces) s += gemm_pieces_measure_pays(q.M, q.N, q.K, 4.0 * ((double)q.M * q.K + (double)q.K * q.N)) ? "/pieces" : "/pieces:six";
+    }
+    if (p.offer_thin) s += "/thin?";
+    if (p.offer_skinny) s += "/skinny?";
+    return s;
+}
+// the slab sum of a launch through mlsp_gemm_f32 (slab and C on 16-byte boundaries, no unfold_dw); null: one pass
+static const char* reducer(const GemmAsk& q, const GemmPlan& p, bool bias_a16) {
+    if (p.status != MLSP_OK) return nullptr;
+    if (p.family == GEMM_FAM_FOLD64) { const GemmAsk in = fold_inner(q); return reducer(in, gemm_plan(in), true); }
+    return p.ns > 1 ? REDUCE_NAMES[gemm_pick_reduce(q.M, q.N, q.ldc, p.ns, !q.bias || bias_a16, false)] : nullptr;
+}
+
+// Shapes for the reach lines: every threshold of gemm_pick_split / gemm_pick_bm / gemm_split_pays / xcd_map / N64 / FOLD64 / the skinny
+// offer from both sides, every count of 128-row panels below 16 (where xcd_map and the tile height turn) against wide N, up to
+// M N K = 2^34 + 2^32 (the largest product the tests launch: 4096 x 2048 x 512 and 65536 x 1024 x 128 are 2^32 and 2^33).  Contiguous
+// operands, as functional.gemm passes them unless told otherwise.
+static void reach() {
+    static const int Ms[] = {1, 32, 33, 64, 100, 128, 192, 256, 320, 384, 512, 640, 768, 896, 960, 1024, 1152, 1280, 1408, 1536, 1664, 1792, 1920, 2048, 4096, 16384, 32768, 65536};
+    static const int Ns[] = {3, 16, 32, 64, 100, 128, 192, 256, 512, 1024, 1408, 1664, 2048, 2560, 4096, 4608, 4736, 8192, 16384};
+    static const int Ks[] = {3, 32, 64, 96, 100, 128, 256, 512, 1024, 2048, 8192, 16384, 32768, 65536, 524288};
+    std::map<std::string, std::string> seen;        // label -> the smallest product that meets it: "ta tb M N K bias"
+    std::map<std::string, double> size;
+    long points = 0;
+    for (int prec = 0; prec < 4; ++prec) for (int M : Ms) for (int N : Ns) for (int K : Ks) for (int t = 0; t < 4; ++t) for (int bias = 0; bias < 2; ++bias) {
+        if ((double)M * N * K > 17179869184.0 + 4294967296.0) continue;
+        GemmAsk q = bare(prec, t & 1, t & 2, M, N, K, 0);
+        q.bias = bias; q.slab_floats = gemm_q_slab_floats(M, N, K);
+        const GemmPlan p = gemm_plan(q);
+        ++points;
+        EXPECT(p.status == MLSP_OK);
+        const std::string l = "p" + std::to_string(prec) + ":" + label(q, p);
+        const double mnk = (double)M * N * K;
+        if (!seen.count(l) || mnk < size[l]) {
+            size[l] = mnk;
+            seen[l] = std::to_string(t & 1) + " " + std::to_string((t & 2) / 2) + " " + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(K) + " " + std::to_string(bias);
+        }
+    }
+    for (const auto& s : seen) printf("reach %s <- %s\n", s.first.c_str(), s.second.c_str());
+    printf("reach: %ld points, %zu labels\n", points, seen.size());
+    EXPECT(seen.size() >= 40);
+}
+
+static void plans() {
+    int prec, ta, tb, a16, b16, bias, bias_a4, bias_a16;
+    long long slab;
+    GemmAsk q;
+    while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %lld", &prec, &ta, &tb, &q.M, &q.N, &q.K, &q.lda, &q.ldb, &q.ldc, &a16, &b16, &bias, &bias_a4, &bias_a16,
+                 &slab) == 15) {
+        if (prec < 0 || prec > 3) { printf("plan: precision %d?\n", prec); ++fails; continue; }
+        q.mode = prec == 3 ? 2 : prec; q.split_half = prec == 3;
+        q.ta = ta; q.tb = tb; q.a16 = a16; q.b16 = b16; q.bias = bias; q.bias_a4 = bias_a4;
+        q.slab_floats = slab < 0 ? gemm_q_slab_floats(q.M, q.N, q.K) : (size_t)slab;
+        const GemmPlan p = gemm_plan(q);
+        const char* red = reducer(q, p, bias_a16 != 0);
+        printf("plan %d %d %d %d %d %d -> %s grid %u,%u vec %d%d reduce %s\n", prec, ta, tb, q.M, q.N, q.K, label(q, p).c_str(), p.grid_x, p.grid_y, (int)p.a_vec,
+               (int)p.b_vec, red ? red : "-");
+    }
+}
+
 int main() {
     agreement();
     pins();
     corners();
+    reach();
+    plans();
     if (fails) { printf("gemm_plan_host_check: %d FAILED\n", fails); return 1; }
     printf("gemm_plan_host_check: ok\n");
     return 0;
