@@ -102,7 +102,8 @@ int mlsp_graph_feature_bwd_f32(const float* dF, const int32_t* rev_off, const in
 
 /* Fused EdgeConv block = get_graph_feature + conv_2d (1x1 Conv2d bias=False + BatchNorm2d + act) + max over k:
  * PointDA/model_utils.py:18-63 with PointDA/Models.py:115-129.  Algebraically folded (edge.hip).
- * W [Cout][2C] in the reference's Conv2d layout.  Saved for backward: uv [P][2Cout], msel [P][Cout],
+ * W [Cout][2C] in the reference's Conv2d layout.  Saved for backward: uv [P][2Cout], msel [P][Cout] (the selected edge's
+ * pre-BatchNorm value y = v_i + the extreme of u_j over the neighbours: the sum, not the extreme alone),
  * argsel [P][Cout] u8, s1 [P][Cout], bn_save [4][Cout].  out (row pitch ldo >= Cout) and dOut (row pitch lddo) may be column
  * slices of a wider matrix: the four EdgeConv outputs are written straight into the [P][512] concatenation of
  * PointDA/Models.py:131 (no torch.cat pass) and its gradient is read in place.

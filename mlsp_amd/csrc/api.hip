@@ -204,7 +204,7 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
         CHECK(launch_build_wd_eval(st, W, Cout, C, Wd, Cout, gamma, beta, run_mean, run_var, bn_save, 0, nullptr, nullptr, nullptr, nullptr, nullptr, eps));
     } else CHECK(launch_build_wd(st, W, Cout, C, Wd, (C >= 128 && C % 32 == 0 && build_wd_leaves_bound(Cout, C)) ? cx.reserve(Wd, 2 * Cout, C, C) : nullptr));   // (mode 3: the fold leaves the bound of what it writes)
     CHECK(launch_gemm(st, cx, false, true, P, 2 * Cout, C, x, ldx, Wd, C, uv, 2 * Cout, so));
-    {   // the neighbour gather + max/min + BN sums: compulsory bytes = u half + indices in, msel + s1 + arg slot out
+    {   // the neighbour gather + max/min + BN sums: compulsory bytes = u half + indices in, ysel (`msel`: v + the extreme) + s1 + arg slot out
         const int tok = prof_cls_begin(st, MLSP_PROF_EDGE_REDUCE);
         const int rc = launch_edge_reduce(st, uv, idx, gamma, P, N, Cout, k, msel, argsel, s1, part, &nparts);
         prof_cls_end(st, tok, (double)P * (Cout * 4.0 + k * 4.0 + Cout * 9.0));
@@ -216,7 +216,7 @@ int mlsp_edgeconv_fwd_f32(const float* x, int ldx, const int32_t* idx, const flo
         CHECK(launch_bn_finalize(st, part, nparts, (double)P * k, Cout, gamma, beta, run_mean, run_var, momentum, eps, scale,
                                  shift, mean, invstd, cx.offered_output(out, P, Cout, ldo, Cout)));
     }
-    CHECK(launch_edge_select_act(st, msel, uv, P, Cout, scale, shift, act, slope, out, ldo));
+    CHECK(launch_edge_select_act(st, msel, P, Cout, scale, shift, act, slope, out, ldo));
     return MLSP_OK;
 }
 
@@ -247,14 +247,18 @@ int mlsp_edgeconv_bwd_f32(const float* dOut, int lddo, const float* x, int ldx, 
     // f16x3: the passes that write duv leave its bound (256 partial maxima in a slot of the workspace tail, found again by both products
     // below) instead of a measuring pass over the finished tensor
     // (only where those products can take the two-piece kernel at all: C a multiple of its 128-column tile -- conv4 of the DGCNN encoder)
-    float* duv_amax = (C % 128 == 0 && edge_bwd_leaves_duv_bound(dOut, out, msel, uv, s1, argsel, Cout, scale, mean, invstd, gz, duv, lddo, ldo))
-                          ? cx.reserve(duv, P, 2 * Cout, 2 * Cout) : nullptr;
-    CHECK(launch_edge_bwd_reduce(st, dOut, out, msel, uv, P, Cout, mean, invstd, act, slope, part, lddo, ldo, duv_amax));
-    CHECK(launch_bn_bwd_finalize(st, part, edge_bwd_reduce_parts(P, Cout, dOut, out, msel, uv, mean, invstd, lddo, ldo), (double)P * k, Cout,
+    // all three passes vectorised: the reduce stores gz on its way (it needs no batch mean) and the gather, which owns destination j, writes
+    // dv_j beside du_j -- the point pass, 4 reads and 2 writes of a [P, Cout] tensor for those two outputs, is not launched
+    const bool fused = edge_bwd_leaves_duv_bound(dOut, out, msel, uv, s1, argsel, Cout, scale, mean, invstd, gz, duv, lddo, ldo);
+    float* duv_amax = (C % 128 == 0 && fused) ? cx.reserve(duv, P, 2 * Cout, 2 * Cout) : nullptr;
+    CHECK(launch_edge_bwd_reduce(st, dOut, out, msel, P, Cout, scale, mean, invstd, act, slope, part, lddo, ldo, fused ? gz : nullptr, duv_amax));
+    CHECK(launch_bn_bwd_finalize(st, part, edge_bwd_reduce_parts(P, Cout, dOut, out, msel, mean, invstd, lddo, ldo), (double)P * k, Cout,
                                  dgamma, dbeta, mean_dz, mean_dzy));
     const float* mdz = training ? mean_dz : nullptr;
-    CHECK(launch_edge_bwd_point(st, dOut, out, uv, s1, P, Cout, k, scale, mean, invstd, mdz, mean_dzy, act, slope, gz, duv, lddo, ldo, duv_amax));
-    CHECK(launch_edge_bwd_gather(st, gz, argsel, uv, rev_off, rev_ent, P, N, Cout, scale, mean, invstd, mdz, mean_dzy, duv, duv_amax));
+    if (!fused)
+        CHECK(launch_edge_bwd_point(st, dOut, out, uv, s1, P, Cout, k, scale, mean, invstd, mdz, mean_dzy, act, slope, gz, duv, lddo, ldo, duv_amax));
+    CHECK(launch_edge_bwd_gather(st, gz, argsel, uv, fused ? s1 : nullptr, k, rev_off, rev_ent, P, N, Cout, scale, mean, invstd, mdz, mean_dzy,
+                                 duv, duv_amax));
     // (the forward's [Wa ; Wb - Wa] is reused when the caller kept it; beta = 1: dx is added into a slice of a wider gradient)
     const float* Wdc = Wd_in;
     if (!Wdc && dx) { CHECK(launch_build_wd(st, W, Cout, C, Wd)); Wdc = Wd; }
@@ -282,8 +286,6 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
     const int P = B * N;
     Workspace w(ws, ws_bytes);
     float* Wd = w.take<float>((size_t)2 * C1 * C);
-    float* msel = w.take<float>((size_t)P * C1);
-    uint8_t* arg1 = w.take<uint8_t>((size_t)P * C1);
     int np1 = edge_reduce_parts(P), np2 = tnet_fwd_parts(B, N, k);
     double* part = w.take<double>((size_t)(np1 > np2 ? np1 : np2) * 2 * C2);
     GemmOpts so; take_slab(w, so, gemm_slab_floats(P, 2 * C1, C));
@@ -293,7 +295,7 @@ int mlsp_tnet_edge_fwd_f32(const float* x, int ldx, const int32_t* idx, const fl
         CHECK(launch_build_wd_eval(st, W1, C1, C, Wd, C1, gamma1, beta1, run_mean1, run_var1, bn1_save, C2, gamma2, beta2, run_mean2, run_var2, bn2_save, eps));
     } else CHECK(launch_build_wd(st, W1, C1, C, Wd));
     CHECK(launch_gemm(st, cx, false, true, P, 2 * C1, C, x, ldx, Wd, C, uv, 2 * C1, so));
-    CHECK(launch_edge_reduce(st, uv, idx, gamma1, P, N, C1, k, msel, arg1, s1, part, &np1));
+    CHECK(launch_edge_reduce(st, uv, idx, gamma1, P, N, C1, k, nullptr, nullptr, s1, part, &np1));     // (this stage reads s1 and the statistics only)
     if (training) {
         CHECK(launch_bn_finalize(st, part, np1, (double)P * k, C1, gamma1, beta1, run_mean1, run_var1, momentum, eps, bn1_save,
                                  bn1_save + C1, bn1_save + 2 * C1, bn1_save + 3 * C1));

@@ -69,10 +69,13 @@ __global__ void unbuild_wd_kernel(const float* __restrict__ dWd, int Cout, int C
     dW[(size_t)o * 2 * C + C + c] = dv;
 }
 
-// per point: selected extreme of u over the neighbours, its slot, s1; per channel: partial sums of y and y^2
+// per point: ysel = v + the selected extreme of u over the neighbours (the selected edge's y: what every consumer of the extreme adds v
+// to -- stored as the sum, one rounding either way), its slot, s1; per channel: partial sums of y and y^2.  ysel and argsel may be null
+// together: the T-Net's first stage only needs s1 and the statistics.  The same holds for the three kernels below (here and in the
+// vectorised form a uniform branch, in the LDS forms a template flag).
 __global__ __launch_bounds__(256) void edge_reduce_kernel(const float* __restrict__ uv, const int* __restrict__ idx,
                                                           const float* __restrict__ gamma, int P, int N, int Cout, int k,
-                                                          float* __restrict__ msel, uint8_t* __restrict__ argsel,
+                                                          float* __restrict__ ysel, uint8_t* __restrict__ argsel,
                                                           float* __restrict__ s1out, double* __restrict__ part) {
     extern __shared__ double shd[];   // [2][4][Cout]
     const int lane = threadIdx.x & 63;
@@ -97,8 +100,10 @@ __global__ __launch_bounds__(256) void edge_reduce_kernel(const float* __restric
                 best = take ? u : best; bs = take ? s : bs;
             }
             float v = uv[(size_t)i * ld + Cout + c];
-            msel[(size_t)i * Cout + c] = best;
-            argsel[(size_t)i * Cout + c] = (uint8_t)bs;
+            if (ysel) {
+                ysel[(size_t)i * Cout + c] = best + v;
+                argsel[(size_t)i * Cout + c] = (uint8_t)bs;
+            }
             s1out[(size_t)i * Cout + c] = s1;
             ps += (double)s1 + (double)k * v;
             pq += (double)s2 + 2.0 * (double)v * s1 + (double)k * v * v;
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(256) void edge_reduce_kernel(const float* __restric
 template <int LR>
 __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __restrict__ uv, const int* __restrict__ idx,
                                                               const float* __restrict__ gamma, int P, int N, int k,
-                                                              float* __restrict__ msel, uint8_t* __restrict__ argsel,
+                                                              float* __restrict__ ysel, uint8_t* __restrict__ argsel,
                                                               float* __restrict__ s1out, double* __restrict__ part) {
     constexpr int Cout = LR * 4, NP = 64 / LR;
     __shared__ double shd[2][4][Cout];
@@ -187,13 +192,15 @@ __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __res
             uint32_t a4 = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                b4[e] = best[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);
+                b4[e] = best[e] + v[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);
                 ps[e] += (double)s1[e] + (double)k * v[e];
                 pq[e] += (double)s2[e] + 2.0 * (double)v[e] * s1[e] + (double)k * v[e] * v[e];
             }
-            *(f32x4*)(msel + (size_t)i * Cout + c) = b4;
             *(f32x4*)(s1out + (size_t)i * Cout + c) = s4;
-            *(uint32_t*)(argsel + (size_t)i * Cout + c) = a4;
+            if (ysel) {
+                *(f32x4*)(ysel + (size_t)i * Cout + c) = b4;
+                *(uint32_t*)(argsel + (size_t)i * Cout + c) = a4;
+            }
         }
     }
     if (sub == 0) {
@@ -213,10 +220,12 @@ __global__ __launch_bounds__(256) void edge_reduce_vec_kernel(const float* __res
 // neighbour row.  A thread owns (point, channel quad) and walks its k neighbours in slot order, so the first-occurrence
 // rule needs no cross-lane merge.  Partial BN statistics: one fp64 row per (cloud, chunk), each slice writes its columns.
 #define ELDS_CS 8           // channels of a slice: 32 KB of LDS at N = 1024 (four workgroups per CU; 16 measured 2 % slower)
-template <int KMAX, bool EXACT>     // EXACT: k == KMAX, the neighbour loop is straight-line (all index / row reads of a point in flight)
+// SEL: ysel and argsel are stored (a compile-time flag here and in the wide kernel: a run-time branch on the pointer reshapes their point
+// loops -- the k = 20 and 40 forms took twice the registers; without the stores the search for the extreme is dead code)
+template <int KMAX, bool EXACT, bool SEL>     // EXACT: k == KMAX, the neighbour loop is straight-line (all index / row reads of a point in flight)
 __global__ __launch_bounds__(256) void edge_reduce_lds_kernel(const float* __restrict__ uv, const int* __restrict__ idx,
                                                               const float* __restrict__ gamma, int B, int N, int k, int Cout, int psplit,
-                                                              float* __restrict__ msel, uint8_t* __restrict__ argsel,
+                                                              float* __restrict__ ysel, uint8_t* __restrict__ argsel,
                                                               float* __restrict__ s1out, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float esm[];
     constexpr int CS = ELDS_CS, QPP = CS / 4, PL = 256 / QPP;
@@ -278,13 +287,15 @@ __global__ __launch_bounds__(256) void edge_reduce_lds_kernel(const float* __res
         uint32_t a4 = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            b4[e] = best[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);
+            b4[e] = best[e] + v[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);
             ps[e] += (double)s1[e] + (double)k * v[e];
             pq[e] += (double)s2[e] + 2.0 * (double)v[e] * s1[e] + (double)k * v[e] * v[e];
         }
-        *(f32x4*)(msel + i * Cout + c0 + 4 * q) = b4;
         *(f32x4*)(s1out + i * Cout + c0 + 4 * q) = s4;
-        *(uint32_t*)(argsel + i * Cout + c0 + 4 * q) = a4;
+        if (SEL) {
+            *(f32x4*)(ysel + i * Cout + c0 + 4 * q) = b4;
+            *(uint32_t*)(argsel + i * Cout + c0 + 4 * q) = a4;
+        }
     }
     __syncthreads();                                           // Us is dead: reuse it for the fp64 column reduction
     double* red = (double*)esm;                                // [2][PL][CS]
@@ -308,15 +319,16 @@ __global__ __launch_bounds__(256) void edge_reduce_lds_kernel(const float* __res
 // one of 1024 threads for N <= 2048); a thread = (point, channel quad) walks the k neighbours of its point in slot order.  The neighbour
 // indices are not staged: the lanes of a point read the same 80 bytes from global (one broadcast line).  The selection runs on t = +-u (sign
 // of the BatchNorm scale folded in at staging: the max search is one compare, the sums are the same IEEE operations on negated values).
-template <int KMAX, bool EXACT, int CS, int NT>
+template <int KMAX, bool EXACT, int CS, int NT, bool SEL>
 __global__ __launch_bounds__(NT, 4) void edge_reduce_wide_kernel(const float* __restrict__ uv, const int* __restrict__ idx,
                                                                 const float* __restrict__ gamma, int B, int N, int k, int Cout, int psplit,
-                                                                float* __restrict__ msel, uint8_t* __restrict__ argsel,
+                                                                float* __restrict__ ysel, uint8_t* __restrict__ argsel,
                                                                 float* __restrict__ s1out, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float esm[];
     constexpr int QPP = CS / 4, PL = NT / QPP;                 // quads per point, points per pass
     float* Us = esm;                                           // [N][CS]  (+-u)
     const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nsl = Cout / CS, bpc = nsl * psplit;
     int b, r;
     xcd_cloud_map(blockIdx.x, bpc, B, b, r);                   // all workgroups of a cloud on one XCD: uv rows come from its L2
@@ -381,21 +393,26 @@ __global__ __launch_bounds__(NT, 4) void edge_reduce_wide_kernel(const float* __
         uint32_t a4 = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            b4[e] = best[e] * sg[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);
+            b4[e] = best[e] * sg[e] + v[e]; s4[e] = s1[e]; a4 |= (uint32_t)(bs[e] & 255) << (8 * e);   // (best * +-1 is exact: one rounding)
             ps[e] += (double)s1[e] + (double)k * v[e];
             pq[e] += (double)s2[e] + 2.0 * (double)v[e] * s1[e] + (double)k * v[e] * v[e];
         }
-        *(f32x4*)(msel + i * Cout + c0 + 4 * q) = b4;
         *(f32x4*)(s1out + i * Cout + c0 + 4 * q) = s4;
-        *(uint32_t*)(argsel + i * Cout + c0 + 4 * q) = a4;
+        if (SEL) {
+            *(f32x4*)(ysel + i * Cout + c0 + 4 * q) = b4;
+            *(uint32_t*)(argsel + i * Cout + c0 + 4 * q) = a4;
+        }
     }
     __syncthreads();                                           // Us is dead: reuse it for the fp64 column reduction
     double* red = (double*)esm;                                // [2][PL][CS]
+    // (the thread index again, from the wave number and the lane count: the k = 20 instantiations sit at their 128 registers through the
+    // point loop, and a thread index kept across it went to scratch once ysel needed v next to the extreme; pl * CS + 4 * q = 4 * tid)
+    const int t2 = wv * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { red[(0 * PL + pl) * CS + 4 * q + e] = ps[e]; red[(1 * PL + pl) * CS + 4 * q + e] = pq[e]; }
+    for (int e = 0; e < 4; ++e) { red[4 * t2 + e] = ps[e]; red[PL * CS + 4 * t2 + e] = pq[e]; }
     __syncthreads();
-    if (tid < 2 * CS) {
-        const int which = tid / CS, c = tid % CS;
+    if (t2 < 2 * CS) {
+        const int which = t2 / CS, c = t2 % CS;
         double a = 0.0;
         for (int u = 0; u < PL; ++u) a += red[(which * PL + u) * CS + c];
         part[((size_t)(b * psplit + ch) * 2 + which) * Cout + c0 + c] = a;
@@ -415,10 +432,21 @@ __device__ __forceinline__ void edge_amax_raise(float* __restrict__ amax, float 
     if (threadIdx.x == 0) atomicMax((unsigned int*)amax + (blockIdx.x & 255), __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
 }
 
-// vectorised reverse gather (same lane layout): du_j over rev(j)
-template <int LR>
+// dv of one (point, channel):  gz - k*A - Bc*(s1 + k*(v - mean))  -- ONE expression for the point pass and for the gather that stands in
+// for it (the two must round alike)
+__device__ __forceinline__ float edge_dv(float g, float A, float Bc, float s1, float fk, float v, float mean) {
+    return g - fk * A - Bc * (s1 + fk * (v - mean));
+}
+
+// vectorised reverse gather (same lane layout): du_j over rev(j).  (An entry's gz quad is fetched whether or not one of its four channels
+// selected this slot: reading argsel first and gz only on a hit skips 81 % of those loads and was SLOWER at every width -- the second
+// load waits for the first, and the loop is bound by round trips, not by bytes: DESIGN.md section 30.)
+// DV: the wave also writes dv_j -- per destination, from gz_j, s1_j, v_j -- next to du_j (one full 2*Cout row of duv), whatever j's
+// in-degree; the point pass is then not launched (its gz came from edge_bwd_reduce_vec_kernel).
+template <int LR, bool DV>
 __global__ __launch_bounds__(256) void edge_bwd_gather_vec_kernel(const float* __restrict__ gz, const uint8_t* __restrict__ argsel,
-                                                                  const float* __restrict__ uv, const int* __restrict__ rev_off,
+                                                                  const float* __restrict__ uv, const float* __restrict__ s1, int k,
+                                                                  const int* __restrict__ rev_off,
                                                                   const int* __restrict__ rev_ent, int P, int N,
                                                                   const float* __restrict__ scale, const float* __restrict__ mean,
                                                                   const float* __restrict__ invstd,
@@ -445,6 +473,15 @@ __global__ __launch_bounds__(256) void edge_bwd_gather_vec_kernel(const float* _
 #pragma unroll
             for (int e = 0; e < 4; ++e) { float sc = scale[c + e]; A[e] = sc * mean_dz[c + e]; Bc[e] = sc * invstd[c + e] * mean_dzy[c + e]; }
         }
+        // the destination's own rows: in flight while the reverse list is walked
+        f32x4 u = {0.f, 0.f, 0.f, 0.f}, gj = u, sj = u, vj = u;
+        if (sub == 0) {
+            u = *(const f32x4*)(uv + (size_t)j * ld + c);
+            if (DV) {
+                gj = *(const f32x4*)(gz + (size_t)j * Cout + c);
+                if (mean_dz) { sj = *(const f32x4*)(s1 + (size_t)j * Cout + c); vj = *(const f32x4*)(uv + (size_t)j * ld + Cout + c); }
+            }
+        }
         float acc[4] = {0, 0, 0, 0};
         for (int ec = e0; ec < e1; ec += 64) {              // chunks of 64 reverse entries: one coalesced load, then shuffles
             const int nent = min(64, e1 - ec);
@@ -469,33 +506,42 @@ __global__ __launch_bounds__(256) void edge_bwd_gather_vec_kernel(const float* _
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
         if (sub == 0) {
-            const f32x4 u = *(const f32x4*)(uv + (size_t)j * ld + c);
             f32x4 o4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { o4[e] = acc[e] - (float)(e1 - e0) * (A[e] + Bc[e] * (u[e] - mean[c + e])); pm = fmaxf(pm, fabsf(o4[e])); }
             *(f32x4*)(duv + (size_t)j * ld + c) = o4;
+            if (DV) {
+                f32x4 dv = gj;                                  // eval mode: dv = gz
+                if (mean_dz) {
+                    const float fk = (float)k;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dv[e] = edge_dv(gj[e], A[e], Bc[e], sj[e], fk, vj[e], mean[c + e]);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pm = fmaxf(pm, fabsf(dv[e]));
+                *(f32x4*)(duv + (size_t)j * ld + Cout + c) = dv;
+            }
         }
     }
     if (duv_amax) edge_amax_raise(duv_amax, pm);
 }
 
-// out = act(scale*(msel + v) + shift)
-__global__ __launch_bounds__(256) void edge_select_act_kernel(const float* __restrict__ msel, const float* __restrict__ uv,
+// out = act(scale*ysel + shift)
+__global__ __launch_bounds__(256) void edge_select_act_kernel(const float* __restrict__ ysel,
                                                               int P, int Cout, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, int act, float slope,
                                                               float* __restrict__ out, int ldo) {
     size_t total = (size_t)P * Cout;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         size_t i = t / Cout; int c = (int)(t % Cout);
-        float y = msel[t] + uv[i * 2 * Cout + Cout + c];
-        out[i * ldo + c] = lrelu_or_relu(fmaf(y, scale[c], shift[c]), act, slope);
+        out[i * ldo + c] = lrelu_or_relu(fmaf(ysel[t], scale[c], shift[c]), act, slope);
     }
 }
 
 // backward pass 1: column partial sums of dz and dz*yhat_sel (only the selected edge of each
 // (point, channel) carries an incoming gradient)
 __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __restrict__ dOut, const float* __restrict__ out,
-                                                              const float* __restrict__ msel, const float* __restrict__ uv,
+                                                              const float* __restrict__ ysel,
                                                               int P, int Cout, const float* __restrict__ mean,
                                                               const float* __restrict__ invstd, int act, float slope,
                                                               double* __restrict__ part, int lddo, int ldo) {
@@ -510,7 +556,7 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __res
             size_t t = (size_t)r * Cout + c;
             float d = dOut[(size_t)r * lddo + c];
             if (act && !(out[(size_t)r * ldo + c] > 0.f)) d *= (act == 1 ? 0.f : slope);
-            float yh = (msel[t] + uv[(size_t)r * 2 * Cout + Cout + c] - mu) * is;
+            float yh = (ysel[t] - mu) * is;
             s += d; q += (double)d * yh;
         }
     }
@@ -552,30 +598,37 @@ __global__ __launch_bounds__(256) void edge_bwd_point_kernel(const float* __rest
 
 // ---- vectorised (16 B per lane) forms of the per-point passes; Cout % 4 == 0, Cout <= 1024, 256 % (Cout/4) == 0 ----
 #define EVROWS 64
+// gz (nullable, with `scale`): the pass also stores gz = scale*dz, which needs no batch mean -- the by-product that lets the gather below
+// write dv and the point pass disappear (mlsp_edgeconv_bwd_f32, all three passes vectorised)
 __global__ __launch_bounds__(256) void edge_bwd_reduce_vec_kernel(const float* __restrict__ dOut, const float* __restrict__ out,
-                                                                  const float* __restrict__ msel, const float* __restrict__ uv,
-                                                                  int P, int Cout, const float* __restrict__ mean,
+                                                                  const float* __restrict__ ysel,
+                                                                  int P, int Cout, const float* __restrict__ scale,
+                                                                  const float* __restrict__ mean,
                                                                   const float* __restrict__ invstd, int act, float slope,
                                                                   double* __restrict__ part, int lddo, int ldo,
-                                                                  float* __restrict__ duv_amax) {
+                                                                  float* __restrict__ gz, float* __restrict__ duv_amax) {
     __shared__ double shd[256 * 8];
     const int tid = threadIdx.x, tpr = Cout >> 2, nrg = 256 / tpr;
-    if (duv_amax && blockIdx.x == 0) duv_amax[tid] = 0.f;       // the 256 partial maxima the two passes below raise (edge_amax_raise)
+    if (duv_amax && blockIdx.x == 0) duv_amax[tid] = 0.f;       // the 256 partial maxima the passes below raise (edge_amax_raise)
     const int cg = tid % tpr, rg = tid / tpr, c = cg * 4;
     double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     const f32x4 mu = *(const f32x4*)(mean + c), is = *(const f32x4*)(invstd + c);
+    f32x4 sc = {0.f, 0.f, 0.f, 0.f};
+    if (gz) sc = *(const f32x4*)(scale + c);
     const int r0 = blockIdx.x * EVROWS, r1 = min(P, r0 + EVROWS);
     for (int r = r0 + rg; r < r1; r += nrg) {
         const size_t t = (size_t)r * Cout + c;
         const f32x4 d4 = *(const f32x4*)(dOut + (size_t)r * lddo + c), o4 = *(const f32x4*)(out + (size_t)r * ldo + c);
-        const f32x4 m4 = *(const f32x4*)(msel + t);
-        const f32x4 v4 = *(const f32x4*)(uv + (size_t)r * 2 * Cout + Cout + c);
+        const f32x4 y4 = *(const f32x4*)(ysel + t);
+        f32x4 g4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float d = d4[e];
             if (act && !(o4[e] > 0.f)) d *= (act == 1 ? 0.f : slope);
-            s[e] += d; q[e] += (double)d * ((m4[e] + v4[e] - mu[e]) * is[e]);
+            s[e] += d; q[e] += (double)d * ((y4[e] - mu[e]) * is[e]);
+            g4[e] = sc[e] * d;
         }
+        if (gz) *(f32x4*)(gz + t) = g4;
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) { shd[tid * 8 + e] = s[e]; shd[tid * 8 + 4 + e] = q[e]; }
@@ -593,17 +646,17 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_vec_kernel(const float* _
     }
 }
 
-__global__ __launch_bounds__(256) void edge_select_act_vec_kernel(const float* __restrict__ msel, const float* __restrict__ uv,
+__global__ __launch_bounds__(256) void edge_select_act_vec_kernel(const float* __restrict__ ysel,
                                                                   size_t total4, int C4, const float* __restrict__ scale,
                                                                   const float* __restrict__ shift, int act, float slope,
                                                                   float* __restrict__ out, int ldo) {
     for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < total4; v += (size_t)gridDim.x * blockDim.x) {
         const size_t i = v / C4; const int c = (int)(v % C4) * 4;
-        const f32x4 m = *(const f32x4*)(msel + v * 4), vv = *(const f32x4*)(uv + i * 8 * C4 + 4 * C4 + c);
+        const f32x4 y = *(const f32x4*)(ysel + v * 4);
         const f32x4 sc = *(const f32x4*)(scale + c), sh = *(const f32x4*)(shift + c);
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = lrelu_or_relu(fmaf(m[e] + vv[e], sc[e], sh[e]), act, slope);
+        for (int e = 0; e < 4; ++e) o[e] = lrelu_or_relu(fmaf(y[e], sc[e], sh[e]), act, slope);
         *(f32x4*)(out + i * ldo + c) = o;
     }
 }
@@ -634,7 +687,7 @@ __global__ __launch_bounds__(256) void edge_bwd_point_vec_kernel(const float* __
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float A = sc[e] * mean_dz[c + e], Bc = sc[e] * invstd[c + e] * mean_dzy[c + e];
-                dv[e] = g[e] - fk * A - Bc * (s4[e] + fk * (vv[e] - mean[c + e]));
+                dv[e] = edge_dv(g[e], A, Bc, s4[e], fk, vv[e], mean[c + e]);
             }
         }
         *(f32x4*)(gz + v * 4) = g;
@@ -724,10 +777,9 @@ static inline int ew_blocks2(size_t total) {
 }
 
 // number of partial rows launch_edge_bwd_reduce writes for this shape
-int edge_bwd_reduce_parts(int P, int Cout, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f,
-                          int lddo, int ldo) {
+int edge_bwd_reduce_parts(int P, int Cout, const void* a, const void* b, const void* c, const void* d, const void* e, int lddo, int ldo) {
     bool vec = Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 && lddo % 4 == 0 && ldo % 4 == 0 &&
-               ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f) & 15) == 0);
+               ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0);
     return vec ? (P + EVROWS - 1) / EVROWS : (P + 511) / 512;
 }
 int edge_reduce_parts(int P) { return (P + 4 * EDGE_PTS_PER_WAVE - 1) / (4 * EDGE_PTS_PER_WAVE); }
@@ -752,9 +804,11 @@ int launch_unbuild_wd(hipStream_t st, const float* dWd, int Cout, int C, float* 
     return mlsp_launch_status();
 }
 // *nparts_used (optional) receives the number of partial-statistics rows written (<= edge_reduce_parts(P))
+// ysel and argsel: both or neither (null: those stores are skipped)
 int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const float* gamma, int P, int N, int Cout, int k,
-                       float* msel, uint8_t* argsel, float* s1, double* part, int* nparts_used) {
-    const bool al = (((uintptr_t)uv | (uintptr_t)msel | (uintptr_t)s1 | (uintptr_t)gamma) & 15) == 0 && (((uintptr_t)argsel) & 3) == 0;
+                       float* ysel, uint8_t* argsel, float* s1, double* part, int* nparts_used) {
+    if (!ysel != !argsel) return MLSP_ERR_ARG;
+    const bool al = (((uintptr_t)uv | (uintptr_t)ysel | (uintptr_t)s1 | (uintptr_t)gamma) & 15) == 0 && (((uintptr_t)argsel) & 3) == 0;
     if (nparts_used) *nparts_used = edge_reduce_parts(P);
     if (al && P % N == 0 && N % 4 == 0 && (k == 20 || k == 40 || k <= 32) && Cout % 32 == 0 && N <= 2048) {
         // wide slices: CS = 16 channels, 512 threads (two workgroups per CU: one stages while the other gathers) while N <= 1024, else 1024
@@ -770,9 +824,10 @@ int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const fl
         const size_t red = (size_t)2 * (NT / (CS / 4)) * CS * sizeof(double);
         if ((lds > red ? lds : red) <= 150 * 1024 && B * psplit <= edge_reduce_parts(P)) {
             const size_t ldsz = lds > red ? lds : red;
-#define EW_GO(KM, EX) do { auto kern = NT == 512 ? edge_reduce_wide_kernel<KM, EX, CS, 512> : edge_reduce_wide_kernel<KM, EX, CS, 1024>; \
+#define EW_GO(KM, EX) do { auto kern = NT == 512 ? (ysel ? edge_reduce_wide_kernel<KM, EX, CS, 512, true> : edge_reduce_wide_kernel<KM, EX, CS, 512, false>) \
+                                                  : (ysel ? edge_reduce_wide_kernel<KM, EX, CS, 1024, true> : edge_reduce_wide_kernel<KM, EX, CS, 1024, false>); \
                 if (ldsz > 64 * 1024) { hipError_t e_ = mlsp_lds_limit((const void*)kern, ldsz); if (e_ != hipSuccess) return (int)e_; } \
-                hipLaunchKernelGGL(kern, dim3(B * nsl * psplit), dim3(NT), ldsz, st, uv, idx, gamma, B, N, k, Cout, psplit, msel, argsel, s1, part); } while (0)
+                hipLaunchKernelGGL(kern, dim3(B * nsl * psplit), dim3(NT), ldsz, st, uv, idx, gamma, B, N, k, Cout, psplit, ysel, argsel, s1, part); } while (0)
             if (k == 20) EW_GO(20, true); else if (k <= 20) EW_GO(20, false); else if (k <= 32) EW_GO(32, false); else EW_GO(40, true);
 #undef EW_GO
             if (nparts_used) *nparts_used = B * psplit;
@@ -785,46 +840,48 @@ int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const fl
         while (psplit < 8 && (B * nsl * psplit < 512 || (N / psplit) * k * 2 > 16 * 1024) && N % (psplit * 2) == 0) psplit *= 2;
         const size_t lds = (size_t)N * ELDS_CS * sizeof(float) + align_up((size_t)((N + psplit - 1) / psplit) * k * 2, 16);
         if (lds <= 150 * 1024 && B * psplit <= edge_reduce_parts(P) && lds >= (size_t)2 * (256 / (ELDS_CS / 4)) * ELDS_CS * sizeof(double)) {
-            auto kern = k == 20 ? edge_reduce_lds_kernel<20, true> : k <= 20 ? edge_reduce_lds_kernel<20, false> : k <= 32 ? edge_reduce_lds_kernel<32, false>
-                      : k == 40 ? edge_reduce_lds_kernel<40, true> : edge_reduce_lds_kernel<40, false>;     // k = 40: BASELINE.json configs[4]
+#define EL_PICK(S) (k == 20 ? edge_reduce_lds_kernel<20, true, S> : k <= 20 ? edge_reduce_lds_kernel<20, false, S> : k <= 32 ? edge_reduce_lds_kernel<32, false, S> \
+                    : k == 40 ? edge_reduce_lds_kernel<40, true, S> : edge_reduce_lds_kernel<40, false, S>)                  // k = 40: BASELINE.json configs[4]
+            auto kern = ysel ? EL_PICK(true) : EL_PICK(false);
+#undef EL_PICK
             if (lds > 64 * 1024) {
                 hipError_t e = mlsp_lds_limit((const void*)kern, lds);
                 if (e != hipSuccess) return (int)e;
             }
-            hipLaunchKernelGGL(kern, dim3(B * nsl * psplit), dim3(256), lds, st, uv, idx, gamma, B, N, k, Cout, psplit, msel, argsel, s1, part);
+            hipLaunchKernelGGL(kern, dim3(B * nsl * psplit), dim3(256), lds, st, uv, idx, gamma, B, N, k, Cout, psplit, ysel, argsel, s1, part);
             if (nparts_used) *nparts_used = B * psplit;
             return mlsp_launch_status();
         }
     }
     if (al && (Cout == 64 || Cout == 128 || Cout == 256)) {
         dim3 g(edge_reduce_parts(P)), b(256);
-        if (Cout == 64) hipLaunchKernelGGL((edge_reduce_vec_kernel<16>), g, b, 0, st, uv, idx, gamma, P, N, k, msel, argsel, s1, part);
-        else if (Cout == 128) hipLaunchKernelGGL((edge_reduce_vec_kernel<32>), g, b, 0, st, uv, idx, gamma, P, N, k, msel, argsel, s1, part);
-        else hipLaunchKernelGGL((edge_reduce_vec_kernel<64>), g, b, 0, st, uv, idx, gamma, P, N, k, msel, argsel, s1, part);
+        if (Cout == 64) hipLaunchKernelGGL((edge_reduce_vec_kernel<16>), g, b, 0, st, uv, idx, gamma, P, N, k, ysel, argsel, s1, part);
+        else if (Cout == 128) hipLaunchKernelGGL((edge_reduce_vec_kernel<32>), g, b, 0, st, uv, idx, gamma, P, N, k, ysel, argsel, s1, part);
+        else hipLaunchKernelGGL((edge_reduce_vec_kernel<64>), g, b, 0, st, uv, idx, gamma, P, N, k, ysel, argsel, s1, part);
         return mlsp_launch_status();
     }
     size_t lds = (size_t)8 * Cout * sizeof(double);
     if (lds > 64 * 1024) return MLSP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(edge_reduce_kernel, dim3(edge_reduce_parts(P)), dim3(256), lds, st, uv, idx, gamma, P, N, Cout, k,
-                       msel, argsel, s1, part);
+                       ysel, argsel, s1, part);
     return mlsp_launch_status();
 }
-int launch_edge_select_act(hipStream_t st, const float* msel, const float* uv, int P, int Cout, const float* scale,
+int launch_edge_select_act(hipStream_t st, const float* ysel, int P, int Cout, const float* scale,
                            const float* shift, int act, float slope, float* out, int ldo) {
-    if (Cout % 4 == 0 && ldo % 4 == 0 && ((((uintptr_t)msel | (uintptr_t)uv | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0)) {
+    if (Cout % 4 == 0 && ldo % 4 == 0 && ((((uintptr_t)ysel | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0)) {
         size_t t4 = (size_t)P * Cout / 4;
-        hipLaunchKernelGGL(edge_select_act_vec_kernel, dim3(ew_blocks2(t4)), dim3(256), 0, st, msel, uv, t4, Cout / 4, scale, shift,
+        hipLaunchKernelGGL(edge_select_act_vec_kernel, dim3(ew_blocks2(t4)), dim3(256), 0, st, ysel, t4, Cout / 4, scale, shift,
                            act, slope, out, ldo);
         return mlsp_launch_status();
     }
-    hipLaunchKernelGGL(edge_select_act_kernel, dim3(ew_blocks2((size_t)P * Cout)), dim3(256), 0, st, msel, uv, P, Cout, scale,
+    hipLaunchKernelGGL(edge_select_act_kernel, dim3(ew_blocks2((size_t)P * Cout)), dim3(256), 0, st, ysel, P, Cout, scale,
                        shift, act, slope, out, ldo);
     return mlsp_launch_status();
 }
-static bool edge_bwd_reduce_vec_ok(const float* dOut, const float* out, const float* msel, const float* uv, int Cout, const float* mean,
+static bool edge_bwd_reduce_vec_ok(const float* dOut, const float* out, const float* ysel, int Cout, const float* mean,
                                    const float* invstd, int lddo, int ldo) {
     return Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 && lddo % 4 == 0 && ldo % 4 == 0 &&
-           ((((uintptr_t)dOut | (uintptr_t)out | (uintptr_t)msel | (uintptr_t)uv | (uintptr_t)mean | (uintptr_t)invstd) & 15) == 0);
+           ((((uintptr_t)dOut | (uintptr_t)out | (uintptr_t)ysel | (uintptr_t)mean | (uintptr_t)invstd) & 15) == 0);
 }
 static bool edge_bwd_point_vec_ok(const float* dOut, const float* out, const float* uv, const float* s1, int Cout, const float* scale,
                                   const float* gz, const float* duv, int lddo, int ldo) {
@@ -834,24 +891,27 @@ static bool edge_bwd_point_vec_ok(const float* dOut, const float* out, const flo
 static bool edge_bwd_gather_vec_ok(const float* gz, const uint8_t* argsel, const float* uv, int Cout, const float* duv) {
     return (((uintptr_t)uv | (uintptr_t)gz | (uintptr_t)duv) & 15) == 0 && (((uintptr_t)argsel) & 3) == 0 && (Cout == 64 || Cout == 128 || Cout == 256);
 }
-// all three backward passes take their vectorised form for these operands: they can leave the bound of duv as a by-product
-// (`duv_amax` of the launchers below; the scalar forms ignore it)
-bool edge_bwd_leaves_duv_bound(const float* dOut, const float* out, const float* msel, const float* uv, const float* s1, const uint8_t* argsel,
+// all three backward passes take their vectorised form for these operands: the reduce can store gz and the gather dv (no point launch:
+// `gz` of launch_edge_bwd_reduce, `s1` of launch_edge_bwd_gather), and they can leave the bound of duv as a by-product (`duv_amax` of
+// the launchers below; the scalar forms ignore it)
+bool edge_bwd_leaves_duv_bound(const float* dOut, const float* out, const float* ysel, const float* uv, const float* s1, const uint8_t* argsel,
                                int Cout, const float* scale, const float* mean, const float* invstd, const float* gz, const float* duv,
                                int lddo, int ldo) {
-    return edge_bwd_reduce_vec_ok(dOut, out, msel, uv, Cout, mean, invstd, lddo, ldo) &&
+    return edge_bwd_reduce_vec_ok(dOut, out, ysel, Cout, mean, invstd, lddo, ldo) &&
            edge_bwd_point_vec_ok(dOut, out, uv, s1, Cout, scale, gz, duv, lddo, ldo) && edge_bwd_gather_vec_ok(gz, argsel, uv, Cout, duv);
 }
-int launch_edge_bwd_reduce(hipStream_t st, const float* dOut, const float* out, const float* msel, const float* uv, int P,
-                           int Cout, const float* mean, const float* invstd, int act, float slope, double* part, int lddo, int ldo,
-                           float* duv_amax) {
-    if (edge_bwd_reduce_vec_ok(dOut, out, msel, uv, Cout, mean, invstd, lddo, ldo)) {
+// gz (nullable; only where edge_bwd_leaves_duv_bound holds): the pass also stores gz = scale*dz, for a gather that writes dv
+int launch_edge_bwd_reduce(hipStream_t st, const float* dOut, const float* out, const float* ysel, int P,
+                           int Cout, const float* scale, const float* mean, const float* invstd, int act, float slope, double* part, int lddo,
+                           int ldo, float* gz, float* duv_amax) {
+    if (edge_bwd_reduce_vec_ok(dOut, out, ysel, Cout, mean, invstd, lddo, ldo)) {
         // NOTE: writes (P+1023)/1024 partial rows -- callers size `part` for (P+511)/512 and pass the count below
-        hipLaunchKernelGGL(edge_bwd_reduce_vec_kernel, dim3((P + EVROWS - 1) / EVROWS), dim3(256), 0, st, dOut, out, msel, uv, P, Cout,
-                           mean, invstd, act, slope, part, lddo, ldo, duv_amax);
+        hipLaunchKernelGGL(edge_bwd_reduce_vec_kernel, dim3((P + EVROWS - 1) / EVROWS), dim3(256), 0, st, dOut, out, ysel, P, Cout,
+                           scale, mean, invstd, act, slope, part, lddo, ldo, gz, duv_amax);
         return mlsp_launch_status();
     }
-    hipLaunchKernelGGL(edge_bwd_reduce_kernel, dim3((Cout + 63) / 64, (P + 511) / 512), dim3(256), 0, st, dOut, out, msel, uv,
+    if (gz) return MLSP_ERR_ARG;
+    hipLaunchKernelGGL(edge_bwd_reduce_kernel, dim3((Cout + 63) / 64, (P + 511) / 512), dim3(256), 0, st, dOut, out, ysel,
                        P, Cout, mean, invstd, act, slope, part, lddo, ldo);
     return mlsp_launch_status();
 }
@@ -868,16 +928,19 @@ int launch_edge_bwd_point(hipStream_t st, const float* dOut, const float* out, c
                        k, scale, mean, invstd, mean_dz, mean_dzy, act, slope, gz, duv, lddo, ldo);
     return mlsp_launch_status();
 }
-int launch_edge_bwd_gather(hipStream_t st, const float* gz, const uint8_t* argsel, const float* uv, const int* rev_off,
-                           const int* rev_ent, int P, int N, int Cout, const float* scale, const float* mean,
+// s1 (nullable; only where edge_bwd_leaves_duv_bound holds, after a reduce that stored gz): the gather also writes dv -- no point pass
+int launch_edge_bwd_gather(hipStream_t st, const float* gz, const uint8_t* argsel, const float* uv, const float* s1, int k,
+                           const int* rev_off, const int* rev_ent, int P, int N, int Cout, const float* scale, const float* mean,
                            const float* invstd, const float* mean_dz, const float* mean_dzy, float* duv, float* duv_amax) {
     if (edge_bwd_gather_vec_ok(gz, argsel, uv, Cout, duv)) {
         dim3 g((P + 3) / 4), b(256);
-        if (Cout == 64) hipLaunchKernelGGL((edge_bwd_gather_vec_kernel<16>), g, b, 0, st, gz, argsel, uv, rev_off, rev_ent, P, N, scale, mean, invstd, mean_dz, mean_dzy, duv, duv_amax);
-        else if (Cout == 128) hipLaunchKernelGGL((edge_bwd_gather_vec_kernel<32>), g, b, 0, st, gz, argsel, uv, rev_off, rev_ent, P, N, scale, mean, invstd, mean_dz, mean_dzy, duv, duv_amax);
-        else hipLaunchKernelGGL((edge_bwd_gather_vec_kernel<64>), g, b, 0, st, gz, argsel, uv, rev_off, rev_ent, P, N, scale, mean, invstd, mean_dz, mean_dzy, duv, duv_amax);
+#define EG_GO(LR) do { if (s1) hipLaunchKernelGGL((edge_bwd_gather_vec_kernel<LR, true>), g, b, 0, st, gz, argsel, uv, s1, k, rev_off, rev_ent, P, N, scale, mean, invstd, mean_dz, mean_dzy, duv, duv_amax); \
+                       else hipLaunchKernelGGL((edge_bwd_gather_vec_kernel<LR, false>), g, b, 0, st, gz, argsel, uv, s1, k, rev_off, rev_ent, P, N, scale, mean, invstd, mean_dz, mean_dzy, duv, duv_amax); } while (0)
+        if (Cout == 64) EG_GO(16); else if (Cout == 128) EG_GO(32); else EG_GO(64);
+#undef EG_GO
         return mlsp_launch_status();
     }
+    if (s1) return MLSP_ERR_ARG;
     hipLaunchKernelGGL(edge_bwd_gather_kernel, dim3((P + 3) / 4), dim3(256), 0, st, gz, argsel, uv, rev_off, rev_ent, P, N,
                        Cout, scale, mean, invstd, mean_dz, mean_dzy, duv);
     return mlsp_launch_status();

@@ -104,8 +104,7 @@ int launch_bn_act_bwd_b16(hipStream_t st, const void* dZ, const void* Y, void* d
 int launch_colsum_groups_b16(hipStream_t st, const void* X, int G, int rows_per_group, int C, float* out, float* scratch);
 
 // edge.hip
-int edge_bwd_reduce_parts(int P, int Cout, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, int lddo,
-                          int ldo);
+int edge_bwd_reduce_parts(int P, int Cout, const void* a, const void* b, const void* c, const void* d, const void* e, int lddo, int ldo);
 int edge_reduce_parts(int P);
 bool build_wd_leaves_bound(int Cout, int C);
 int launch_build_wd(hipStream_t st, const float* W, int Cout, int C, float* Wd, float* amax = nullptr);
@@ -113,21 +112,22 @@ int launch_build_wd_eval(hipStream_t st, const float* W, int Cout, int C, float*
                          const float* rva, float* sva, int Cb, const float* gb, const float* bb, const float* rmb, const float* rvb, float* svb,
                          float eps);
 int launch_unbuild_wd(hipStream_t st, const float* dWd, int Cout, int C, float* dW);
-int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const float* gamma, int P, int N, int Cout, int k, float* msel,
+int launch_edge_reduce(hipStream_t st, const float* uv, const int* idx, const float* gamma, int P, int N, int Cout, int k, float* ysel,
                        uint8_t* argsel, float* s1, double* part, int* nparts_used);
-int launch_edge_select_act(hipStream_t st, const float* msel, const float* uv, int P, int Cout, const float* scale, const float* shift, int act,
-                           float slope, float* out, int ldo);
-bool edge_bwd_leaves_duv_bound(const float* dOut, const float* out, const float* msel, const float* uv, const float* s1, const uint8_t* argsel,
+int launch_edge_select_act(hipStream_t st, const float* ysel, int P, int Cout, const float* scale, const float* shift, int act, float slope,
+                           float* out, int ldo);
+bool edge_bwd_leaves_duv_bound(const float* dOut, const float* out, const float* ysel, const float* uv, const float* s1, const uint8_t* argsel,
                                int Cout, const float* scale, const float* mean, const float* invstd, const float* gz, const float* duv, int lddo,
                                int ldo);
-int launch_edge_bwd_reduce(hipStream_t st, const float* dOut, const float* out, const float* msel, const float* uv, int P, int Cout,
-                           const float* mean, const float* invstd, int act, float slope, double* part, int lddo, int ldo, float* duv_amax);
+int launch_edge_bwd_reduce(hipStream_t st, const float* dOut, const float* out, const float* ysel, int P, int Cout, const float* scale,
+                           const float* mean, const float* invstd, int act, float slope, double* part, int lddo, int ldo, float* gz,
+                           float* duv_amax);
 int launch_edge_bwd_point(hipStream_t st, const float* dOut, const float* out, const float* uv, const float* s1, int P, int Cout, int k,
                           const float* scale, const float* mean, const float* invstd, const float* mean_dz, const float* mean_dzy, int act,
                           float slope, float* gz, float* duv, int lddo, int ldo, float* duv_amax);
-int launch_edge_bwd_gather(hipStream_t st, const float* gz, const uint8_t* argsel, const float* uv, const int* rev_off, const int* rev_ent, int P,
-                           int N, int Cout, const float* scale, const float* mean, const float* invstd, const float* mean_dz, const float* mean_dzy,
-                           float* duv, float* duv_amax);
+int launch_edge_bwd_gather(hipStream_t st, const float* gz, const uint8_t* argsel, const float* uv, const float* s1, int k, const int* rev_off,
+                           const int* rev_ent, int P, int N, int Cout, const float* scale, const float* mean, const float* invstd,
+                           const float* mean_dz, const float* mean_dzy, float* duv, float* duv_amax);
 int launch_graph_feature_fwd(hipStream_t st, const float* x, const int* idx, int P, int N, int C, int k, float* F);
 int launch_graph_feature_bwd(hipStream_t st, const float* dF, const int* rev_off, const int* rev_ent, int P, int N, int C, int k, float* dx);
 
