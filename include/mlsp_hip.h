@@ -379,7 +379,8 @@ int mlsp_knn_normals_f32(const float* x, int ldx, const int32_t* idx, int B, int
  * N source points (same format as mlsp_knn_reverse) for the deterministic backward of the grouping. */
 /* kNN of query points among DIFFERENT reference points: `square_distance` + argsort()[:, :, :k] (pointnet_util.py:26-38,116-118 knn=True
  * grouping, :237-239 Msg, :287-289 the 3-NN of feature propagation; the KNN calls of PointDA/model_utils.py:175,188 have this shape).
- * d = (-2 q.r + |q|^2) + |r|^2 in fp32 (dot = fmaf chain over the C <= 8 coordinates), ascending, ties -> lower reference index.
+ * d = sum_c (q_c - r_c)^2 in fp32 -- the reference's return statement (pointnet_util.py:36), c ascending over the C <= 8 coordinates,
+ * ((dx*dx + dy*dy) + dz*dz) + ..., no contraction: never negative, exactly 0 at coincident points -- ascending, ties -> lower reference index.
  * ref [B][Nr] rows (pitch ldr), qry [B][Nq] rows (pitch ldq) -> idx [B][Nq][k] (local to the cloud), dist [B][Nq][k] (nullable). k <= 64.
  * Index contract: every returned index lies in [0, Nr), whatever the coordinates hold (k <= Nr is required).  A distance that is not
  * finite (a NaN coordinate in the query or the reference, a squared norm that overflows) counts as +inf; +inf candidates fill the slots
@@ -394,6 +395,10 @@ int mlsp_interp3_fwd_f32(const float* feat, const int32_t* idx, const float* dis
 int mlsp_interp3_bwd_f32(const float* dout, const float* dist, const int32_t* rev_off, const int32_t* rev_ent, int B, int N, int S, int D,
                          float* dfeat, mlsp_stream_t stream);
 int mlsp_fps_f32(const float* xyz, int ldx, int B, int N, int S, const int32_t* start, int32_t* fps_idx, mlsp_stream_t stream);
+/* Which kernel mlsp_fps_f32 runs a cloud of N points on (host arithmetic only, no launch): 2 = the four-wave DPP kernel (64 <= N <= 2048),
+ * 1 = the 1024-thread kernel (every other N up to 8192), 0 = no kernel (N <= 0 or N > 8192: mlsp_fps_f32 returns MLSP_ERR_ARG). */
+int mlsp_fps_plan(int N);
+/* (a query without a hit inside the radius -- the reference indexes out of range there -- gets 0 in every slot) */
 int mlsp_ball_query_f32(const float* xyz, int ldx, const float* new_xyz, int ldq, int B, int N, int S, float radius_sq, int nsample,
                         int32_t* idx, mlsp_stream_t stream);
 int mlsp_group_reverse(const int32_t* idx, int B, int S, int N, int ns, int32_t* rev_off, int32_t* rev_ent, mlsp_stream_t stream);
@@ -434,8 +439,9 @@ int mlsp_sa_fold_fwd_f32(const float* u, const float* w, const int32_t* idx, int
 int mlsp_sa_fold_bwd_f32(const float* dZ, const float* u, const float* w, const int32_t* idx, const int32_t* rev_off, const int32_t* rev_ent,
                          const int32_t* rev_cnt, const int32_t* pad_cnt, int B, int N, int S, int ns, int C, const float* bn_save, int training,
                          float* du, float* dw, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mlsp_stream_t stream);
-/* Reverse index of padded groups WITHOUT their padding slots (ball-query groups repeat their first hit: slot s > 0 with idx[i][s] ==
- * idx[i][0]): rev_off [B*N+1] list starts, rev_cnt [B*N] list lengths (the lists of a cloud no longer fill its S*ns entries), rev_ent as
+/* Reverse index of padded groups WITHOUT their padding slots (ball-query groups end in copies of their first hit: the padding slots of a
+ * group are its TRAILING run of slots s > 0 with idx[i][s] == idx[i][0]; a repeat of slot 0 further up a row is an ordinary slot, so any
+ * idx is handled, not only ball-query output): rev_off [B*N+1] list starts, rev_cnt [B*N] list lengths (the lists of a cloud no longer fill its S*ns entries), rev_ent as
  * mlsp_group_reverse, pad_cnt [B*S] padding slots per group.  mlsp_sa_fold_bwd_f32 takes rev_cnt / pad_cnt (both or neither, NULL = the
  * full index of mlsp_group_reverse) and adds a group's identical padding rows as a multiple of one row.  The compact form rests on a
  * premise the caller must meet: every padding row of a group carries the same dZ as the group's LAST slot (the row that is read for all

@@ -111,6 +111,7 @@ SIGNATURES = {
     "mlsp_interp3_fwd_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mlsp_interp3_bwd_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mlsp_fps_f32": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "mlsp_fps_plan": [_I],
     "mlsp_ball_query_f32": [_P, _I, _P, _I, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_group_reverse": [_P, _I, _I, _I, _I, _P, _P, _P],
     "mlsp_sa_group_fwd_f32": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P],

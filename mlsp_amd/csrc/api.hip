@@ -4,6 +4,7 @@
 #include "common.h"
 #include "../../include/mlsp_hip.h"
 #include "knn_plan.h"      // mlsp_knn_f32 sizes the planes from the plan of its call
+#include "fps_plan.h"      // mlsp_fps_plan reports what launch_fps follows
 
 #define CHECK(x) do { int _r = (x); if (_r != MLSP_OK) return _r; } while (0)
 #define SLAB_BOUND_FLOATS ((size_t)16 << 20)   /* 64 MiB of fp32: bound on any split-K slab (gemm_pick_split) */
@@ -128,6 +129,7 @@ int mlsp_scan_select_f32(const float* X, int B, int N, int C, const double* R, i
 int mlsp_fps_f32(const float* xyz, int ldx, int B, int N, int S, const int32_t* start, int32_t* fps_idx, mlsp_stream_t st) {
     return launch_fps(st, xyz, ldx, B, N, S, start, fps_idx);
 }
+int mlsp_fps_plan(int N) { return fps_plan(N); }
 int mlsp_ball_query_f32(const float* xyz, int ldx, const float* new_xyz, int ldq, int B, int N, int S, float radius_sq, int nsample,
                         int32_t* idx, mlsp_stream_t st) {
     return launch_ball_query(st, xyz, ldx, new_xyz, ldq, B, N, S, radius_sq, nsample, idx);

@@ -12,13 +12,15 @@
 // `nsplit` workgroups per cloud, each owns a contiguous slice of the destinations: it counts only the edges that point into its
 // slice (LDS atomics are the expensive instruction here: ~3 clocks per lane), gets the slice's base offset by counting the edges
 // that point BELOW it (plain adds + one block reduction), fills its lists and orders every list.
-// skip_pad: the padding slots of a ball-query group (copies of its first hit: slot s > 0 with idx[i][s] == idx[i][0]) are left out of the
-// lists -- their rows are identical, the consumer adds them as a multiple of one row (sa.hip, sa_fold_bwd_point_kernel).  The lists of a
-// cloud then no longer fill its E entries, so the list LENGTHS are returned as well (rev_cnt, nullable otherwise).
+// pad_cnt (nullable; [B*S], from group_pad_count_kernel): the padding slots of a group -- its TRAILING run of copies of slot 0, which is
+// what a ball query appends; a repeat of slot 0 further up a caller's own row is an ordinary slot -- are left out of the lists: slot s of
+// group g is padding iff s >= k - pad_cnt[g].  Their rows are identical and the group's last slot is one of them, so the consumer adds
+// them as a multiple of that row (sa.hip, sa_fold_bwd_point_kernel).  The lists of a cloud then no longer fill its E entries, so the
+// list LENGTHS are returned as well (rev_cnt, nullable otherwise).
 typedef int knn_i32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict__ idx, int N, int k,
                                                            int* __restrict__ rev_off, int* __restrict__ rev_ent,
-                                                           int B, int S, int nsplit, int skip_pad, int* __restrict__ rev_cnt) {
+                                                           int B, int S, int nsplit, const int* __restrict__ pad_cnt, int* __restrict__ rev_cnt) {
     extern __shared__ __attribute__((aligned(16))) int ism[];
     __shared__ int wsum[16];
     __shared__ int nbig;                  // lists of more than 64 entries: queued (cnt is free by then) for the whole-workgroup loop
@@ -34,6 +36,7 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
     // S source rows of k slots per cloud point at N destinations (S == N for the kNN graph; the set-abstraction grouping has
     // S sampled centres gathering from N points)
     const int* ib = idx + (size_t)b * S * k;
+    const int* pb = pad_cnt ? pad_cnt + (size_t)b * S : nullptr;
     const int E = S * k;
     for (int j = tid; j < nd; j += nt) cnt[j] = 0;
     if (tid == 0) nbig = 0;
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
 #pragma unroll
         for (int u = 0; u < RV_B; ++u) {
             int j = jk[u];
-            if (skip_pad && j >= 0) { const int e = eb + u * nt, sl = e % k; if (sl != 0 && j == ib[e - sl]) j = -1; }
+            if (pb && j >= 0) { const int e = eb + u * nt; if (e % k >= k - pb[e / k]) j = -1; }
             jk[u] = j;
             below += j >= 0 && j < d0;
             const bool mine = j >= d0 && j < d1;
@@ -134,7 +137,7 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
         for (int u = 0; u < RV_B; ++u) {
             int j = jk[u];
             const int e = eb + u * nt;
-            if (!one_trip && skip_pad && j >= 0) { const int sl = e % k; if (sl != 0 && j == ib[e - sl]) j = -1; }
+            if (!one_trip && pb && j >= 0 && e % k >= k - pb[e / k]) j = -1;
             if (j >= d0 && j < d1) {
                 const int pos = atomicAdd(&cnt[j - d0], 1);
                 ent[eoff[j - d0] + pos] = ((e / k) << 8) | (e % k);
@@ -218,7 +221,21 @@ __global__ __launch_bounds__(1024) void knn_reverse_kernel(const int* __restrict
     }
 }
 
-static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent, int skip_pad = 0,
+// pad_cnt [B*S] = number of padding slots of every group: the length of the trailing run of slots s > 0 with idx[i][s] == idx[i][0]
+// (0 .. k - 1).  Counted BEFORE the lists are built: knn_reverse_kernel reads it, so both hold ONE definition of a padding slot and
+// "pad_cnt times the row of the last slot" is right for any idx, not only for the trailing pads a ball query makes.
+__global__ __launch_bounds__(256) void group_pad_count_kernel(const int* __restrict__ idx, int G, int k, int* __restrict__ pad_cnt) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const int* r = idx + (size_t)g * k;
+    const int first = r[0];
+    int c = 0;
+    for (int s = 1; s < k; ++s) c = r[s] == first ? c + 1 : 0;      // (a forward pass over independent loads: the run that reaches slot k - 1)
+    pad_cnt[g] = c;
+}
+
+// pad_cnt / rev_cnt: both or neither (the compact form)
+static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent, int* pad_cnt = nullptr,
                           int* rev_cnt = nullptr) {
     if (!idx || !rev_off || !rev_ent || B <= 0 || N <= 0 || S <= 0 || k <= 0 || k > 256 || N > (1 << 22) || S > (1 << 22)) return MLSP_ERR_ARG;
     const int nsplit = B * 8 >= 256 || N < 1024 ? 8 : RV_SPLIT_MAX;
@@ -229,7 +246,8 @@ static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, i
         hipError_t e = mlsp_lds_limit((const void*)knn_reverse_kernel, lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(knn_reverse_kernel, dim3(B * nsplit), dim3(1024), lds, st, idx, N, k, rev_off, rev_ent, B, S, nsplit, skip_pad, rev_cnt);
+    if (pad_cnt) hipLaunchKernelGGL(group_pad_count_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, idx, B * S, k, pad_cnt);
+    hipLaunchKernelGGL(knn_reverse_kernel, dim3(B * nsplit), dim3(1024), lds, st, idx, N, k, rev_off, rev_ent, B, S, nsplit, (const int*)pad_cnt, rev_cnt);
     return mlsp_launch_status();
 }
 
@@ -237,23 +255,11 @@ static int launch_reverse(hipStream_t st, const int* idx, int B, int S, int N, i
 int launch_group_reverse(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_ent) {
     return launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent);
 }
-// the same without the padding slots; pad_cnt [B*S] = number of padding slots of every group (s > 0 with idx[i][s] == idx[i][0])
-__global__ __launch_bounds__(256) void group_pad_count_kernel(const int* __restrict__ idx, int G, int k, int* __restrict__ pad_cnt) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= G) return;
-    const int* r = idx + (size_t)g * k;
-    const int first = r[0];
-    int c = 0;
-    for (int s = 1; s < k; ++s) c += r[s] == first;
-    pad_cnt[g] = c;
-}
+// the same without the padding slots (the trailing copies of slot 0), and how many each group has
 int launch_group_reverse_compact(hipStream_t st, const int* idx, int B, int S, int N, int k, int* rev_off, int* rev_cnt, int* rev_ent,
                                  int* pad_cnt) {
     if (!rev_cnt || !pad_cnt) return MLSP_ERR_ARG;
-    const int rc = launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, 1, rev_cnt);
-    if (rc != MLSP_OK) return rc;
-    hipLaunchKernelGGL(group_pad_count_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, idx, B * S, k, pad_cnt);
-    return mlsp_launch_status();
+    return launch_reverse(st, idx, B, S, N, k, rev_off, rev_ent, pad_cnt, rev_cnt);
 }
 int launch_knn_reverse(hipStream_t st, const int* idx, int B, int N, int k, int* rev_off, int* rev_ent) {
     return launch_reverse(st, idx, B, N, N, k, rev_off, rev_ent);

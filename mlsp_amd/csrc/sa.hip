@@ -5,12 +5,11 @@
 // contraction), same tie rule (first index), same "first nsample in index order, padded with the first" selection.
 // The SA-MLP behind the grouping is the existing Linear+BN+act kernel family over the B*S*nsample edge rows.
 #include "common.h"
+#include "fps_plan.h"      // FPS_T / FPS_PPT, and which of the two FPS kernels a cloud size runs on
 #include <cfloat>
 
 // ---- FPS: one workgroup per cloud, the cloud in LDS, running distances in registers.
-// out[b][i] = index of the i-th sample; sample 0 is start[b].  N <= 8 * 1024.
-#define FPS_T 1024
-#define FPS_PPT 8
+// out[b][i] = index of the i-th sample; sample 0 is start[b].  N <= FPS_T * FPS_PPT = 8 * 1024 (fps_plan.h).
 __global__ __launch_bounds__(FPS_T) void fps_kernel(const float* __restrict__ xyz, int ldx, int N, int S, const int* __restrict__ start,
                                                     int* __restrict__ out) {
     extern __shared__ float fsm[];
@@ -129,7 +128,8 @@ __global__ __launch_bounds__(256) void fps_kernel2(const float* __restrict__ xyz
 }
 
 // ---- ball query: one wave per query; candidates scanned in index order, 64 at a time.
-// idx[b][i][0..nsample): the first nsample j with !(|q_i - x_j|^2 > r2), padded with the first hit.
+// idx[b][i][0..nsample): the first nsample j with !(|q_i - x_j|^2 > r2), padded with the first hit.  A query without a hit (the
+// reference would index out of range there) gets 0 in every slot: in range for the gathers downstream.
 __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ xyz, int ldx, const float* __restrict__ q, int ldq, int N,
                                                          int S, float r2, int nsample, int* __restrict__ idx) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -211,14 +211,15 @@ __global__ __launch_bounds__(256) void sa_group_bwd_kernel(const float* __restri
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 int launch_fps(hipStream_t st, const float* xyz, int ldx, int B, int N, int S, const int* start, int* out) {
-    if (!xyz || !start || !out || B <= 0 || N <= 0 || S <= 0 || S > N || ldx < 3 || N > FPS_T * FPS_PPT) return MLSP_ERR_ARG;
+    const int plan = fps_plan(N);
+    if (!xyz || !start || !out || B <= 0 || S <= 0 || S > N || ldx < 3 || plan == FPS_PLAN_NONE) return MLSP_ERR_ARG;
     size_t lds = ((size_t)3 * N + 32) * sizeof(float);
     if (lds > 150 * 1024) return MLSP_ERR_UNSUPPORTED;
     if (lds > 64 * 1024) {
         hipError_t e = mlsp_lds_limit((const void*)fps_kernel, lds);
         if (e != hipSuccess) return (int)e;
     }
-    if (N <= 2048 && N >= 64) {
+    if (plan == FPS_PLAN_KERNEL2) {
         const size_t lds2 = ((size_t)3 * ((N + 1) & ~1)) * sizeof(float) + 8 * sizeof(unsigned long long);
         hipLaunchKernelGGL(fps_kernel2, dim3(B), dim3(256), lds2, st, xyz, ldx, N, S, start, out);
         return mlsp_launch_status();
@@ -256,24 +257,26 @@ int launch_sa_group_bwd(hipStream_t st, const float* dG, int ldg, int col, int D
 // ---- kNN of QUERY points among REFERENCE points (ref != query): `square_distance` + argsort()[:, :, :k] of
 // pointnet_util.py:26-38,116-118 (knn=True grouping, :237-239 Msg) and the 3-NN of PointNetFeaturePropagation (:287-289);
 // also the shape of knn_cuda.KNN / the KNN calls of PointDA/model_utils.py:175,188.
-//   d(q, r) = fl( fl(-2 * dot(q, r) + |q|^2) + |r|^2 ),  dot an fmaf chain over the C <= 8 coordinates, norms (x0^2 + x1^2) + ...
+//   d(q, r) = sum over c of (q_c - r_c)^2 -- the reference's return statement (pointnet_util.py:36, PointDA/model_utils.py:531: the
+//   difference first; the docstring above it describes the expanded form, which its code does not compute): c ascending over the
+//   C <= 8 coordinates, ((dx*dx + dy*dy) + dz*dz) + ..., no contraction: for C = 3 the bits of ball_query_kernel's d and of torch's
+//   sum(-1).  Never negative, exactly 0 at coincident points (the 3-NN weights 1 / (d + 1e-8) rely on that: xyz2 is a subset of xyz1).
 //   order: d ascending, ties -> lower reference index; the k best, nearest first.
 // One thread per query with a sorted k-list in registers; the references stream through LDS in tiles of 256.
 template <int KMAX>
 __global__ __launch_bounds__(256) void knn_query_kernel(const float* __restrict__ ref, int ldr, int Nr, const float* __restrict__ qry,
                                                         int ldq, int Nq, int C, int k, int* __restrict__ idx, float* __restrict__ dist) {
     __shared__ float rs[256 * 8];
-    __shared__ float rn[256];
     const int b = blockIdx.y, tid = threadIdx.x, q = blockIdx.x * 256 + tid;
     const float* rb = ref + (size_t)b * Nr * ldr;
-    float qv[8], qn = 0.f;
+    float qv[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) qv[c] = 0.f;
     if (q < Nq) {
         const float* qp = qry + ((size_t)b * Nq + q) * ldq;
 #pragma unroll
         for (int c = 0; c < 8; ++c)
-            if (c < C) { qv[c] = qp[c]; qn = c == 0 ? qv[0] * qv[0] : qn + qv[c] * qv[c]; }
+            if (c < C) qv[c] = qp[c];
     }
     float bv[KMAX];
     int bi[KMAX];
@@ -282,22 +285,16 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float* __restrict_
     for (int r0 = 0; r0 < Nr; r0 += 256) {
         __syncthreads();
         const int r = r0 + tid;
-        float nn = 0.f;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float v = (r < Nr && c < C) ? rb[(size_t)r * ldr + c] : 0.f;
-            rs[tid * 8 + c] = v;
-            if (c < C) nn = c == 0 ? v * v : nn + v * v;
-        }
-        rn[tid] = nn;
+        for (int c = 0; c < 8; ++c) rs[tid * 8 + c] = (r < Nr && c < C) ? rb[(size_t)r * ldr + c] : 0.f;
         __syncthreads();
         const int lim = min(256, Nr - r0);
         for (int j = 0; j < lim; ++j) {
-            float dot = 0.f;
+            const float d0 = qv[0] - rs[j * 8];
+            float d = d0 * d0;
 #pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (c < C) dot = fmaf(qv[c], rs[j * 8 + c], dot);
-            const float d = (-2.f * dot + qn) + rn[j];
+            for (int c = 1; c < 8; ++c)
+                if (c < C) { const float dc = qv[c] - rs[j * 8 + c]; d = d + dc * dc; }
             const int jj = r0 + j;
             // strict: an equal distance with a higher index stays out.  The first KMAX references (a uniform test) enter whatever their
             // distance: a NaN or overflowed distance counts as +inf -- held as FLT_MAX in the list, below the INFINITY of a slot that is
@@ -548,9 +545,10 @@ __global__ __launch_bounds__(256) void sa_fold_bwd_point_kernel(const float* __r
     f32x4 m1 = {0, 0, 0, 0}, m2 = {0, 0, 0, 0};
     if (m1v) { m1 = *(const f32x4*)(m1v + c); m2 = *(const f32x4*)(m2v + c); }
     const f32x4 uq = *(const f32x4*)(u + (size_t)j * C + c);
-    // compact lists (rev_cnt / pad_cnt, mlsp_group_reverse_compact): the padding slots of a ball-query group are not listed; their
-    // rows are identical (same u_j, same w_i, same incoming gradient), so a group's slot-0 entry also adds pad_cnt times the row of its
-    // LAST slot -- without this a point that pads many groups collects hundreds of entries
+    // compact lists (rev_cnt / pad_cnt, mlsp_group_reverse_compact): the padding slots of a group -- its trailing run of copies of slot 0,
+    // what a ball query appends -- are not listed; their rows are identical (same u_j, same w_i, same incoming gradient) and the LAST slot
+    // is one of them whenever pad_cnt > 0, so a group's slot-0 entry also adds pad_cnt times the row of its last slot -- without this a
+    // point that pads many groups collects hundreds of entries
     const int e0 = rev_off[j], e1 = rev_cnt ? e0 + rev_cnt[j] : rev_off[j + 1];
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (pad_cnt) {

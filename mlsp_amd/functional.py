@@ -2448,8 +2448,9 @@ class _Interp3Add(Function):
 
 def interp3_add(feat, add, idx=None, dist=None):
     """add [B, N, C] + sum_j w_j feat[b, idx[b, n, j]]: feat [B, S, C], idx int32 [B, N, 3] (entries in [0, S)) and dist float32 [B, N, 3] as
-    knn_point(3, ..., return_dist=True) leaves them, w = 1 / (dist + 1e-8) normalised over the three (pointnet_util.py:287-294 followed by
-    hengshuang_model.py:46) -> [B, N, C].  S == 1: every row receives the cloud's one source row, idx / dist are not read.  Gradients to
+    knn_point(3, ..., return_dist=True) leaves them (dist = sum_c (q_c - r_c)^2, difference first: >= 0, and exactly 0 where a point is
+    one of the sampled ones, so no weight is ever negative), w = 1 / (dist + 1e-8) normalised over the three (pointnet_util.py:287-294
+    followed by hengshuang_model.py:46) -> [B, N, C].  S == 1: every row receives the cloud's one source row, idx / dist are not read.  Gradients to
     feat (over the reverse index, no atomics) and add (dout itself)."""
     _lib.require_gpu(feat, add, idx, dist)
     if feat.shape[1] != 1:

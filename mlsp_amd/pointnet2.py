@@ -75,8 +75,11 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
 
 
 def knn_point(k, xyz, new_xyz, return_dist=False):
-    """`square_distance(new_xyz, xyz).argsort()[:, :, :k]` (pointnet_util.py:26-38,116-118) without the [B,S,N] matrix:
-    xyz [B,N,3] reference points, new_xyz [B,S,3] queries -> idx [B,S,k] int64, nearest first (ties -> lower index)."""
+    """`square_distance(new_xyz, xyz).argsort()[:, :, :k]` (pointnet_util.py:22-36,116-118) without the [B,S,N] matrix:
+    xyz [B,N,3] reference points, new_xyz [B,S,3] queries -> idx [B,S,k] int64, nearest first (ties -> lower index).
+    The distance is the one `square_distance` above returns, sum_c (q_c - r_c)^2 with the difference taken first (the reference's return
+    statement, :36) -- never negative, exactly 0 at coincident points -- not the expanded -2 q.r + |q|^2 + |r|^2 of its docstring;
+    `return_dist` hands those values out [B,S,k] float32 (+inf where a distance is not finite)."""
     lib = _lib.load()
     x, q = _xyz_rows(xyz), _xyz_rows(new_xyz)
     _lib.require_gpu(x, q)

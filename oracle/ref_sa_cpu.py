@@ -91,10 +91,10 @@ def sa_forward(params, buffers, cfg, xyz, points, start, training=True, momentum
 
 # --------------------------------------------------------------------------- round 2: knn grouping, multi-scale grouping, feature propagation
 def square_distance(src, dst):
-    """pointnet_util.py:22-38: -2 src.dst^T + |src|^2 + |dst|^2, in that association."""
-    d = -2 * torch.matmul(src, dst.permute(0, 2, 1))
-    d = d + torch.sum(src ** 2, -1).unsqueeze(-1)
-    return d + torch.sum(dst ** 2, -1).unsqueeze(1)
+    """pointnet_util.py:36 (and PointDA/model_utils.py:531): sum((src[:, :, None] - dst[:, None]) ** 2, -1) -- the difference first, then
+    the squares summed over the coordinates in ascending order.  Never negative, exactly 0 at coincident points.  (The docstring above
+    that return statement in the reference describes the expanded form -2 src.dst^T + |src|^2 + |dst|^2; its code does not compute it.)"""
+    return torch.sum((src[:, :, None] - dst[:, None]) ** 2, dim=-1)
 
 
 def knn_group(k, xyz, new_xyz):

@@ -20,16 +20,19 @@ SlicePath = collections.namedtuple("SlicePath", "b part nsplit dper nd one_trip 
 
 
 def _keep(idx, skip_pad):
-    """[B][S][k] bool: the slots the lists hold (skip_pad: not the slots s > 0 that repeat the group's slot 0)"""
+    """[B][S][k] bool: the slots the lists hold (skip_pad: not the group's padding -- its TRAILING run of slots s > 0 that repeat slot 0,
+    what a ball query appends; a repeat of slot 0 further up a row is an ordinary slot)"""
     keep = np.ones(idx.shape, dtype=bool)
     if skip_pad:
-        keep[:, :, 1:] = idx[:, :, 1:] != idx[:, :, :1]
+        differs = idx[:, :, 1:] != idx[:, :, :1]
+        # a slot is kept iff it, or some slot after it, differs from slot 0
+        keep[:, :, 1:] = np.flip(np.logical_or.accumulate(np.flip(differs, -1), -1), -1)
     return keep
 
 
 def reverse_reference(idx, N, skip_pad=False):
     """The exact reverse index of idx [B][S][k] (values in [0, N)): per cloud and destination j the entries (i << 8) | s with
-    idx[b][i][s] == j, ascending; skip_pad leaves out the slots s > 0 whose index equals the group's slot 0.
+    idx[b][i][s] == j, ascending; skip_pad leaves out every group's trailing run of slots s > 0 whose index equals its slot 0.
     -> Reverse(rev_off [B*N+1] (a cloud's lists start at b*S*k; rev_off[B*N] = B*S*k), rev_ent [B*S*k] (-1 where no list lies),
     listed [B*S*k] bool (the positions that belong to a list), rev_cnt [B*N] list lengths, pad_cnt [B*S] skipped slots per group)."""
     idx = np.asarray(idx)
@@ -134,6 +137,14 @@ def _uniform(c, rng):
     return rng.integers(0, c.N, size=(c.B, c.S, c.k)).astype(np.int32)
 
 
+def _some_trailing_pads(c, idx):
+    """every 7th group of a wide case ends in a copy of its slot 0: padding (a trailing run of length >= 1) in every slice, so that the
+    compact index has slots to leave out on every path -- chance repeats of slot 0 further up a row are ordinary slots"""
+    if c.k >= 12:
+        idx[:, ::7, -1] = idx[:, ::7, 0]
+    return idx
+
+
 def _columns_mod64(c, rng, ncol):
     idx = _uniform(c, rng)
     i, s = np.arange(c.S)[:, None], np.arange(ncol)[None, :]
@@ -146,7 +157,7 @@ def case_idx(name):
     c = CASES[name]
     rng = np.random.default_rng(0)
     if c.kind == "uniform":
-        return _uniform(c, rng)
+        return _some_trailing_pads(c, _uniform(c, rng))
     if c.kind == "hubs":                       # D: column 0 -> point 7, columns 1..8 -> point 150
         idx = _uniform(c, rng)
         idx[:, :, 0] = 7
@@ -155,9 +166,9 @@ def case_idx(name):
     if c.kind == "one_point":                  # E
         return np.full((c.B, c.S, c.k), 37, dtype=np.int32)
     if c.kind == "mod64x12":                   # G
-        return _columns_mod64(c, rng, 12)
+        return _some_trailing_pads(c, _columns_mod64(c, rng, 12))
     if c.kind == "mod64x20":                   # H
-        return _columns_mod64(c, rng, 20)
+        return _some_trailing_pads(c, _columns_mod64(c, rng, 20))
     assert c.kind == "ball_like"
     return ball_like(rng, c.B, c.S, c.N, c.k)
 

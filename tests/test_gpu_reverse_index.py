@@ -313,8 +313,8 @@ def test_sa_fold_bwd_both_index_forms_vs_float64(dev, C, ns, training):
 
 # ----------------------------------------------------------------------------- e. the query kNN's index contract
 def _grid(shape, gen):
-    """coordinates on the grid of eighths in [-1, 1]: every product and sum of the distance is exact in fp32, whatever its association --
-    the kernel's fmaf chain, the oracle's matmul and the host restatement compute the same numbers, and exact ties abound"""
+    """coordinates on the grid of eighths in [-1, 1]: every difference, square and sum of the distance is exact in fp32, whatever its
+    association -- the kernel, the oracle and the host restatement compute the same numbers, and exact ties abound"""
     return torch.randint(-8, 9, shape, generator=gen).float() / 8
 
 
@@ -343,7 +343,7 @@ def test_knn_point_indices_stay_in_range_on_non_finite_input(dev, C, k):
             x[1, k - 1:, C - 1] = nan
             rows_ok[1] = False
         else:
-            x[1, 17, 0] = 1e30                                 # finite, but its squared norm overflows: d = +inf in fp32
+            x[1, 17, 0] = 1e30                                 # finite, but its squared difference overflows: d = +inf in fp32
         got, dist = p2.knn_point(k, x.to(dev), q.to(dev), return_dist=True)
         got, dist = got.cpu(), dist.cpu().numpy()
         assert int(got.min()) >= 0 and int(got.max()) < Nr, (kind, int(got.min()), int(got.max()))
@@ -351,7 +351,7 @@ def test_knn_point_indices_stay_in_range_on_non_finite_input(dev, C, k):
         assert torch.equal(got[rows_ok], want[rows_ok]), kind
         xn, qn = x.numpy(), q.numpy()
         with np.errstate(all="ignore"):
-            d = (-2 * np.einsum("bqc,brc->bqr", qn, xn) + (qn * qn).sum(-1)[:, :, None]) + (xn * xn).sum(-1)[:, None, :]
+            d = ((qn[:, :, None, :] - xn[:, None, :, :]) ** 2).sum(-1)          # the kernel's form: the difference first
         assert d.dtype == np.float32
         d = np.where(np.isfinite(d), d, np.float32(np.inf))
         order = np.argsort(d, axis=-1, kind="stable")[:, :, :k]

@@ -39,20 +39,25 @@ def test_constants_match_the_kernel_source():
 def test_reference_on_a_hand_written_example():
     """B = 1, S = 2 groups of k = 3 over N = 4 points: group 0 = (2, 0, 2), group 1 = (1, 1, 2).
     Entries (i << 8) | s:  point 0 <- (0,1) = 1;  point 1 <- (1,0) = 256, (1,1) = 257;  point 2 <- (0,0) = 0, (0,2) = 2, (1,2) = 258;
-    point 3 <- nothing.  With skip_pad the slots that repeat their group's slot 0 go: (0,2) and (1,1)."""
+    point 3 <- nothing.  With skip_pad a group's TRAILING repeats of its slot 0 go: (0,2).  (1,1) repeats slot 0 too, but slot (1,2) after
+    it does not: an ordinary slot, which stays listed -- the consumer replaces the skipped slots by multiples of the group's LAST row, and
+    the last row of group 1 belongs to point 2.  (Until the padding was defined as the trailing run, this example pinned (1,1) as skipped.)"""
     idx = np.array([[[2, 0, 2], [1, 1, 2]]], dtype=np.int32)
     r = rr.reverse_reference(idx, 4)
     assert r.rev_off.tolist() == [0, 1, 3, 6, 6]
     assert r.rev_ent.tolist() == [1, 256, 257, 0, 2, 258]
     assert r.listed.all() and r.rev_cnt.tolist() == [1, 2, 3, 0] and r.pad_cnt.tolist() == [0, 0]
     r = rr.reverse_reference(idx, 4, skip_pad=True)
-    assert r.rev_off.tolist() == [0, 1, 2, 4, 6]
-    assert r.rev_ent.tolist() == [1, 256, 0, 258, -1, -1]
-    assert r.listed.tolist() == [True] * 4 + [False] * 2 and r.rev_cnt.tolist() == [1, 1, 2, 0] and r.pad_cnt.tolist() == [1, 1]
+    assert r.rev_off.tolist() == [0, 1, 3, 5, 6]
+    assert r.rev_ent.tolist() == [1, 256, 257, 0, 258, -1]
+    assert r.listed.tolist() == [True] * 5 + [False] and r.rev_cnt.tolist() == [1, 2, 2, 0] and r.pad_cnt.tolist() == [1, 0]
     # a second cloud starts at b * S * k whatever the first one left unfilled
     r = rr.reverse_reference(np.concatenate([idx, idx[:, ::-1]]), 4, skip_pad=True)
-    assert r.rev_off.tolist() == [0, 1, 2, 4, 6, 7, 8, 10, 12]
-    assert r.rev_ent.tolist() == [1, 256, 0, 258, -1, -1, 257, 0, 2, 256, -1, -1] and r.pad_cnt.tolist() == [1, 1, 1, 1]
+    assert r.rev_off.tolist() == [0, 1, 3, 5, 6, 7, 9, 11, 12]
+    assert r.rev_ent.tolist() == [1, 256, 257, 0, 258, -1, 257, 0, 1, 2, 256, -1] and r.pad_cnt.tolist() == [1, 0, 0, 1]
+    # a row that is one point throughout is slot 0 plus k - 1 padding slots; a lone repeat in the middle is not padding
+    r = rr.reverse_reference(np.array([[[3, 3, 3], [3, 3, 0]]], dtype=np.int32), 4, skip_pad=True)
+    assert r.pad_cnt.tolist() == [2, 0] and r.rev_cnt.tolist() == [1, 0, 0, 3]
 
 
 def test_ball_like_groups():

@@ -119,9 +119,20 @@ def test_feature_propagation_oracle_matches_reference(name):
     p1 = torch.from_numpy(g["points1"]).requires_grad_(True)
     p2 = torch.from_numpy(g["points2"]).requires_grad_(True)
     out, nb = sa.fp_forward(params, buffers, [16, 12], torch.from_numpy(g["xyz1"]), torch.from_numpy(g["xyz2"]), p1, p2)
-    # the interpolation weights 1 / (d + 1e-8) amplify the rounding of d = -2ab + a^2 + b^2 for near-coincident points (d ~ 1e-4)
-    np.testing.assert_allclose(out.detach().numpy(), g["out"], rtol=1e-4, atol=1e-4)
+    # The oracle's distance is the reference's return statement, sum((a - b)^2) with the difference first (pointnet_util.py:36), and with it
+    # the oracle IS the reference on these fixtures.  Measured max |oracle - golden| over both fixtures, at 2, 3, 4, 6, 8 and 16 threads:
+    #   output 0.0, d_points1 / d_points2 0.0, BatchNorm buffers 0.0  -> compared exactly (three times the measured distance is 0);
+    #   parameter gradients 0.0 at 8 and 16 threads, up to 6.1e-5 (on entries up to 1.8e2) at 2 .. 6 threads, where the conv backward splits
+    #   its sum over the 400 rows differently  -> atol = 1.8e-4 (three times the largest), rtol = 0.
+    # (With the expanded form -2ab + a^2 + b^2 that this oracle used to compute, the output sat 2.6e-5 away and this test allowed 1e-4 .. 2e-3
+    # throughout: the weights 1 / (d + 1e-8) amplify that form's rounding residue at the coincident points of xyz2 within xyz1, where the
+    # direct form gives d = 0 exactly.  On ONE thread torch's BatchNorm sums in another order -- the output moves by 1.2e-6 -- and the older
+    # tests of this file miss their bars as well.)
+    np.testing.assert_allclose(out.detach().numpy(), g["out"], rtol=0, atol=0)
     (out * torch.from_numpy(g["wgt"])).sum().backward()
-    np.testing.assert_allclose(p1.grad.numpy(), g["d_points1"], rtol=1e-3, atol=1e-4)
-    np.testing.assert_allclose(p2.grad.numpy(), g["d_points2"], rtol=1e-3, atol=1e-4)
-    check_grads_and_buffers(g, params, nb, rtol=2e-3, atol=5e-4)
+    np.testing.assert_allclose(p1.grad.numpy(), g["d_points1"], rtol=0, atol=0)
+    np.testing.assert_allclose(p2.grad.numpy(), g["d_points2"], rtol=0, atol=0)
+    for k, v in params.items():
+        np.testing.assert_allclose(v.grad.numpy(), g["grad/" + k], rtol=0, atol=1.8e-4, err_msg=k)
+    for k, v in nb.items():
+        np.testing.assert_allclose(v.numpy(), g["state_after/" + k], rtol=0, atol=0, err_msg=k)
