@@ -704,6 +704,38 @@ int mlsp_batch_prepare_f32(const float* raw, int ld, int B, int Nmax, const int*
                            const double* Rpre, const double* Rpost, const double* noise, double sigma, double clip, float* out, int* idx,
                            mlsp_stream_t stream);
 
+/* Segmentation supervision (PointSegDA/trainer.py:221-233, 253-258: nn.CrossEntropyLoss on logits.permute(0, 2, 1), logits.max(dim=2)[1],
+ * seg_metrics) from one read of the logits (segsup.hip).  logits fp32 [B][N][C], contiguous in C, row pitch ld >= C (cloud pitch N ld);
+ * labels int64 [B][N].  Limits: 1 <= C <= 64, B >= 1, N >= 1, B N < 2^31 -- anything else returns MLSP_ERR_UNSUPPORTED and launches
+ * nothing.  Rows are read as 16-byte quads where C % 4 == 0, ld % 4 == 0 and logits is 16-byte aligned, element by element otherwise.
+ * No entry reaches a matrix core or takes a product mode.  Integer counters are added with LDS atomics; every floating-point sum is
+ * taken in double in a fixed order (points of a thread, threads of a chunk, chunks of a cloud, clouds of the batch, each ascending): the
+ * results are bit-identical run to run.
+ *
+ * A label outside [0, C) -- torch's ignore_index -100 among them -- is never used as an index: its point adds nothing to the loss, to the
+ * valid-point count or to the metric counters, and its gradient row is 0; its lse and pred are still written.  (torch raises for such a
+ * label other than ignore_index.)
+ *
+ * Forward, two launches: lse [B][N] double = m + log sum_c exp(x_c - m) (exps in fp32, sum and log in double); loss_pt [B][N] fp32
+ * (nullable) = lse - x[label], 0 at ignored points; pred [B][N] int64 = the index of the maximum, the LOWEST index on ties (a NaN logit
+ * gives a NaN loss and a pred somewhere in [0, C)); stats [B + 1][5] double: row b = loss sum | mIoU | accuracy | valid points | mean
+ * loss of cloud b, row B = mean loss over the batch's valid points | their number | 0 | 0 | 0; mean [1] fp32 (nullable) = the mean loss rounded once.
+ * mIoU: the mean over the classes with true[c] + pred[c] > 0 of tp[c] / (true[c] + pred[c] - tp[c]) in double from integer counts, the
+ * quotients taken in ascending c and added in the order of numpy's add.reduce (eight running sums from eight classes on) --
+ * sklearn.metrics.jaccard_score(average='macro') bit for bit; accuracy = correct / valid.  A cloud without a valid
+ * point has NaN metrics; a batch without one a NaN mean.  ws: at least mlsp_seg_workspace_bytes(B, N, C) bytes (0: shape refused).
+ * Backward, one launch: dlogits [B][N][C] (contiguous, written completely) = (exp(x - lse) - [c == label]) g with g = g_pt[b][n]
+ * (reduction 'none') or g_mean[0] / stats[B][1] (reduction 'mean'); exactly one of g_pt and g_mean is non-NULL.
+ * Metrics alone: labels and preds int64 [B][N] -> stats as above with the loss fields 0, through the same counters and finaliser.  A pred
+ * outside [0, C) at a valid point counts for its label's class and as a miss, and for no predicted class. */
+size_t mlsp_seg_workspace_bytes(int B, int N, int C);
+int mlsp_seg_ce_fwd_f32(const float* logits, int ld, const int64_t* labels, int B, int N, int C, double* lse, float* loss_pt, int64_t* pred,
+                        double* stats, float* mean, void* ws, size_t ws_bytes, mlsp_stream_t stream);
+int mlsp_seg_ce_bwd_f32(const float* logits, int ld, const int64_t* labels, const double* lse, int B, int N, int C, const float* g_pt,
+                        const float* g_mean, const double* stats, float* dlogits, mlsp_stream_t stream);
+int mlsp_seg_metrics_i64(const int64_t* labels, const int64_t* preds, int B, int N, int C, double* stats, void* ws, size_t ws_bytes,
+                         mlsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,10 @@ SIGNATURES = {
     "mlsp_cloud_mean_fwd_f32": [_P, _I, _I, _I, _P, _P],
     "mlsp_cloud_mean_bwd_f32": [_P, _I, _I, _I, _P, _P],
     "mlsp_batch_prepare_f32": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P],
+    "mlsp_seg_workspace_bytes": [_I, _I, _I],
+    "mlsp_seg_ce_fwd_f32": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "mlsp_seg_ce_bwd_f32": [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "mlsp_seg_metrics_i64": [_P, _P, _I, _I, _I, _P, _P, _SZ, _P],
     "mlsp_radius_count_f32": [_P, _I, _I, _I, _F, _I, _P, _P],
     "mlsp_knn_normals_f32": [_P, _I, _P, _I, _I, _I, _P, _P],
     "mlsp_knn_query_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -179,7 +183,7 @@ class Defer(_c.Structure):
 
 
 _RESTYPE = {"mlsp_strerror": _c.c_char_p, "mlsp_workspace_bytes": _SZ, "mlsp_gn_edge_workspace_bytes": _SZ,
-            "mlsp_thin_in_workspace_bytes": _SZ}
+            "mlsp_thin_in_workspace_bytes": _SZ, "mlsp_seg_workspace_bytes": _SZ}
 
 _lib = None
 

@@ -1182,4 +1182,20 @@ int mlsp_batch_prepare_f32(const float* raw, int ld, int B, int Nmax, const int*
     return launch_batch_prepare(st, raw, ld, B, Nmax, counts, S, flags, start, Rpre, Rpost, noise, sigma, clip, out, idx);
 }
 
+size_t mlsp_seg_workspace_bytes(int B, int N, int C) { return seg_ws_bytes(B, N, C); }
+int mlsp_seg_ce_fwd_f32(const float* logits, int ld, const int64_t* labels, int B, int N, int C, double* lse, float* loss_pt, int64_t* pred,
+                        double* stats, float* mean, void* ws, size_t ws_bytes, mlsp_stream_t st) {
+    Workspace wsp(ws, ws_bytes);
+    return launch_seg_ce_fwd(st, logits, ld, (const long long*)labels, B, N, C, lse, loss_pt, (long long*)pred, stats, mean, wsp);
+}
+int mlsp_seg_ce_bwd_f32(const float* logits, int ld, const int64_t* labels, const double* lse, int B, int N, int C, const float* g_pt,
+                        const float* g_mean, const double* stats, float* dlogits, mlsp_stream_t st) {
+    return launch_seg_ce_bwd(st, logits, ld, (const long long*)labels, lse, B, N, C, g_pt, g_mean, stats, dlogits);
+}
+int mlsp_seg_metrics_i64(const int64_t* labels, const int64_t* preds, int B, int N, int C, double* stats, void* ws, size_t ws_bytes,
+                         mlsp_stream_t st) {
+    Workspace wsp(ws, ws_bytes);
+    return launch_seg_metrics(st, (const long long*)labels, (const long long*)preds, B, N, C, stats, wsp);
+}
+
 }  // extern "C"

@@ -324,3 +324,13 @@ int launch_cloud_mean_bwd(hipStream_t st, const float* dOut, int B, int N, int C
 // counts / flags: HOST arrays [B] (nullable); start / Rpre / Rpost / noise: device, nullable where no cloud's flags or count ask for them
 int launch_batch_prepare(hipStream_t st, const float* raw, int ld, int B, int Nmax, const int* counts, int S, const int* flags, const int* start,
                          const double* Rpre, const double* Rpost, const double* noise, double sigma, double clip, float* out, int* idx);
+
+// segsup.hip
+size_t seg_ws_bytes(int B, int N, int C);                                  // what the two launchers below take from `ws` (0: shape outside the limits)
+// loss_pt / mean nullable; stats [B + 1][5] doubles: per cloud loss sum | mIoU | accuracy | valid points | mean loss, row B mean loss | valid points | 0 ..
+int launch_seg_ce_fwd(hipStream_t st, const float* logits, int ld, const long long* labels, int B, int N, int C, double* lse, float* loss_pt,
+                      long long* pred, double* stats, float* mean, Workspace& ws);
+int launch_seg_metrics(hipStream_t st, const long long* labels, const long long* preds, int B, int N, int C, double* stats, Workspace& ws);
+// exactly one of g_pt [B N] (reduction 'none') and g_mean [1] (reduction 'mean', with the forward's stats)
+int launch_seg_ce_bwd(hipStream_t st, const float* logits, int ld, const long long* labels, const double* lse, int B, int N, int C,
+                      const float* g_pt, const float* g_mean, const double* stats, float* dlogits);

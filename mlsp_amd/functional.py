@@ -2495,6 +2495,108 @@ def cloud_mean(X, B, N):
     return _CloudMean.apply(X, int(B), int(N))
 
 
+_SEG_NEEDS = "needs fp32 logits [B, N, C] with 1 <= C <= 64, B >= 1, N >= 1, B * N < 2**31 and int64 labels [B, N]"
+
+
+def _seg_rows(logits):
+    """logits itself where the kernels can read it in place -- [B, N, C] with unit class stride, a row pitch of at least C and clouds N rows
+    apart -- else one contiguous copy"""
+    B, N, C = logits.shape
+    if C > 0 and (C == 1 or logits.stride(2) == 1) and (N == 1 or logits.stride(1) >= C) and \
+            (B == 1 or logits.stride(0) == N * (logits.stride(1) if N > 1 else C)):
+        return logits, (logits.stride(1) if N > 1 else C)
+    return logits.contiguous(), C
+
+
+def _seg_stats(B, device):
+    return torch.empty((B + 1, 5), dtype=torch.float64, device=device)
+
+
+class _SegCE(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, reduction):
+        lib = _lib.load()
+        _lib.require_gpu(logits, labels)
+        if logits.dim() != 3 or logits.dtype != torch.float32 or labels.dtype != torch.int64 or tuple(labels.shape) != tuple(logits.shape[:2]):
+            raise _lib.MlspLibraryError("seg_cross_entropy: logits %s %s, labels %s %s (%s)"
+                                        % (tuple(logits.shape), logits.dtype, tuple(labels.shape), labels.dtype, _SEG_NEEDS))
+        x, ld = _seg_rows(logits.detach())
+        labels = labels.contiguous()
+        B, N, C = x.shape
+        dev = x.device
+        lse = torch.empty((B, N), dtype=torch.float64, device=dev)
+        preds = torch.empty((B, N), dtype=torch.int64, device=dev)
+        loss_pt = torch.empty((B, N), dtype=torch.float32, device=dev) if reduction == "none" else None
+        mean = torch.empty((), dtype=torch.float32, device=dev)
+        stats = _seg_stats(B, dev)
+        ws, wsn = _lib.workspace_of(dev, lib.mlsp_seg_workspace_bytes(B, N, C))
+        _check_supported(lib.mlsp_seg_ce_fwd_f32(x.data_ptr(), ld, labels.data_ptr(), B, N, C, lse.data_ptr(), _lib.ptr(loss_pt), preds.data_ptr(),
+                                                 stats.data_ptr(), mean.data_ptr(), ws, wsn, _lib.stream()), "mlsp_seg_ce_fwd_f32", _SEG_NEEDS)
+        ctx.save_for_backward(x, labels, lse, stats)
+        ctx.ld, ctx.reduction = ld, reduction
+        cloud = stats[:B]
+        outs = (loss_pt if reduction == "none" else mean, preds, cloud[:, 1], cloud[:, 2], cloud[:, 4])
+        ctx.mark_non_differentiable(*outs[1:])
+        ctx.set_materialize_grads(False)                         # (else every backward fills four zero tensors for the outputs without a gradient)
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gloss, *unused):
+        if gloss is None:
+            return None, None, None
+        lib = _lib.load()
+        x, labels, lse, stats = ctx.saved_tensors
+        B, N, C = x.shape
+        gloss = gloss.contiguous().float()
+        g_pt, g_mean = (gloss, None) if ctx.reduction == "none" else (None, gloss)
+        dlogits = torch.empty((B, N, C), dtype=torch.float32, device=x.device)
+        _check_supported(lib.mlsp_seg_ce_bwd_f32(x.data_ptr(), ctx.ld, labels.data_ptr(), lse.data_ptr(), B, N, C, _lib.ptr(g_pt), _lib.ptr(g_mean),
+                                                 stats.data_ptr(), dlogits.data_ptr(), _lib.stream()), "mlsp_seg_ce_bwd_f32", _SEG_NEEDS)
+        return dlogits, None, None
+
+
+def seg_cross_entropy(logits, labels, reduction="mean", with_metrics=False):
+    """nn.CrossEntropyLoss on segmentation logits [B, N, C] (fp32, classes contiguous; a row pitch above C is read in place) with int64
+    labels [B, N]: the mean over the valid points, or the per-point loss [B, N] for reduction='none'.  with_metrics=True returns
+    (loss, preds [B, N] int64, miou [B] float64, acc [B] float64, per_cloud_loss [B] float64) from the same pass over the logits: preds
+    = logits.max(dim=2)[1] (the lowest index on ties), miou = sklearn's jaccard_score(average='macro') of every cloud, acc the fraction of
+    its valid points predicted right, per_cloud_loss the mean loss of its valid points.  Everything stays on the device; only the loss
+    carries a gradient.
+
+    A label outside [0, C) is ignored: no loss, no gradient, not among the valid points or the metric counts.  For -100 that is torch's
+    ignore_index default; for any other such value torch raises instead.  With every label ignored the mean loss is NaN, as in torch,
+    and so are a cloud's metrics.  Two HIP launches forward, one backward; bit-identical run to run."""
+    if reduction not in ("mean", "none"):
+        raise NotImplementedError("seg_cross_entropy: reduction=%r (the trainer uses 'mean' and 'none')" % (reduction,))
+    outs = _SegCE.apply(logits, labels, reduction)
+    return outs if with_metrics else outs[0]
+
+
+def _seg_metrics_stats(labels, preds, num_classes):
+    """the stats rows [B + 1, 5] float64 of mlsp_seg_metrics_i64 (include/mlsp_hip.h): column 1 mIoU, column 2 accuracy"""
+    lib = _lib.load()
+    _lib.require_gpu(labels, preds)
+    if labels.dim() != 2 or labels.shape != preds.shape or labels.dtype != torch.int64 or preds.dtype != torch.int64:
+        raise _lib.MlspLibraryError("seg_metrics_device: labels %s %s, preds %s %s (int64 [B, N] both)"
+                                    % (tuple(labels.shape), labels.dtype, tuple(preds.shape), preds.dtype))
+    labels, preds = labels.contiguous(), preds.contiguous()
+    B, N = labels.shape
+    stats = _seg_stats(B, labels.device)
+    ws, wsn = _lib.workspace_of(labels.device, lib.mlsp_seg_workspace_bytes(B, N, int(num_classes)))
+    _check_supported(lib.mlsp_seg_metrics_i64(labels.data_ptr(), preds.data_ptr(), B, N, int(num_classes), stats.data_ptr(), ws, wsn, _lib.stream()),
+                     "mlsp_seg_metrics_i64", _SEG_NEEDS)
+    return stats
+
+
+def seg_metrics_device(labels, preds, num_classes=64):
+    """(miou [B], acc [B]) float64 on the device from int64 labels and predictions [B, N]: per cloud sklearn's
+    jaccard_score(average='macro') and np.mean(labels == preds), from integer counts.  Class ids lie in [0, num_classes), num_classes <= 64; a
+    label outside is ignored (as in seg_cross_entropy), a prediction outside counts as a miss.  Two HIP launches, no host round trip."""
+    stats = _seg_metrics_stats(labels, preds, num_classes)
+    return stats[:-1, 1], stats[:-1, 2]
+
+
 def _gemm_row_view(t):
     """t itself where the kernels can read it in place -- a 2-D row view with unit column stride and a pitch of at least the row length --
     else a contiguous copy"""
